@@ -15,7 +15,14 @@ GPU) starts the N ranks itself (`python -m torch.distributed.run --nproc-per-nod
 relays rank 0's JSON line and exits with the children's status.  Under an external torchrun
 (WORLD_SIZE set) the process is one of the ranks.
 
-Rank 0 prints ONE JSON line (contract in the task statement), carrying
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: `value`, `ms_per_step` (wall
+time of the timed region / K), the rest of the contract's keys and the configuration -- nothing else is measured, and no
+HIP event sits in or behind the timed region.  `--dump-outputs DIR` writes, after the timed steps, what the last of them
+returned to its caller (the tags; `--workload train`: the loss and the updated parameters) as float32 DIR/<name>.npy;
+the inputs are seeded, so the same arguments give the same inputs on every run.
+
+`--full` adds everything else to the line, measured after the timed region (the kernel durations: HIP events inside it,
+or in 8 more steps right behind a short one), and writes the whole result beside it:
   roofline      the dominant kernel of the workload against the ceiling that really bounds it (see
                 roofline_for): HBM stream, Infinity-Cache/L2 row gather, f32 VALU or f32 MFMA; its mean
                 duration is measured with HIP events on the launch stream inside the timed region;
@@ -27,7 +34,8 @@ Rank 0 prints ONE JSON line (contract in the task statement), carrying
                 against the oracle AFTER the timed region, for whichever workload ran;
   other_configs (default invocation only) the other single-GPU BASELINE configs -- ifst_crf, decomp
                 (rank 50), fst4 -- and the decomposed model in the shape of the reference's shipped example
-                configurations (rank 250, farnn 2), timed for a few hundred ms each with their own roofline and parity.
+                configurations (rank 250, farnn 2), timed for a few hundred ms each with their own roofline and parity;
+  compact, pipelined, host_inclusive   the bit-packed form, two batches in flight, CPU tensors in and out (never `value`).
 """
 import argparse
 import json
@@ -158,7 +166,8 @@ def result_line(out):
     if len(str(cfg.get('workload', ''))) > 200:
         cfg['workload'] = cfg['workload'][:197] + '...'
     d['config'] = cfg
-    d['roofline'] = slim_roofline(out.get('roofline', {}))
+    if out.get('roofline'):
+        d['roofline'] = slim_roofline(out['roofline'])
     cb = out.get('cpu_baseline')
     if cb:
         d['cpu_baseline'] = _pick(cb, ('value', 'unit', 'cores', 'kind', 'host_threads', 'cpu_quota_cores'))
@@ -210,6 +219,22 @@ def write_full(out):
         return None
 
 
+DUMP_CAP = 64 << 20        # bytes: all arrays of one --dump-outputs together
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: each array as float32 `path/<name>.npy`.  Should they exceed DUMP_CAP together, each array keeps a fixed,
+    seeded sample of its rows (the same arguments give the same sample, so two builds still compare entry for entry)."""
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        if total > DUMP_CAP and v.ndim > 0:
+            keep = max(1, v.shape[0] * DUMP_CAP // total)
+            v = v[np.sort(np.random.RandomState(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, k + '.npy'), v)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -248,8 +273,13 @@ def parse():
                     help='N > 0: capture N consecutive steps into one HIP graph and replay it (steps must be a '
                          'multiple of N); 0 = plain stream launches')
     ap.add_argument('--event-stride', type=int, default=-1,
-                    help='time the kernels of every N-th step with HIP events (0 = never; default: chosen from '
+                    help='--full: time the kernels of every N-th step with HIP events (0 = never; default: chosen from '
                          '--steps so that at least 8 launches are timed, at most every 16th step)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: per-kernel timing and roofline, the post-run oracle check, CPU baselines, '
+                         'the compact / pipelined / host-inclusive figures, the other single-GPU configs and the full result file')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32)')
     a = ap.parse_args()
     if a.states > 0:
         d_, v_, s_, c_ = WORKLOADS[a.workload]
@@ -864,7 +894,7 @@ def run_train(a, world, rank, dev, dist):
 
     for _ in range(max(a.warmup, 1)):
         step()
-    tc.set_profiling(1 if a.event_stride else 0)
+    tc.set_profiling(1 if a.full and a.event_stride else 0)
     tc.time()
     if world > 1:
         dist.barrier()
@@ -887,6 +917,20 @@ def run_train(a, world, rank, dev, dist):
         tok_total = int(lengths.sum())
     lib_ms, lib_n = tc.time()
     if rank == 0:
+        if a.dump_outputs:                      # what a caller of the step gets back: the loss and the updated parameters
+            write_outputs(a.dump_outputs, dict(loss=loss.detach().cpu(), **{'param_' + k: v.detach().cpu() for k, v in p.items()}))
+        out = {
+            'metric': 'trained tokens/sec @ batch=256, seqlen=64 (decomposed i-FST, one optimizer step per batch)',
+            'value': tok_total * a.steps / el, 'unit': 'tokens/s', 'n_gpus': world, 'steps': a.steps,
+            'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'config': {'workload': '{}{}: V={} S={} R={} K={}, batch {} x seqlen {} per GPU'.format(
+                           desc.replace('farnn 0', 'farnn {}'.format(a.farnn)), ' with the CRF loss' if a.crf else '', V, S, R, K, B, L),
+                       'valid_tokens_per_step': tok_total, 'padded_tokens_per_step': world * B * L,
+                       'parallelism': 'data parallel x{}{}'.format(world, ', one RCCL all-reduce of the gradients' if world > 1 else ''),
+                       'final_loss': float(loss.detach())},
+        }
+    if rank == 0 and a.full:
         tok_local = int(lengths.sum())
         # VALU flops of the library part per valid token: forward recurrence 2(4SR+2S^2) + scoring 2KS, the
         # backward pass about twice that (BPTT products + the parameter-gradient outer products), gates on top
@@ -898,26 +942,16 @@ def run_train(a, world, rank, dev, dist):
         flops = 3.0 * fwd * tok_local
         lib_s = (lib_ms / max(lib_n, 1)) * 1e-3
         achieved = flops / lib_s / 1e12 if lib_s > 0 else 0.0
-        out = {
-            'metric': 'trained tokens/sec @ batch=256, seqlen=64 (decomposed i-FST, one optimizer step per batch)',
-            'value': tok_total * a.steps / el, 'unit': 'tokens/s', 'n_gpus': world, 'steps': a.steps,
-            'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': '{}{}: V={} S={} R={} K={}, batch {} x seqlen {} per GPU'.format(
-                           desc.replace('farnn 0', 'farnn {}'.format(a.farnn)), ' with the CRF loss' if a.crf else '', V, S, R, K, B, L),
-                       'valid_tokens_per_step': tok_total, 'padded_tokens_per_step': world * B * L,
-                       'parallelism': 'data parallel x{}{}'.format(world, ', one RCCL all-reduce of the gradients' if world > 1 else ''),
-                       'final_loss': float(loss.detach())},
-            'roofline': {'bound': 'valu_f32', 'kernel': 'train_backward_kernel (+train_forward_kernel, train_loss_kernel, atb_*)',
-                         'achieved': achieved, 'peak': F32_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / F32_PEAK_TFLOPS,
-                         'traffic': None, 'algorithmic_flops_per_launch': flops,
-                         'kernel_avg_us': lib_s * 1e6, 'launches_timed': lib_n,
-                         'step_latency_us': lib_s * 1e6 / (2 * L),
-                         'note': 'the library part of the step is bound by the latency of 64 sequential recurrence '
-                                 'steps per direction (forward, then backward in time), not by bandwidth or flops'},
-        }
+        out['roofline'] = {'bound': 'valu_f32', 'kernel': 'train_backward_kernel (+train_forward_kernel, train_loss_kernel, atb_*)',
+                           'achieved': achieved, 'peak': F32_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / F32_PEAK_TFLOPS,
+                           'traffic': None, 'algorithmic_flops_per_launch': flops,
+                           'kernel_avg_us': lib_s * 1e6, 'launches_timed': lib_n,
+                           'step_latency_us': lib_s * 1e6 / (2 * L),
+                           'note': 'the library part of the step is bound by the latency of 64 sequential recurrence '
+                                   'steps per direction (forward, then backward in time), not by bandwidth or flops'}
         if world == 1 and not a.no_cpu_baseline and not a.crf and not a.farnn:
             out['cpu_baseline'] = train_cpu_baseline(p, beta, x, lengths, labels, a.cpu_seconds)
+    if rank == 0:
         print(result_line(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -1081,6 +1115,9 @@ def run_tagging(a, name, steps, warmup, world, rank, dev, dist, want_pipelined, 
 
     elapsed, (chain_ms, chain_n, score_ms, score_n) = timed_region(n_main, steps, warmup, event_stride)
     timed_how = timed_by[0]
+    if headline and a.dump_outputs and rank == 0:
+        # what the caller of the last timed step received: its tags (int32 [B, L], -1 at pads; N > 1: every rank's, gathered)
+        write_outputs(a.dump_outputs, {'tags': (og.last() if og is not None else tags_bufs[(steps - 1) % n_main]).cpu().numpy()})
     pipelined = None
     if want_pipelined and n_main == 1:
         # same K steps with two batches in flight (two streams, two handles): the score/decode kernel
@@ -1121,14 +1158,15 @@ def run_tagging(a, name, steps, warmup, world, rank, dev, dist, want_pipelined, 
                    'parallelism': 'batch-sharded x{} (weights replicated{}){}'.format(
                        world, ', RCCL all_gather of tag ids' if world > 1 else '',
                        ', {} batches in flight per GPU'.format(n_main) if n_main > 1 else '')},
-        'roofline': roofline_for(name, a, h, extras, tok_local, chain_avg_s, score_avg_s, chain_n),
     }
-    out['roofline']['timed_by'] = timed_how
+    if a.full:
+        out['roofline'] = roofline_for(name, a, h, extras, tok_local, chain_avg_s, score_avg_s, chain_n)
+        out['roofline']['timed_by'] = timed_how
     if pipelined:
         out['pipelined'] = {'streams': pipelined[0], 'value': tok_total * steps / pipelined[1],
                             'unit': 'tokens/s', 'ms_per_step': pipelined[1] / steps * 1e3,
                             'note': 'same K steps with two batches in flight on two HIP streams'}
-    if world == 1 and not a.no_parity:
+    if world == 1 and a.full and not a.no_parity:
         # the last timed step wrote tags_bufs[(steps - 1) % n_main] from batch (steps - 1) mod NBATCH (a graph: the last of its steps)
         last = last_written[(steps - 1) % n_main]
         got = tags_bufs[(steps - 1) % n_main].cpu().numpy()
@@ -1136,7 +1174,7 @@ def run_tagging(a, name, steps, warmup, world, rank, dev, dist, want_pipelined, 
         out['parity']['batch_checked'] = last
         if out['parity']['tags_equal'] is False:
             print('WARNING: {}: GPU results differ from the oracle'.format(name), file=sys.stderr)
-    if headline and world == 1 and name in ('ifst', 'synth512') and h.has_compact():
+    if headline and a.full and world == 1 and name in ('ifst', 'synth512') and h.has_compact():
         # the compact form (bit-packed blocks + active-state walk) reported SEPARATELY; the contract
         # number above stays fp32-dense.  Same batch, same handle; its tags must equal the dense kernel's.
         dense_tags = tags_bufs[(steps - 1) % n_main].clone()
@@ -1164,10 +1202,10 @@ def run_tagging(a, name, steps, warmup, world, rank, dev, dist, want_pipelined, 
                           'note': 'bit-packed transition blocks, walk over the non-zero state entries only; latency-bound '
                                   '(serial step chain), reported beside the fp32-dense contract number, never as it'}
         h.set_compact(False)
-    if headline and world == 1 and not a.no_cpu_baseline and name == 'ifst':
+    if headline and a.full and world == 1 and not a.no_cpu_baseline and name == 'ifst':
         out['cpu_baseline'] = cpu_baseline(extras, x, lengths, a.cpu_seconds)
         out['cpu_baseline_faithful'] = cpu_baseline_faithful(extras, x, lengths, min(a.cpu_seconds, 6.0))
-    if headline and world == 1 and name == 'ifst' and not a.no_parity:
+    if headline and a.full and world == 1 and name == 'ifst' and not a.no_parity:
         for hh in handles:
             hh.close()
         handles = []
@@ -1247,8 +1285,9 @@ def main():
 
     if a.workload == 'train':
         return run_train(a, world, rank, dev, dist)
-    stride = a.event_stride if a.event_stride >= 0 else auto_event_stride(a.steps, a.workload)
-    want_pipe = not a.no_pipelined and a.streams == 1 and a.workload != 'synth512'   # no second 63 GB replica
+    # a plain run times the steps and nothing else: no HIP events in or after the timed region, no second measurement
+    stride = 0 if not a.full else a.event_stride if a.event_stride >= 0 else auto_event_stride(a.steps, a.workload)
+    want_pipe = a.full and not a.no_pipelined and a.streams == 1 and a.workload != 'synth512'   # no second 63 GB replica
     res = run_tagging(a, a.workload, a.steps, a.warmup, world, rank, dev, dist, want_pipe, stride, True)
     if rank == 0:
         out = {'metric': 'tagged tokens/sec @ batch=256, seqlen=64; achieved HBM GB/s vs peak',
@@ -1260,7 +1299,7 @@ def main():
             out['gather'] = gather_info
         defaults = (a.batch, a.seqlen, a.rank, a.farnn, a.semiring, a.full_length, a.streams, a.graph) == \
                    (256, 64, 50, 0, 'sum', False, 1, 0)
-        if world == 1 and a.workload == 'ifst' and defaults and not a.no_other_configs:
+        if world == 1 and a.full and a.workload == 'ifst' and defaults and not a.no_other_configs:
             others = []
             for name, st, wu, over, label in OTHER_CONFIGS:
                 t0 = time.perf_counter()
@@ -1292,7 +1331,8 @@ def main():
                 others.append(r)
                 print(other_config_line(r), flush=True)       # its own line, BEFORE the result line
             out['other_configs'] = others
-        out['full'] = write_full(out)
+        if a.full:
+            out['full'] = write_full(out)
         print(result_line(out), flush=True)                   # the ONE result line: last on stdout, <= LINE_CAP bytes
     if world > 1:
         dist.barrier()

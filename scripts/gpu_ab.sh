@@ -3,7 +3,7 @@
 # a hang in A's first launch ends the script.  usage: gpu_ab.sh [pytest files...]
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/ab; rm -rf $O; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-other-configs --no-pipelined"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-pipelined"
 timeout 150 $B --steps 20 --warmup 5 > $O/A_driver_0.json 2>$O/err0.txt || { echo "first launch failed or hung (rc $?)"; tail -5 $O/err0.txt; exit 1; }
 if [ $# -gt 0 ]; then timeout 1200 python -m pytest "$@" -x -q -m gpu 2>&1 | tail -3; fi
 for rep in 1 2 3; do

@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT
 run() {
-  timeout 300 python bench.py --steps 300 --warmup 20 --no-pipelined --no-cpu-baseline --event-stride 4 $2 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --steps 300 --warmup 20 --no-pipelined --no-cpu-baseline --event-stride 4 $2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; print('$1 $2', 'tok/s %.3e' % d['value'], 'ms/step %.4f' % d['ms_per_step'], 'chain_us %.1f score_us %.1f' % (r['chain_avg_us'], r['score_decode_avg_us']))"
 }

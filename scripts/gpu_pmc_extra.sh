@@ -8,7 +8,7 @@ i=0
 for grp in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS"; do
   i=$((i+1))
   for wl in ifst ifst_crf decomp; do
-    rocprofv3 --pmc $grp --output-format csv -d $O/g${i}_$wl -- python3 bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/g${i}_$wl.log 2>&1
+    rocprofv3 --pmc $grp --output-format csv -d $O/g${i}_$wl -- python3 bench.py --full --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/g${i}_$wl.log 2>&1
   done
 done
 python3 - <<'PY'

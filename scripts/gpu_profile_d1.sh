@@ -2,12 +2,12 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/d1prof
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --workload decomp1 --steps 50 --warmup 5 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --workload decomp1 --steps 50 --warmup 5 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/stats.log 2>&1
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS" "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VMEM_RD"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --output-format csv -d $O/g${i} -- python3 bench.py --workload decomp1 --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/g${i}.log 2>&1
+  rocprofv3 --pmc $grp --output-format csv -d $O/g${i} -- python3 bench.py --full --workload decomp1 --steps 6 --warmup 2 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/g${i}.log 2>&1
 done
 python3 - <<'PY'
 import csv, glob, collections

@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/trace_crf
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload ifst_crf --steps 100 --warmup 10 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload ifst_crf --steps 100 --warmup 10 --no-cpu-baseline --no-pipelined --event-stride 0 > $O/log.txt 2>&1
 f=$(find $O -name '*_kernel_stats.csv' | head -1)
 python3 - "$f" <<'PY'
 import csv,sys

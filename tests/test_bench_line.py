@@ -7,6 +7,8 @@ import json
 import os
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -100,3 +102,19 @@ def test_no_fraction_above_one_when_the_split_model_is_beaten():
     d = json.loads(bench.result_line(full))
     assert d['roofline']['frac'] <= 1.0 and d['roofline']['model_falsified'] is True
     assert d['roofline']['frac_split'] > 1.0 and abs(d['roofline']['frac'] - d['roofline']['frac_all_l2']) < 1e-6
+
+
+def test_dumped_outputs_are_float32_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays; above the cap every array keeps the same fixed sample of its rows, the same on every run"""
+    src = {'tags': np.arange(64 * 32, dtype=np.int32).reshape(64, 32), 'loss': np.float64(1.5)}
+    bench.write_outputs(str(tmp_path / 'whole'), src)
+    assert np.array_equal(np.load(tmp_path / 'whole' / 'tags.npy'), src['tags'].astype(np.float32))
+    monkeypatch.setattr(bench, 'DUMP_CAP', 4096)
+    for run in ('a', 'b'):
+        bench.write_outputs(str(tmp_path / run), src)
+    tags, loss = np.load(tmp_path / 'a' / 'tags.npy'), np.load(tmp_path / 'a' / 'loss.npy')
+    assert tags.dtype == np.float32 and loss.dtype == np.float32 and loss == 1.5
+    assert tags.nbytes + loss.nbytes <= 4096 and tags.shape[1] == 32 and len(tags) > 0
+    rows = (tags[:, 0] // 32).astype(np.int64)
+    assert (np.diff(rows) > 0).all() and np.array_equal(tags, src['tags'][rows].astype(np.float32))
+    assert np.array_equal(tags, np.load(tmp_path / 'b' / 'tags.npy'))

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +25,7 @@ def test_bench_two_ranks_on_one_device(extra):
     env = dict(os.environ, FARNN_BENCH_ONE_DEVICE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5',
-           '--warmup', '2', '--no-cpu-baseline'] + extra
+           '--warmup', '2', '--no-cpu-baseline', '--full'] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -69,7 +70,7 @@ def test_bench_default_line_carries_every_single_gpu_config():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--full',
                         '--cpu-seconds', '2'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -107,6 +108,47 @@ def test_bench_default_line_carries_every_single_gpu_config():
     assert full['roofline']['l1_pipeline']['cycles_per_workgroup_step'] == 16 * 24 + 71 * 72 * 4 / 64
     assert abs(full['value'] - d['value']) <= 1e-5 * d['value']
 
+
+
+def test_bench_plain_run_dumps_what_its_last_step_returned(tmp_path):
+    """The plain invocation (no --full): the contract's keys and nothing measured beside the timed steps, and --dump-outputs
+    writes the tags the last of the --steps timed steps returned.  Two runs with the same arguments dump the same tags, and
+    they are the oracle's for the batch that step tagged (step i runs batch i mod 4, bench.batch_variants)."""
+    from oracle import c_port
+    from re2nn_seq_amd import synth
+    sys.path.insert(0, ROOT)
+    import bench
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        env.pop(k, None)
+    steps = 7
+    dumps = []
+    for run in range(2):
+        out = tmp_path / str(run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '2',
+                            '--dump-outputs', str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1 and lines[0].startswith('{"metric"'), r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d['steps'] == steps and d['warmup'] == 2 and d['n_gpus'] == 1 and d['unit'] == 'tokens/s' and d['dtype'] == 'f32'
+        assert d['higher_is_better'] is True and d['value'] > 0 and d['ms_per_step'] > 0
+        tok = d['config']['valid_tokens_per_step']
+        assert abs(d['value'] * d['ms_per_step'] * 1e-3 - tok) <= 1e-4 * tok      # value = tokens per step / step time
+        for k in ('roofline', 'parity', 'cpu_baseline', 'compact', 'pipelined', 'host_inclusive', 'other_configs_ms_per_step', 'full'):
+            assert k not in d, k
+        assert os.listdir(out) == ['tags.npy']
+        tags = np.load(out / 'tags.npy')
+        assert tags.dtype == np.float32 and tags.shape == (256, 64)
+        assert int((tags == -1).sum()) == d['config']['padded_tokens_per_step'] - tok
+        dumps.append(tags)
+    assert np.array_equal(dumps[0], dumps[1])
+    _, V, S, C = bench.WORKLOADS['ifst']
+    T, W, O, h0, hT = synth.random_ifst_tensors(V, S, C, np.random.RandomState(1234))
+    x, lengths = synth.random_batch(V, 256, 64, np.random.RandomState(4321))
+    xs = bench.batch_variants('ifst', x, lengths, 0, 4)
+    ref, _, _ = c_port.onehot_ifst_tag(T + W, O, h0, hT, xs[(steps - 1) % 4], lengths, nthreads=8)
+    assert np.array_equal(dumps[0], ref.astype(np.float32))
 
 def test_bench_config5_path_two_ranks_dry_run():
     """BASELINE configs[4]'s code path (`--workload synth512`: device-side tensor generation, the S = 512 geometry of the
