@@ -400,6 +400,48 @@ int  farnn_decomp_ifst_train_step(farnn_train_ctx *ctx, const farnn_train_weight
 int  farnn_train_set_profiling(farnn_train_ctx *ctx, int32_t enable);
 int  farnn_train_time(farnn_train_ctx *ctx, double *total_ms, int64_t *steps);
 
+/* ---- training step of the onehot i-FST (FARNN_S_O_I_S, --method onehot --independent 2) -----------------
+ * Replaces FARNN_S_O_I_S.forward_local(train=True) + loss.backward() (model_onehot.py:131-146,351-428,
+ * train_onehot.py:156-206) for the sum semiring and the CE1 loss: cross-entropy (mean over the valid tokens) of
+ * the scores output_mat (alpha * beta) [. P], and its gradient with respect to language_tensor, the only tensor the
+ * reference trains (model_onehot.py:326-337).  M_w = T[w] + W; the state mask is output_mat.sum(0).
+ * Limits: S <= 128 (farnn_onehot_train_create returns FARNN_ERANGE above), B L < 2^30 (the step returns FARNN_ERANGE
+ * before enqueuing anything).  All pointers are DEVICE pointers; matrices are row-major and unpadded. */
+typedef struct farnn_onehot_train_ctx farnn_onehot_train_ctx;
+
+typedef struct {
+    int32_t V, S, C;            /* vocabulary rows of T, states, score columns (labels + 1)          */
+    int32_t nl;                 /* FARNN_NL_NONE .. FARNN_NL_RELUTANH (update_nonlinear, :379-386)  */
+    float   threshold;          /* decode clamp of column C-1 (model_onehot.py:171-176)              */
+    int32_t o_idx;              /* label written for column C-1 (:175)                               */
+} farnn_onehot_train_dims;
+
+typedef struct {
+    const float *T;             /* [V][S][S] language_tensor */
+    const float *W;             /* [S][S]    wildcard_mat    */
+    const float *O;             /* [C][S]    output_mat      */
+    const float *h0, *hT;       /* [S]                       */
+    const float *P;             /* [C][C] priority matrix or NULL (args.use_priority = 0) */
+} farnn_onehot_train_weights;
+
+typedef struct {
+    float *loss;                /* [1]                                                                 */
+    float *dT;                  /* [V][S][S] (rows of words absent from the batch are written as zero) */
+    int32_t *tags;              /* [B][L] decoded labels of this forward pass, -1 at pad positions     */
+} farnn_onehot_train_outputs;
+
+int  farnn_onehot_train_create(const farnn_onehot_train_dims *dims, int device, farnn_onehot_train_ctx **out);
+void farnn_onehot_train_destroy(farnn_onehot_train_ctx *ctx);
+/* One step on the given stream: writes all outputs (no float atomics: bit-identical across runs).  x, lengths,
+ * labels: int64 [B][L], [B], [B][L]; labels outside 0..C-1 or words outside 0..V-1 at valid positions are counted
+ * as 0 / clamped, and the next call returns FARNN_EINVAL.  valid_tokens = the sum of the lengths clamped to 0..L. */
+int  farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *ctx, const farnn_onehot_train_weights *w, const int64_t *x,
+                                  const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                  int64_t valid_tokens, const farnn_onehot_train_outputs *out, void *stream);
+/* as farnn_train_set_profiling / farnn_train_time */
+int  farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *ctx, int32_t enable);
+int  farnn_onehot_train_time(farnn_onehot_train_ctx *ctx, double *total_ms, int64_t *steps);
+
 /* ---- introspection / measurement ----------------------------------------------------- */
 int  farnn_abi_version(void);
 /* 1: the A/B (profiling) build of the library (csrc/build.py --probes): it also carries the forms the production build left behind --

@@ -118,7 +118,27 @@ class TrainOutputs(C.Structure):
                                           'dWss1', 'dWrs1', 'dbs1', 'dWss2', 'dWrs2', 'dbs2')]
 
 
+class OnehotTrainDims(C.Structure):
+    _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('C', C.c_int32), ('nl', C.c_int32), ('threshold', C.c_float),
+                ('o_idx', C.c_int32)]
+
+
+class OnehotTrainWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('T', 'W', 'O', 'h0', 'hT', 'P')]
+
+
+class OnehotTrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT', 'tags')]
+
+
 SIGNATURES = {
+    'farnn_onehot_train_create': (C.c_int, [C.POINTER(OnehotTrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_onehot_train_destroy': (None, [C.c_void_p]),
+    'farnn_onehot_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(OnehotTrainWeights), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                               C.POINTER(OnehotTrainOutputs), C.c_void_p]),
+    'farnn_onehot_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_onehot_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -531,4 +551,42 @@ class TrainContext:
     def time(self):
         ms, n = C.c_double(0), C.c_int64(0)
         check(load().farnn_train_time(self._raw, C.byref(ms), C.byref(n)), 'farnn_train_time')
+        return ms.value, n.value
+
+
+class OnehotTrainContext:
+    """Owns one farnn_onehot_train_ctx* (training step of the onehot i-FST, include/farnn.h)."""
+
+    def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
+        d = OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx))
+        out = C.c_void_p()
+        check(load().farnn_onehot_train_create(C.byref(d), int(device), C.byref(out)), 'farnn_onehot_train_create')
+        self._raw = out
+        self.dims = (int(V), int(S), int(n_cols))
+
+    def close(self):
+        if self._raw:
+            load().farnn_onehot_train_destroy(self._raw)
+            self._raw = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, weights, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, stream=None):
+        """weights / outputs: dicts of device pointers (ints) keyed like the C structs."""
+        w = OnehotTrainWeights(**{k: (weights.get(k) or None) for k, _ in OnehotTrainWeights._fields_})
+        o = OnehotTrainOutputs(**{k: outputs.get(k) for k, _ in OnehotTrainOutputs._fields_})
+        check(load().farnn_onehot_ifst_train_step(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, int(B), int(L),
+                                                  int(valid_tokens), C.byref(o), stream),
+              'farnn_onehot_ifst_train_step')
+
+    def set_profiling(self, enable):
+        check(load().farnn_onehot_train_set_profiling(self._raw, int(enable)), 'farnn_onehot_train_set_profiling')
+
+    def time(self):
+        ms, n = C.c_double(0), C.c_int64(0)
+        check(load().farnn_onehot_train_time(self._raw, C.byref(ms), C.byref(n)), 'farnn_onehot_train_time')
         return ms.value, n.value

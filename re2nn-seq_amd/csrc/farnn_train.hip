@@ -1,5 +1,6 @@
-// libfarnn_hip.so -- the training step of the decomposed i-FST (farnn_train_*; include/farnn.h).
-// Its own translation unit: the kernels of train.hip.h compile beside the tagging path.
+// libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h) and the onehot
+// i-FST (farnn_onehot_train_*).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
+// loss) compile once, beside the tagging path.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdlib.h>
@@ -10,6 +11,7 @@
 #include "common.hip.h"
 #include "host_util.hip.h"
 #include "train.hip.h"
+#include "onehot_train.hip.h"
 
 using namespace farnn;
 
@@ -425,6 +427,226 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
     atb_partial_kernel<<<jobs.total_wgs, 256, 0, s>>>(jobs);
     atb_reduce_kernel<<<(jobs.total_out + 255) / 256, 256, 0, s>>>(jobs);
     add_row_to_all_kernel<<<(unsigned)((K * S + 255) / 256), 256, 0, s>>>(o->dC, c->dOsum, (int)K, (int)S);
+    FARNN_HIP_TRY(hipGetLastError());
+    if (e0 && e1) { (void)hipEventRecord(e1, s); c->pending.emplace_back(e0, e1); }
+    return FARNN_OK;
+}
+
+// ---- training step of the onehot i-FST (FARNN_S_O_I_S; onehot_train.hip.h) -------------------------------
+struct farnn_onehot_train_ctx {
+    farnn_onehot_train_dims d;
+    int device = 0;
+    int n_cu = 256;
+    float *ws = nullptr;          // per-batch float workspace: stashes, adjoints, MT, o, loss partials, dT partial tiles
+    size_t ws_floats = 0;
+    int *iws = nullptr;           // per-batch int workspace: bucket counts / offsets, per-word tables, the sorted positions
+    size_t iws_ints = 0;
+    int profiling = 0;
+    double prof_ms = 0.0;
+    int64_t prof_n = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    volatile int *err_host = nullptr;   // pinned, device-mapped: bit 0 a bad label, bit 1 a word outside 0..V-1
+    int *err_dev = nullptr;
+};
+
+extern "C" int farnn_onehot_train_create(const farnn_onehot_train_dims *d, int device, farnn_onehot_train_ctx **out) {
+    if (!d || !out) return fail(FARNN_EINVAL, "onehot_train_create: null argument%s%s");
+    *out = nullptr;
+    if (d->V <= 0 || d->S <= 0 || d->C <= 0) return fail(FARNN_EINVAL, "onehot_train_create: bad dimensions%s%s");
+    if (d->nl < FARNN_NL_NONE || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "onehot_train_create: bad nonlinearity%s%s");
+    if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "onehot_train_create: more than 128 states%s%s");
+    {   // the loss kernel keeps output_mat or reads it through L2; its per-wavefront vectors must fit
+        const size_t SPd0 = ((size_t)(d->S + 3) & ~(size_t)3) + 8;
+        if (8 * (SPd0 + 2 * (size_t)d->C) * sizeof(float) > 150 * 1024) return fail(FARNN_ERANGE, "onehot_train_create: too many score columns%s%s");
+    }
+    int rc;
+    if ((rc = select_device(device))) return rc;
+    farnn_onehot_train_ctx *c = new farnn_onehot_train_ctx();
+    c->d = *d; c->device = device;
+    {
+        int ncu = 0;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->n_cu = ncu;
+    }
+    if (hipHostMalloc((void **)&c->err_host, sizeof(int), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&c->err_dev, (void *)c->err_host, 0) != hipSuccess) {
+        farnn_onehot_train_destroy(c);
+        return fail(FARNN_ENOMEM, "onehot_train_create: out of memory%s%s");
+    }
+    *c->err_host = 0;
+    *out = c;
+    return FARNN_OK;
+}
+
+extern "C" void farnn_onehot_train_destroy(farnn_onehot_train_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    for (auto &e : c->pending) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    if (c->ws) (void)hipFree(c->ws);
+    if (c->iws) (void)hipFree(c->iws);
+    if (c->err_host) (void)hipHostFree((void *)c->err_host);
+    delete c;
+}
+
+extern "C" int farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *c, int32_t enable) {
+    if (!c) return fail(FARNN_EINVAL, "onehot_train_set_profiling: null context%s%s");
+    c->profiling = enable;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_onehot_train_time(farnn_onehot_train_ctx *c, double *total_ms, int64_t *steps) {
+    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "onehot_train_time: null argument%s%s");
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    FARNN_HIP_TRY(hipDeviceSynchronize());
+    for (auto &e : c->pending) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) { c->prof_ms += ms; c->prof_n++; }
+        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
+    }
+    c->pending.clear();
+    *total_ms = c->prof_ms; *steps = c->prof_n;
+    c->prof_ms = 0.0; c->prof_n = 0;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const farnn_onehot_train_weights *w, const int64_t *x,
+                                            const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                            int64_t valid_tokens, const farnn_onehot_train_outputs *o, void *stream) {
+    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "onehot_train_step: null argument%s%s");
+    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "onehot_train_step: null weight%s%s");
+    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "onehot_train_step: null output%s%s");
+    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "onehot_train_step: B, L and valid_tokens must be positive%s%s");
+    // positions are 32-bit flat indices b L + i in the bucketing and dT kernels
+    if ((unsigned long long)B * (L + 1) >= (1ull << 30))
+        return fail(FARNN_ERANGE, "onehot_train_step: B (L+1) must stay below 2^30%s%s");
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (*c->err_host) {        // set by an earlier step's kernels straight in pinned host memory (no sync here)
+        FARNN_HIP_TRY(hipStreamSynchronize(s));
+        const int e = *c->err_host;
+        *c->err_host = 0;
+        return fail(FARNN_EINVAL, (e & 2) ? "onehot_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
+                                          : "onehot_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
+    }
+    const size_t S = c->d.S, K = c->d.C, V = c->d.V, SS = S * S;
+    const size_t N1 = (size_t)B * (L + 1), N0 = (size_t)B * L;
+    const int nch = (int)((N0 + OT_CH - 1) / OT_CH);
+    // the loss kernel's persistent workgroups: three per compute unit (48 KiB of LDS each at ATIS size; one per unit left
+    // the position loop latency-bound: 127 us)
+    const unsigned lgrid = (unsigned)std::min<size_t>(3 * (size_t)c->n_cu, (N0 + 7) / 8);
+    const size_t ntiles = 2 * ((N0 + OT_G - 1) / OT_G) + 1;             // partial tiles of the words with several runs
+    const size_t need = 6 * N1 * S + N0 * (K + S) + 2 * V * SS + ((S + 3) & ~(size_t)3) + (size_t)lgrid * 8 + ntiles * SS;
+    const size_t ineed = V * (size_t)nch + 4 * V + 2 + N0;
+    if (need > c->ws_floats) {
+        if (c->ws) { FARNN_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(c->ws); c->ws = nullptr; c->ws_floats = 0; }
+        if (hipMalloc((void **)&c->ws, need * sizeof(float)) != hipSuccess)
+            return fail(FARNN_ENOMEM, "onehot_train_step: out of device memory for the workspace%s%s");
+        c->ws_floats = need;
+    }
+    if (ineed > c->iws_ints) {
+        if (c->iws) { FARNN_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(c->iws); c->iws = nullptr; c->iws_ints = 0; }
+        if (hipMalloc((void **)&c->iws, ineed * sizeof(int)) != hipSuccess)
+            return fail(FARNN_ENOMEM, "onehot_train_step: out of device memory for the workspace%s%s");
+        c->iws_ints = ineed;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, s);
+
+    // every workspace entry a kernel reads is written by an earlier kernel of this step (the chains write the stash rows
+    // 0..len, the loss kernel the adjoint rows of every valid position): only the bucket counts are zeroed
+    OhTrainParams q;
+    memset(&q, 0, sizeof(q));
+    float *f = c->ws;
+    q.A = f; f += N1 * S; q.Bk = f; f += N1 * S; q.GA = f; f += N1 * S; q.GB = f; f += N1 * S;
+    q.UF = f; f += N1 * S; q.DQ = f; f += N1 * S;
+    float *DS = f; f += N0 * K;
+    float *AB = f; f += N0 * S;
+    float *M = f; f += V * SS;
+    float *MT = f; f += V * SS;
+    float *osum = f; f += (S + 3) & ~(size_t)3;
+    float *loss_part = f; f += (size_t)lgrid * 8;
+    float *partial = f;
+    int *cnt = c->iws, *wstart = cnt + V * (size_t)nch, *wcount = wstart + V, *itoff = wcount + V, *psoff = itoff + V + 1,
+        *list = psoff + V + 1;
+    q.M = M; q.MT = MT; q.o = osum; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
+    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = c->d.nl;
+
+    int rc;
+    FARNN_HIP_TRY(hipMemsetAsync(cnt, 0, V * (size_t)nch * sizeof(int), s));
+    {
+        PrepJobs pj;
+        memset(&pj, 0, sizeof(pj));
+        PrepJob &j0 = pj.j[pj.n++];                     // o = output_mat.sum(0)
+        j0.kind = 2; j0.src = w->O; j0.dst = osum; j0.rows = (int)K; j0.cols = (int)S; j0.e0 = 0;
+        pj.total = (int)(((S + 255) / 256) * 256);
+        train_prep_kernel<<<(pj.total + 255) / 256, 256, 0, s>>>(pj);
+    }
+    {
+        const unsigned nt = (unsigned)((S + 31) / 32);
+        onehot_premix_kernel<<<(unsigned)V * nt * nt, 256, 0, s>>>(w->T, w->W, M, MT, (int)S);
+    }
+    onehot_bucket_count_kernel<<<nch, OT_CH, 0, s>>>(x, lengths, B, L, (int)V, nch, cnt, c->err_dev);
+    {
+        const size_t ncnt = V * (size_t)nch;
+        const size_t lds_s = ncnt * sizeof(int) <= 144 * 1024 ? ncnt * sizeof(int) : 0;
+        if (lds_s && (rc = raise_lds_limit(onehot_bucket_scan_kernel, lds_s))) return rc;
+        onehot_bucket_scan_kernel<<<1, 1024, lds_s, s>>>(cnt, (int)V, nch, wstart, wcount, itoff, psoff, lds_s ? (int)ncnt : 0);
+    }
+    onehot_bucket_fill_kernel<<<nch, OT_CH, 0, s>>>(x, lengths, B, L, (int)V, nch, cnt, list);
+
+    const dim3 cgrid(B, 2);
+    const size_t lds_tok = (size_t)(L + 1) * sizeof(int);
+#define FARNN_OH_CHAIN(BPTT)                                                                                           \
+    do {                                                                                                               \
+        if (S <= 64)      { if ((rc = raise_lds_limit(onehot_train_chain_kernel<8, BPTT>, lds_tok))) return rc;       \
+                            onehot_train_chain_kernel<8, BPTT><<<cgrid, OT_THREADS, lds_tok, s>>>(q); }                \
+        else if (S <= 72) { if ((rc = raise_lds_limit(onehot_train_chain_kernel<18, BPTT>, lds_tok))) return rc;      \
+                            onehot_train_chain_kernel<18, BPTT><<<cgrid, OT_THREADS, lds_tok, s>>>(q); }               \
+        else if (S <= 96) { if ((rc = raise_lds_limit(onehot_train_chain_kernel<24, BPTT>, lds_tok))) return rc;      \
+                            onehot_train_chain_kernel<24, BPTT><<<cgrid, OT_THREADS, lds_tok, s>>>(q); }               \
+        else              { if ((rc = raise_lds_limit(onehot_train_chain_kernel<32, BPTT>, lds_tok))) return rc;      \
+                            onehot_train_chain_kernel<32, BPTT><<<cgrid, OT_THREADS, lds_tok, s>>>(q); }               \
+    } while (0)
+    FARNN_OH_CHAIN(false);
+    {   // scores, cross-entropy, decode, d loss / d alpha, d loss / d beta: the decomposed step's kernel (PHASE 0) with
+        // output_mat in C_output_mat's place, the loss as per-wavefront partials
+        TrainParams p;
+        memset(&p, 0, sizeof(p));
+        p.C = w->O; p.P = w->P; p.len = lengths; p.labels = labels; p.err = c->err_dev;
+        p.A = q.A; p.Bk = q.Bk; p.GA = q.GA; p.GB = q.GB; p.DS = DS; p.AB = AB;
+        p.loss = o->loss; p.loss_part = loss_part; p.tags = o->tags;
+        p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
+        p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
+        const size_t SPd0 = ((S + 3) & ~(size_t)3) + 8;
+        const size_t lds_lw = 8 * (SPd0 + 2 * K) * sizeof(float), lds_lc = ((K * (S + 1) + 3) & ~(size_t)3) * sizeof(float);
+        const bool clds = lds_lw + lds_lc <= 150 * 1024;
+        const size_t lds_l = lds_lw + (clds ? lds_lc : 0);
+        if (clds) {
+            if ((rc = raise_lds_limit(train_loss_kernel<true, 0>, lds_l))) return rc;
+            train_loss_kernel<true, 0><<<lgrid, 512, lds_l, s>>>(p);
+        } else {
+            if ((rc = raise_lds_limit(train_loss_kernel<false, 0>, lds_l))) return rc;
+            train_loss_kernel<false, 0><<<lgrid, 512, lds_l, s>>>(p);
+        }
+        onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    }
+    FARNN_OH_CHAIN(true);
+#undef FARNN_OH_CHAIN
+    {
+        const unsigned ngrid = (unsigned)(V + (N0 + OT_G - 1) / OT_G);   // bound on the runs: sum_w max(1, ceil(n_w / G))
+        const size_t lds_d = 4 * (size_t)OT_G * S * sizeof(float);
+#define FARNN_OH_DT(NT)                                                                                                \
+        do {                                                                                                           \
+            if ((rc = raise_lds_limit(onehot_dT_kernel<NT>, lds_d))) return rc;                                       \
+            onehot_dT_kernel<NT><<<ngrid, 256, lds_d, s>>>(q, list, wstart, wcount, itoff, psoff, o->dT, partial);    \
+        } while (0)
+        if (S <= 32) FARNN_OH_DT(2);
+        else if (S <= 64) FARNN_OH_DT(4);
+        else if (S <= 96) FARNN_OH_DT(6);
+        else FARNN_OH_DT(8);
+#undef FARNN_OH_DT
+        onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((SS + 255) / 256)), 256, 0, s>>>(itoff, psoff, partial, o->dT, (int)S);
+    }
     FARNN_HIP_TRY(hipGetLastError());
     if (e0 && e1) { (void)hipEventRecord(e1, s); c->pending.emplace_back(e0, e1); }
     return FARNN_OK;

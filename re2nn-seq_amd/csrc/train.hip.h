@@ -54,6 +54,8 @@ struct TrainParams {
     int *err;                 // sticky device flag: bit 0 = a label outside 0..K-1 at a valid position
     int B, L, V, S, R, K, nl, o_idx;
     float threshold, inv_tokens;
+    float *loss_part;         // NULL: the loss is accumulated with atomics; else one partial per wavefront of train_loss_kernel
+                              // ([gridDim.x * 8], summed in index order afterwards: the onehot step, onehot_train.hip.h)
 };
 
 __device__ __forceinline__ float nl_grad_from_output(float y, int nl) {
@@ -529,7 +531,9 @@ train_loss_kernel(const TrainParams p) {
             gb[s] = d * al[s];
         }
     }
-    if (lane == 0 && loss_acc != 0.0f) atomicAdd(p.loss, loss_acc * p.inv_tokens);
+    if (p.loss_part) {
+        if (lane == 0) p.loss_part[blockIdx.x * nw + w] = loss_acc * p.inv_tokens;
+    } else if (lane == 0 && loss_acc != 0.0f) atomicAdd(p.loss, loss_acc * p.inv_tokens);
 }
 
 // ---- CRF negative log-likelihood on the emissions (reference baselines/crf.py:48-99, 202-260) -------------------

@@ -110,7 +110,92 @@ class FARNN_S_O_I_S(_OnehotBase):
         return _lib.create_onehot_ifst(self.language_tensor, self.wildcard_mat, self.output_mat, self.h0,
                                        self.hT, **kw)
 
+    # ---- training step (reference :351-428 with train=True + train_onehot.py:156-206) ----
+    def _check_trainable(self):
+        """The cases the HIP training step does not cover, refused before any device work."""
+        a = self.args
+        if a.train_mode != 'sum':
+            raise NotImplementedError('training the onehot i-FST covers the sum semiring only; --train_mode {} is not '
+                                      'built (DESIGN.md, row f5)'.format(a.train_mode))
+        if a.local_loss_func != 'CE1':
+            raise NotImplementedError('training the onehot i-FST covers the CE1 loss only (main.py:127)')
+        if self.use_crf:
+            raise NotImplementedError('training the onehot i-FST with the CRF extension (enable_crf) is not built; the '
+                                      "reference's onehot models never read use_crf (DESIGN.md, row f5)")
+        from ..dist import world
+        if world()[1] > 1:
+            raise NotImplementedError('multi-GPU data-parallel training of the onehot i-FST is not built; train on one '
+                                      'GPU (DESIGN.md, row f5)')
+
+    def enable_training(self):
+        """Device-resident tensors (language_tensor the only one with requires_grad, as in the reference :326-337) and
+        the library context.  An edge-built model gets its dense tensors here (_dense())."""
+        self._check_trainable()
+        if getattr(self, '_tp', None) is not None:
+            return self
+        if not torch.cuda.is_available():
+            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
+        dev = self._dev()
+        sd = self.state_dict()
+        self._tp = {}
+        for k in ('language_tensor', 'wildcard_mat', 'output_mat', 'h0', 'hT'):
+            t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).clone()
+            self._tp[k] = t.requires_grad_(k == 'language_tensor')
+        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
+            if self.args.use_priority else None
+        V, S, _ = self._tp['language_tensor'].shape
+        self._tc = _lib.OnehotTrainContext(V, S, self.C, nl=self.args.update_nonlinear, threshold=self.args.threshold,
+                                           o_idx=self.o_idx, device=self.device_index)
+        self._dirty = False
+        return self
+
+    def parameters(self):
+        tp = getattr(self, '_tp', None)
+        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+
+    def named_parameters(self):
+        tp = getattr(self, '_tp', None)
+        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
+
+    def sync_from_training(self):
+        """Copy the trained language_tensor back into the host attributes the tagging handle is built from.  An
+        edge-built model becomes a dense one (its edges no longer describe the weights)."""
+        tp = getattr(self, '_tp', None)
+        if tp is None or not self._dirty:
+            return
+        if getattr(self, 'edges', None) is not None:
+            self.language_tensor, self.wildcard_mat, self.output_mat = self._dense()
+            self.output_wildcard_vector = np.zeros(self.S, np.float32)
+            self.edges = None
+        self.language_tensor = tp['language_tensor'].detach().cpu().numpy()
+        self._dirty = False
+        self.invalidate()
+
+    def eval(self):
+        self.sync_from_training()
+        return super().eval()
+
+    def forward_local(self, input, label, lengths, train=True, re_tags=None):
+        if not train:
+            self.sync_from_training()
+            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
+        from .train_step import onehot_ifst_train_step
+        self.enable_training()
+        tp = self._tp
+        on_host = lengths.device.type == 'cpu'
+        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
+        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
+        x = input[:, :Lmax]
+        lab = label[:, :Lmax]
+        loss, tags = onehot_ifst_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_mat'],
+                                            tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
+        self._dirty = True
+        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
+        true = self._flatten(label, lengths).to(input.device)
+        return loss, pred, true
+
     def state_dict(self):
+        self.sync_from_training()
         if getattr(self, 'edges', None) is not None:
             T, W, O = self._dense()
             return {'h0': self.h0, 'hT': self.hT, 'language_tensor': T, 'wildcard_mat': W, 'output_mat': O,

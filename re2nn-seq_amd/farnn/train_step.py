@@ -1,5 +1,5 @@
-"""The training step of the decomposed i-FST on the HIP path, as a torch.autograd.Function around
-farnn_decomp_ifst_train_step (include/farnn.h).
+"""The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step and
+farnn_onehot_ifst_train_step (include/farnn.h).
 
 What the reference does in FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
 (model_decompose_single.py:207-304, train_decompose.py:186-190) is split like this: the word table
@@ -11,6 +11,9 @@ computes loss and all gradients in its forward call (the stash lives in its work
 only hands them out, scaled by the incoming gradient.
 
 Scope: farnn = 0/1/2, sum semiring, CE1 loss or (use_crf) the CRF negative log-likelihood.
+
+The onehot i-FST (FARNN_S_O_I_S, model_onehot.py:351-428 + train_onehot.py:156-206) trains only
+language_tensor: one library call computes the loss, the tags and d loss / d language_tensor.
 """
 import torch
 
@@ -82,3 +85,44 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
     the caller already has it (device-resident lengths would otherwise cost a synchronising read per step)."""
     return _DecompIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cmat, h0, hT, crf_trans,
                                       *gates)
+
+
+class _OnehotIfstTrainStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
+        dev = T.device
+        if dev.type != 'cuda':
+            raise _lib.FarnnError('the training step runs on the HIP device only (no CPU fallback)')
+        ws = {n: t.detach().contiguous().float() for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
+        Pc = None if P is None else P.detach().contiguous().float()
+        B, L = x.shape
+        if ntok is None:            # counted on the host when the lengths live there (no device round trip in the step)
+            ntok = int(lengths.clamp(0, L).sum())
+        x = x.to(dev).contiguous()
+        lengths = lengths.to(dev).contiguous()
+        labels = labels.to(dev).contiguous()
+        if ntok <= 0:
+            raise ValueError('empty batch')
+        dT = torch.empty_like(ws['T'])
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        tags = torch.empty((B, L), dtype=torch.int32, device=dev)
+        weights = {n: t.data_ptr() for n, t in ws.items()}
+        weights['P'] = None if Pc is None else Pc.data_ptr()
+        outputs = {'loss': loss.data_ptr(), 'dT': dT.data_ptr(), 'tags': tags.data_ptr()}
+        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
+                torch.cuda.current_stream(dev).cuda_stream)
+        ctx.save_for_backward(dT)
+        ctx.mark_non_differentiable(tags)
+        return loss.reshape(()), tags
+
+    @staticmethod
+    def backward(ctx, gloss, _gtags):
+        dT, = ctx.saved_tensors
+        return (None,) * 10 + (dT * gloss,)
+
+
+def onehot_ifst_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens=None):
+    """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W, O, h0, hT and P are read
+    but receive no gradient (the reference's requires_grad=False, model_onehot.py:326-337).  valid_tokens: the sum of
+    the clamped lengths if the caller already has it."""
+    return _OnehotIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)

@@ -1,8 +1,8 @@
 """``--method onehot`` driver (reference src_seq/train_onehot.py:20-154: data, automaton ->
 tensors -> model, INIT evaluation on train/dev/test, `.res` record).  The epoch loop of the
-reference (:156-206, backward pass + Adam) is outside the forward tagging path: with
-``--epoch 0`` (what ``--train_portion 0`` requires, main.py:147-148) this driver is complete;
-a positive epoch count is refused."""
+reference (:156-206, backward pass + Adam) runs for the i-FST (``--independent 2``, sum semiring,
+no CRF extension) on the HIP training step; for the other onehot models a
+positive epoch count is refused before any device work."""
 from .create_logic_mat_bias import create_mat_priority_MITR
 from .data import SlotBatchDataset, iter_batches, load_slot_dataset
 from .RE import build_onehot_model
@@ -47,13 +47,22 @@ def init_evaluation(model, splits, args, s2i, i2s, logger, model_dir='../model_s
                                    init_results_test=results['test'],
                                    save_model=bool(getattr(args, 'save_model', 0)))
     if args.epoch > 0:
-        if not hasattr(model, 'enable_training'):
-            raise NotImplementedError(
-                'training epochs are implemented for the decomposed i-FST (--method decompose --independent 2, '
-                'farnn 0, no CRF: DESIGN.md row f3); run the other models with --epoch 0')
+        check_trainable(model)
         train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats)
     path = save_model_and_log(logger, recorder, args, model_dir=model_dir)
     return results, stats, path
+
+
+def check_trainable(model):
+    """Refuses a model the HIP training step does not cover (raises NotImplementedError; no device work)."""
+    if not hasattr(model, 'enable_training'):
+        raise NotImplementedError(
+            'training epochs are implemented for the i-FST models only (--independent 2: --method decompose, DESIGN.md '
+            'row f3, and --method onehot, row f5); {} has no training step, run it with --epoch 0'.format(
+                type(model).__name__))
+    from .farnn.model_onehot import FARNN_S_O_I_S
+    if isinstance(model, FARNN_S_O_I_S):
+        model._check_trainable()                  # max semiring, CRF extension, several GPUs
 
 
 def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
@@ -118,4 +127,6 @@ def train_slot_onehot(args, data_dir='../data/', model_dir='../model_seq/'):
     model = build_onehot_model(args, automata, t2i, s2i, create_mat_priority_MITR(s2i))
     if getattr(args, 'use_crf', 0) and hasattr(model, 'enable_crf'):
         model.enable_crf()                         # BASELINE config 4
+    if args.epoch > 0:
+        check_trainable(model)                     # before the INIT evaluations touch the device
     return init_evaluation(model, splits, args, s2i, i2s, logger, model_dir)
