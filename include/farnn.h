@@ -344,8 +344,8 @@ int64_t farnn_flatten_host(const int64_t *a, const int64_t *len_host, int32_t B,
 
 /* ---- training step of the decomposed i-FST -----------------------------------
  * Replaces FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
- * (model_decompose_single.py:207-304, train_decompose.py:186-190) for farnn = 0/1/2, the sum semiring and the
- * CE1 loss: cross-entropy (mean over the valid tokens) of the scores, or with use_crf the CRF negative
+ * (model_decompose_single.py:207-304, train_decompose.py:186-190) for farnn = 0/1/2, the sum or the max semiring
+ * (farnn_train_set_semiring) and the CE1 loss: cross-entropy (mean over the valid tokens) of the scores, or with use_crf the CRF negative
  * log-likelihood, and the gradient with respect to every tensor the recurrence and the scoring read.  The generalized word table Vgen
  * (model_decompose.py:222-241) is an input; the caller differentiates it from dVgen.
  * All pointers are DEVICE pointers; matrices are row-major and unpadded. */
@@ -399,6 +399,12 @@ int  farnn_decomp_ifst_train_step(farnn_train_ctx *ctx, const farnn_train_weight
  * profiling is enabled with farnn_train_set_profiling(ctx, 1) */
 int  farnn_train_set_profiling(farnn_train_ctx *ctx, int32_t enable);
 int  farnn_train_time(farnn_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* The semiring of the recurrence (the reference's --train_mode, model_decompose_single.py:159-166): FARNN_SEMIRING_SUM
+ * (the default) or FARNN_SEMIRING_MAX, where a step is n[s] = max_j in[j] Tr_w[j,s] with Tr_w = S1 diag(Vgen[w]) S2^T + W
+ * (torch.max: the first maximal j takes the whole adjoint).  Everything else of the step is the same in both.  Returns
+ * FARNN_EINVAL for any other value and FARNN_ERANGE for FARNN_SEMIRING_MAX above 192 states.  The max step's workspace
+ * (three S x S blocks per distinct word of the batch) is allocated by its first step. */
+int  farnn_train_set_semiring(farnn_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the onehot i-FST (FARNN_S_O_I_S, --method onehot --independent 2) -----------------
  * Replaces FARNN_S_O_I_S.forward_local(train=True) + loss.backward() (model_onehot.py:131-146,351-428,

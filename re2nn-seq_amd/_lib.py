@@ -146,6 +146,7 @@ SIGNATURES = {
                                                C.POINTER(TrainOutputs), C.c_void_p]),
     'farnn_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_onehot_ifst_create': (C.c_int, [C.POINTER(OnehotIfstDesc), C.c_int, C.POINTER(_vp)]),
     'farnn_onehot_ifst_create_from_edges': (C.c_int, [C.POINTER(OnehotIfstDesc), C.POINTER(EdgeList), C.c_int,
                                                       C.POINTER(_vp)]),
@@ -518,13 +519,19 @@ class TrainContext:
     """Owns one farnn_train_ctx* (training step of the decomposed i-FST, include/farnn.h)."""
 
     def __init__(self, V, S, R, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0,
-                 sigmoid_exponent=5.0):
+                 sigmoid_exponent=5.0, semiring='sum'):
         d = TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
                       float(sigmoid_exponent), int(bool(use_crf)))
         out = C.c_void_p()
         check(load().farnn_train_create(C.byref(d), int(device), C.byref(out)), 'farnn_train_create')
         self._raw = out
         self.dims = (int(V), int(S), int(R), int(K))
+        if semiring != 'sum':
+            self.set_semiring(semiring)
+
+    def set_semiring(self, semiring):
+        """'sum' or 'max' (the reference's --train_mode) for the following steps."""
+        check(load().farnn_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_train_set_semiring')
 
     def close(self):
         if self._raw:

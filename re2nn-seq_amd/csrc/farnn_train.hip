@@ -12,6 +12,7 @@
 #include "host_util.hip.h"
 #include "train.hip.h"
 #include "onehot_train.hip.h"
+#include "train_max.hip.h"
 
 using namespace farnn;
 
@@ -37,6 +38,11 @@ struct farnn_train_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     volatile int *err_host = nullptr;   // pinned, device-mapped: the kernels set bit 0 on a bad label (only then is it touched)
     int *err_dev = nullptr;             // the device's address of err_host
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_train_set_semiring
+    float *mws = nullptr;               // max semiring only (train_max.hip.h): M, MT, dM, IN, GM; allocated on first use
+    size_t mws_floats = 0;
+    int *miws = nullptr;                // max semiring only: IDX, the bucketing of the positions, the word slots
+    size_t miws_ints = 0;
 };
 
 extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out) {
@@ -96,6 +102,8 @@ extern "C" void farnn_train_destroy(farnn_train_ctx *c) {
     if (c->VgenT) (void)hipFree(c->VgenT);
     if (c->GV) (void)hipFree(c->GV);
     if (c->S1T) (void)hipFree(c->S1T);
+    if (c->mws) (void)hipFree(c->mws);
+    if (c->miws) (void)hipFree(c->miws);
     if (c->err_host) (void)hipHostFree((void *)c->err_host);
     delete c;
 }
@@ -103,6 +111,16 @@ extern "C" void farnn_train_destroy(farnn_train_ctx *c) {
 extern "C" int farnn_train_set_profiling(farnn_train_ctx *c, int32_t enable) {
     if (!c) return fail(FARNN_EINVAL, "train_set_profiling: null context%s%s");
     c->profiling = enable;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_train_set_semiring(farnn_train_ctx *c, int32_t semiring) {
+    if (!c) return fail(FARNN_EINVAL, "train_set_semiring: null context%s%s");
+    if (semiring != FARNN_SEMIRING_SUM && semiring != FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "train_set_semiring: semiring must be FARNN_SEMIRING_SUM or FARNN_SEMIRING_MAX%s%s");
+    if (semiring == FARNN_SEMIRING_MAX && c->d.S > TM_MAX_S)
+        return fail(FARNN_ERANGE, "train_set_semiring: the max-semiring step holds at most 192 states%s%s");
+    c->semiring = semiring;
     return FARNN_OK;
 }
 
@@ -222,6 +240,44 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
     p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.R = (int)R; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
     p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
 
+    // max semiring (train_max.hip.h): blocks of the batch's distinct words (at most min(V, B L)), the per-step argmax and
+    // dTr entries, the bucketing of the positions by word
+    const bool mx = c->semiring == FARNN_SEMIRING_MAX;
+    TrainMaxParams mp;
+    memset(&mp, 0, sizeof(mp));
+    float *dM = nullptr;
+    int *mcnt = nullptr, *mwstart = nullptr, *mwcount = nullptr, *mitoff = nullptr, *mpsoff = nullptr, *mlist = nullptr;
+    int *mwslot = nullptr, *mwlist = nullptr, *mnwords = nullptr;
+    const int nch = (int)((N0 + OT_CH - 1) / OT_CH);
+    const size_t nwmax = std::min(V, N0);
+    if (mx) {
+        const size_t SS = S * S;
+        const size_t mneed = 3 * nwmax * SS + 4 * N1 * S;
+        const size_t mineed = 2 * N1 * S + V * (size_t)nch + 5 * V + 2 + N0 + V + nwmax + 1;
+        if (mneed > c->mws_floats) {
+            if (c->mws) { FARNN_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(c->mws); c->mws = nullptr; c->mws_floats = 0; }
+            if (hipMalloc((void **)&c->mws, mneed * sizeof(float)) != hipSuccess)
+                return fail(FARNN_ENOMEM, "train_step: out of device memory for the max-semiring workspace%s%s");
+            c->mws_floats = mneed;
+        }
+        if (mineed > c->miws_ints) {
+            if (c->miws) { FARNN_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(c->miws); c->miws = nullptr; c->miws_ints = 0; }
+            if (hipMalloc((void **)&c->miws, mineed * sizeof(int)) != hipSuccess)
+                return fail(FARNN_ENOMEM, "train_step: out of device memory for the max-semiring workspace%s%s");
+            c->miws_ints = mineed;
+        }
+        float *f = c->mws;
+        mp.M = f; f += nwmax * SS;
+        mp.MT = f; f += nwmax * SS;
+        dM = f; f += nwmax * SS;
+        mp.INf = f; f += N1 * S; mp.INb = f; f += N1 * S; mp.GMf = f; f += N1 * S; mp.GMb = f;
+        int *qi = c->miws;
+        mp.IDXf = qi; qi += N1 * S; mp.IDXb = qi; qi += N1 * S;
+        mcnt = qi; qi += V * (size_t)nch; mwstart = qi; qi += V; mwcount = qi; qi += V; mitoff = qi; qi += V + 1;
+        mpsoff = qi; qi += V + 1; mlist = qi; qi += N0; mwslot = qi; qi += V; mwlist = qi; qi += nwmax; mnwords = qi;
+        mp.wslot = mwslot; mp.wlist = mwlist; mp.nwords = mnwords;
+    }
+
     FARNN_HIP_TRY(hipMemsetAsync(c->ws, 0, need * sizeof(float), s));
     {
         PrepJobs pj;
@@ -332,7 +388,23 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
             else       FARNN_TRAIN_CHAIN3(KERN, false, false, TR_NSEQ_L2, LDSB);                          \
         }                                                                                                 \
     } while (0)
-    if (ldsw_f) FARNN_TRAIN_CHAIN(train_forward_kernel, true, ns_f, lds_f);
+    const size_t lds_tok = (size_t)L * sizeof(int);
+    if (mx) {
+        // the positions bucketed by word (onehot_train.hip.h), the distinct words' slots, their blocks, both chains
+        FARNN_HIP_TRY(hipMemsetAsync(mcnt, 0, V * (size_t)nch * sizeof(int), s));
+        onehot_bucket_count_kernel<<<nch, OT_CH, 0, s>>>(x, lengths, B, L, (int)V, nch, mcnt, nullptr);
+        const size_t ncnt = V * (size_t)nch;
+        const size_t lds_s = ncnt * sizeof(int) <= 144 * 1024 ? ncnt * sizeof(int) : 0;
+        if (lds_s && (rc = raise_lds_limit(onehot_bucket_scan_kernel, lds_s))) return rc;
+        onehot_bucket_scan_kernel<<<1, 1024, lds_s, s>>>(mcnt, (int)V, nch, mwstart, mwcount, mitoff, mpsoff, lds_s ? (int)ncnt : 0);
+        onehot_bucket_fill_kernel<<<nch, OT_CH, 0, s>>>(x, lengths, B, L, (int)V, nch, mcnt, mlist);
+        tmax_slots_kernel<<<1, 1024, 0, s>>>(mwcount, (int)V, mwslot, mwlist, mnwords);
+        const unsigned nt = (unsigned)((S + 31) / 32);
+        tmax_premix_kernel<<<dim3((unsigned)nwmax, nt * nt), 256, 0, s>>>(w->Vgen, w->S1, w->S2, w->W, mwlist, mnwords,
+                                                                         (float *)mp.M, (float *)mp.MT, (int)S, (int)R);
+        if ((rc = raise_lds_limit(tmax_forward_kernel, lds_tok))) return rc;
+        tmax_forward_kernel<<<dim3(B, 2), TM_THREADS, lds_tok, s>>>(p, mp);
+    } else if (ldsw_f) FARNN_TRAIN_CHAIN(train_forward_kernel, true, ns_f, lds_f);
     else        FARNN_TRAIN_CHAIN(train_forward_kernel, false, ns_f, lds_f);
     {
         int dev = 0, ncu = 0;
@@ -366,7 +438,10 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
         }
 #undef FARNN_LAUNCH_LOSS
     }
-    if (ldsw_b) FARNN_TRAIN_CHAIN(train_backward_kernel, true, ns_b, lds_b);
+    if (mx) {
+        if ((rc = raise_lds_limit(tmax_backward_kernel, lds_tok))) return rc;
+        tmax_backward_kernel<<<dim3(B, 2), TM_THREADS, lds_tok, s>>>(p, mp);
+    } else if (ldsw_b) FARNN_TRAIN_CHAIN(train_backward_kernel, true, ns_b, lds_b);
     else        FARNN_TRAIN_CHAIN(train_backward_kernel, false, ns_b, lds_b);
 #undef FARNN_TRAIN_CHAIN
 #undef FARNN_TRAIN_CHAIN3
@@ -382,21 +457,33 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
         }
         train_prep_kernel<<<(tj.total + 255) / 256, 256, 0, s>>>(tj);
     }
+    if (mx) {                                          // dM per distinct word, then dS1 (+ dVgen, dW) and dS2 from it
+        const size_t lds_m = S * S * sizeof(float), lds_w = tmax_wgrad_lds_bytes(S);
+        if ((rc = raise_lds_limit(tmax_dM_kernel, lds_m))) return rc;
+        tmax_dM_kernel<<<(unsigned)nwmax, TM_THREADS, lds_m, s>>>(p, mp, mlist, mwstart, mwcount, dM);
+        const dim3 wgrid((unsigned)((R + 63) / 64), (unsigned)((S + 31) / 32), TM_WCH);
+        if ((rc = raise_lds_limit(tmax_wgrad_kernel<false>, lds_w))) return rc;
+        tmax_wgrad_kernel<false><<<wgrid, 256, lds_w, s>>>(p, mp, dM, o->dS1, o->dW);
+        if ((rc = raise_lds_limit(tmax_wgrad_kernel<true>, lds_w))) return rc;
+        tmax_wgrad_kernel<true><<<wgrid, 256, lds_w, s>>>(p, mp, dM, o->dS2, o->dW);
+    }
     // parameter gradients = tall-skinny products over the per-token rows (rows of non-tokens are zero)
     AtbJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     jobs.chunk = 128;
-    atb_add(jobs, p.Zf, p.Tf, o->dS2, (long long)N1, (int)S, (int)R);                 // dS2 += Zf^T (v*rr)
-    if (!farnn) {
-        atb_add(jobs, p.A, p.D1f + R, o->dS1, (long long)N1 - 1, (int)S, (int)R);     // dS1 += f_{t-1}^T (u*v)
-        atb_add(jobs, p.A, p.Zf + S, o->dW, (long long)N1 - 1, (int)S, (int)S);       // dW  += f_{t-1}^T z
-    } else {                                                                            // the chain input is hbar_t, stored per row
-        atb_add(jobs, p.HBARf, p.D1f, o->dS1, (long long)N1, (int)S, (int)R);
-        atb_add(jobs, p.HBARf, p.Zf, o->dW, (long long)N1, (int)S, (int)S);
+    if (!mx) {
+        atb_add(jobs, p.Zf, p.Tf, o->dS2, (long long)N1, (int)S, (int)R);                 // dS2 += Zf^T (v*rr)
+        if (!farnn) {
+            atb_add(jobs, p.A, p.D1f + R, o->dS1, (long long)N1 - 1, (int)S, (int)R);     // dS1 += f_{t-1}^T (u*v)
+            atb_add(jobs, p.A, p.Zf + S, o->dW, (long long)N1 - 1, (int)S, (int)S);       // dW  += f_{t-1}^T z
+        } else {                                                                            // the chain input is hbar_t, stored per row
+            atb_add(jobs, p.HBARf, p.D1f, o->dS1, (long long)N1, (int)S, (int)R);
+            atb_add(jobs, p.HBARf, p.Zf, o->dW, (long long)N1, (int)S, (int)S);
+        }
+        atb_add(jobs, p.Zb, p.Tb, o->dS1, (long long)N1, (int)S, (int)R);                 // backward chain: roles of S1, S2 swap
+        atb_add(jobs, p.BBAR, p.D1b, o->dS2, (long long)N1, (int)S, (int)R);
+        atb_add(jobs, p.Zb, p.BBAR, o->dW, (long long)N1, (int)S, (int)S);                // pre_j += sum_s bbar_s W[j][s]
     }
-    atb_add(jobs, p.Zb, p.Tb, o->dS1, (long long)N1, (int)S, (int)R);                 // backward chain: roles of S1, S2 swap
-    atb_add(jobs, p.BBAR, p.D1b, o->dS2, (long long)N1, (int)S, (int)R);
-    atb_add(jobs, p.Zb, p.BBAR, o->dW, (long long)N1, (int)S, (int)S);                // pre_j += sum_s bbar_s W[j][s]
     atb_add(jobs, p.DS, p.AB, o->dC, (long long)N0, (int)K, (int)S);                  // dC += ds^T (alpha*beta)
     if (farnn) {
         // gates read the raw previous state (stash shifted by one row) and v_t: dWss = h_{t-1}^T da, dWrs = v^T da, dbs = 1^T da

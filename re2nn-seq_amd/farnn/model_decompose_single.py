@@ -182,10 +182,10 @@ class FARNN_S_D_W_I_S(NativeTagger):
 
     def _check_trainable(self, re_tags):
         a = self.args
-        if a.farnn not in (0, 1, 2) or a.train_mode != 'sum' or a.local_loss_func != 'CE1' or re_tags is not None \
-                or getattr(a, 'marryup_type', 'none') not in ('none', None):
-            raise NotImplementedError('the HIP training step covers the sum semiring and the CE1 loss (with or without '
-                                      'the CRF), no KD/PR teachers (DESIGN.md, row f3)')
+        if a.farnn not in (0, 1, 2) or a.train_mode not in ('sum', 'max') or a.local_loss_func != 'CE1' \
+                or re_tags is not None or getattr(a, 'marryup_type', 'none') not in ('none', None):
+            raise NotImplementedError('the HIP training step covers the sum and max semirings and the CE1 loss (with or '
+                                      'without the CRF), no KD/PR teachers (DESIGN.md, row f3)')
 
     def enable_training(self):
         """Device-resident leaf tensors for the optimizer (returned by parameters()) and the library context."""
@@ -210,7 +210,8 @@ class FARNN_S_D_W_I_S(NativeTagger):
         self._tc = _lib.TrainContext(self._tp['V_embed'].shape[0], S, R, self._tp['C_output_mat'].shape[0],
                                      nl=self.args.update_nonlinear, threshold=self.args.threshold, o_idx=self.o_idx,
                                      device=self.device_index, use_crf=self.use_crf, farnn=int(self.args.farnn),
-                                     sigmoid_exponent=float(self.args.sigmoid_exponent))
+                                     sigmoid_exponent=float(self.args.sigmoid_exponent),
+                                     semiring=self.args.train_mode)
         self._dirty = False
         return self
 

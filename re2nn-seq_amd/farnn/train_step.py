@@ -10,7 +10,8 @@ scores, the cross-entropy and the back-propagation through time -- is one librar
 computes loss and all gradients in its forward call (the stash lives in its workspace); backward()
 only hands them out, scaled by the incoming gradient.
 
-Scope: farnn = 0/1/2, sum semiring, CE1 loss or (use_crf) the CRF negative log-likelihood.
+Scope: farnn = 0/1/2, sum or max semiring (TrainContext(semiring=...)), CE1 loss or (use_crf) the CRF
+negative log-likelihood.
 
 The onehot i-FST (FARNN_S_O_I_S, model_onehot.py:351-428 + train_onehot.py:156-206) trains only
 language_tensor: one library call computes the loss, the tags and d loss / d language_tensor.
