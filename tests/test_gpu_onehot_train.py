@@ -9,7 +9,7 @@ import torch
 
 import onehot_train_ref as otr
 from test_onehot_train_cpu import N_CASES, case
-from util import GOLDEN, assert_float_path, ns
+from util import GOLDEN, assert_float_path, check_grad, ns, present_words
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +55,30 @@ def _run_step(T, W, O, h0, hT, P, x, lengths, labels, nl='none', threshold=0.5, 
     return float(loss.detach()), Tt.grad.cpu().numpy(), tags.cpu().numpy(), tc
 
 
+def run_step_c_abi(c, nl='none'):
+    """farnn_onehot_ifst_train_step called directly on pre-filled outputs (the autograd wrapper of _run_step allocates dT
+    with torch.empty_like, which says nothing about entries the library leaves alone); returns (loss, dT)"""
+    from re2nn_seq_amd import _lib
+    dev = torch.device('cuda', 0)
+    V, S, _ = c['T'].shape
+    tc = _lib.OnehotTrainContext(V, S, c['O'].shape[0], nl=nl, threshold=0.5, o_idx=0, device=0)
+    try:
+        w = {n: torch.from_numpy(np.ascontiguousarray(c[n], dtype=np.float32)).to(dev) for n in ('T', 'W', 'O', 'h0', 'hT')}
+        P = None if c['P'] is None else torch.from_numpy(np.ascontiguousarray(c['P'], dtype=np.float32)).to(dev)
+        x, lengths, labels = (torch.from_numpy(np.ascontiguousarray(c[n])).to(dev) for n in ('x', 'lengths', 'labels'))
+        B, L = c['x'].shape
+        dT = torch.full_like(w['T'], 7.0)                    # the library must zero it itself
+        loss = torch.full((1,), 3.0, device=dev)
+        tags = torch.empty((B, L), dtype=torch.int32, device=dev)
+        tc.step(dict({n: t.data_ptr() for n, t in w.items()}, P=None if P is None else P.data_ptr()), x.data_ptr(),
+                lengths.data_ptr(), labels.data_ptr(), B, L, int(np.clip(c['lengths'], 0, L).sum()),
+                dict(loss=loss.data_ptr(), dT=dT.data_ptr(), tags=tags.data_ptr()))
+        torch.cuda.synchronize()
+        return float(loss), dT.cpu().numpy()
+    finally:
+        tc.close()
+
+
 def _random_case(V, S, C, B, L, seed, priority=False):
     from re2nn_seq_amd import synth
     rng = np.random.RandomState(seed)
@@ -68,19 +92,26 @@ def _random_case(V, S, C, B, L, seed, priority=False):
     return dict(T=T, W=W, O=O, h0=h0, hT=hT, P=P, x=x, lengths=lengths, labels=labels)
 
 
-def _check_against_restatement(c, nl='none'):
-    loss, dT, _, _ = _run_step(nl=nl, **c)
+def _check_against_restatement(c, nl='none', case='onehot'):
+    """loss and dT by the ONE rule through the autograd wrapper; dT also by the gradient rule (tests/util.py:assert_grad_path)
+    through the C-ABI on a pre-filled buffer: at the tensor's own scale, block by block at each present word's scale,
+    exactly zero for the words that occur at no valid position"""
+    loss, dT, _, tc = _run_step(nl=nl, **c)
+    tc.close()
     l32, g32, _ = otr.step(dtype=torch.float32, nl=nl, **c)
     l64, g64, _ = otr.step(dtype=torch.float64, nl=nl, **c)
     assert_float_path(loss, l32, l64, err_msg='loss')
     assert_float_path(dT, g32, g64, err_msg='dT')
+    loss2, dT2 = run_step_c_abi(c, nl)
+    assert_float_path(loss2, l32, l64, err_msg='loss (C-ABI)')
+    check_grad(case, 'dT', dT2, g32, g64, slices=0, present=present_words(c['x'], c['lengths'], dT2.shape[0]))
 
 
 def test_headline_shape_against_the_restatement():
     """V = 950, S = 71, C = 128, B = 256, L = 64 with ragged lengths and one full-length row (bench.py's ifst shape)."""
     c = _random_case(950, 71, 128, 256, 64, seed=11)
     assert c['lengths'].max() == 64 and c['lengths'].min() < 64
-    _check_against_restatement(c)
+    _check_against_restatement(c, case='onehot headline')
 
 
 @pytest.mark.parametrize('S,B,L,nl,up', [(104, 64, 40, 'tanh', True), (104, 7, 9, 'relu', False),
@@ -88,7 +119,7 @@ def test_headline_shape_against_the_restatement():
                                          (14, 5, 1, 'none', False), (64, 17, 12, 'tanh', False)])
 def test_other_state_counts_and_geometries(S, B, L, nl, up):
     c = _random_case(300, S, 20, B, L, seed=S + B + L, priority=up)
-    _check_against_restatement(c, nl=nl)
+    _check_against_restatement(c, nl=nl, case='onehot S{} B{} L{} {}'.format(S, B, L, nl))
 
 
 def test_two_steps_are_bit_identical():

@@ -23,10 +23,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from oracle import farnn_train_oracle as to  # noqa: E402
-from test_gpu_onehot_train import _check_against_restatement, _random_case, _run_step  # noqa: E402
+from test_gpu_onehot_train import _check_against_restatement, _random_case, _run_step, run_step_c_abi  # noqa: E402
 import onehot_train_ref as otr  # noqa: E402
 from test_gpu_train_max import check_against, gapped_case, run_library  # noqa: E402
-from util import assert_float_path  # noqa: E402
+from util import assert_float_path, check_grad, present_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -136,8 +136,10 @@ def viterbi_tags_and_margin(sc, lengths, trans):
     return tags, gap
 
 
-def check_sum_step(res, ref32, ref64, lengths, farnn, trans=None, o_idx=1, threshold=0.5):
-    """loss and every gradient against the float64 and float32 oracle; tags against the float64 decode"""
+def check_sum_step(res, ref32, ref64, lengths, farnn, trans=None, o_idx=1, threshold=0.5, x=None, case='sum'):
+    """loss and every gradient against the float64 and float32 oracle, by the ONE rule and by the gradient rule (each tensor
+    at its own scale; with the batch `x`, dVgen also row by row at each present word's scale and exactly zero at the absent
+    ones); tags against the float64 decode"""
     (l32, g32, _), (l64, g64, sc64) = ref32, ref64
     crf = trans is not None
     assert_float_path([res['loss']], [float(l32)], [float(l64)], err_msg='loss')
@@ -145,8 +147,12 @@ def check_sum_step(res, ref32, ref64, lengths, farnn, trans=None, o_idx=1, thres
     for n, key in names:
         got = res['d' + n]
         assert_float_path(got, g32[key].numpy().reshape(got.shape), g64[key].numpy().reshape(got.shape), err_msg='d' + n)
+        sliced = n == 'Vgen' and x is not None
+        check_grad(case, 'd' + n, got, g32[key].numpy().reshape(got.shape), g64[key].numpy().reshape(got.shape),
+                   slices=0 if sliced else None, present=present_words(x, lengths, got.shape[0]) if sliced else None)
     if crf:
         assert_float_path(res['dtrans'], g32['crf.transitions'].numpy(), g64['crf.transitions'].numpy(), err_msg='dtrans')
+        check_grad(case, 'dtrans', res['dtrans'], g32['crf.transitions'].numpy(), g64['crf.transitions'].numpy())
     # tags where the decision is wider than float noise
     sc = sc64.numpy()
     B, L, K = sc.shape
@@ -201,7 +207,8 @@ def test_sum_step_forms_vs_float64_oracle(S, R, K, V, B, L, farnn, crf, nl):
     ref32 = sum_oracle(p, x, lengths, labels, nl, farnn, 3.0, torch.float32)
     tc = _lib.TrainContext(V, S, R, K, nl=nl, threshold=0.5, o_idx=1, use_crf=crf, farnn=farnn, sigmoid_exponent=3.0)
     res = SumRun(p, x, lengths, labels, farnn, crf).step(tc)
-    check_sum_step(res, ref32, ref64, lengths, farnn, p['crf.transitions'] if crf else None)
+    check_sum_step(res, ref32, ref64, lengths, farnn, p['crf.transitions'] if crf else None, x=x,
+                   case='envelope-sum S{} R{} K{} farnn{} crf{}'.format(S, R, K, farnn, int(crf)))
     tc.close()
 
 
@@ -236,7 +243,7 @@ def test_sum_step_refusals_leave_the_context_usable():
     torch.cuda.synchronize(dev)
     res = run.step(tc)
     check_sum_step(res, sum_oracle(p, x, lengths, labels, nl, farnn, 3.0, torch.float32),
-                   sum_oracle(p, x, lengths, labels, nl, farnn, 3.0, torch.float64), lengths, farnn)
+                   sum_oracle(p, x, lengths, labels, nl, farnn, 3.0, torch.float64), lengths, farnn, x=x, case='envelope-sum after refusals')
     tc.close()
 
 
@@ -260,7 +267,7 @@ def test_sum_step_refuses_more_than_512_states_or_rank(S, R):
 def test_max_step_at_its_limits_vs_float64_restatement(S, R, K, V, B, L, nl, farnn, crf, prio):
     w, x, lengths, labels, ref32, ref64 = gapped_case(S, R, K, V, B, L, nl, farnn, crf, prio, seed0=S + R)
     res, _ = run_library(w, x, lengths, labels, nl, farnn, crf)
-    check_against(res, ref32, ref64, farnn, crf)
+    check_against(res, ref32, ref64, farnn, crf, x=x, lengths=lengths, case='envelope-max S{} R{}'.format(S, R))
     mask = np.arange(L)[None, :] < lengths[:, None]
     assert (res['tags'][~mask] == -1).all()
 
@@ -279,7 +286,7 @@ def test_max_step_at_its_limits_vs_float64_restatement(S, R, K, V, B, L, nl, far
     128,   # chain <32> at OT_MAX_S, dT <8>
 ])
 def test_onehot_step_each_chain_and_dT_form(S):
-    _check_against_restatement(_random_case(300, S, 20, 9, 15, seed=S), nl='tanh')
+    _check_against_restatement(_random_case(300, S, 20, 9, 15, seed=S), nl='tanh', case='envelope-onehot S{}'.format(S))
 
 
 @pytest.mark.parametrize('S,C,B,L', [
@@ -291,7 +298,7 @@ def test_onehot_step_loss_forms_and_geometries(S, C, B, L):
     c = _random_case(300, S, C, B, L, seed=S + C + B)
     if B > 1:
         assert c['lengths'].max() == L and c['lengths'].min() < L
-    _check_against_restatement(c, nl='none')
+    _check_against_restatement(c, nl='none', case='envelope-onehot S{} C{} B{} L{}'.format(S, C, B, L))
 
 
 def test_onehot_create_refusals_and_the_score_column_limit():
@@ -306,6 +313,7 @@ def test_onehot_create_refusals_and_the_score_column_limit():
     l64, g64, _ = otr.step(dtype=torch.float64, **c)
     assert_float_path(loss, l32, l64, err_msg='loss')
     assert_float_path(dT, g32, g64, err_msg='dT')
+    check_grad('envelope-onehot C2332', 'dT', run_step_c_abi(c)[1], g32, g64, slices=0, present=present_words(c['x'], c['lengths'], 40))
     mask = np.arange(c['x'].shape[1])[None, :] < c['lengths'][:, None]
     assert (tags[~mask] == -1).all()
     tc.close()

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import decomp_max_train_ref as dmr  # noqa: E402
-from util import GOLDEN, assert_float_path, ns  # noqa: E402
+from util import GOLDEN, assert_float_path, check_grad, ns, present_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -164,7 +164,9 @@ def run_library(w, x, lengths, labels, nl, farnn, crf, semiring='max', tc=None, 
     return res, tc
 
 
-def check_against(res, ref32, ref64, farnn, crf, tol=1e-4):
+def check_against(res, ref32, ref64, farnn, crf, tol=1e-4, x=None, lengths=None, case='max'):
+    """the ONE rule and the gradient rule (each tensor at its own scale; with the batch, dVgen also row by row at each
+    present word's scale and exactly zero at the absent ones)"""
     l32, g32, _ = ref32
     l64, g64, _ = ref64
     assert_float_path([res['loss']], [l32], [l64], tol, 'loss')
@@ -172,6 +174,9 @@ def check_against(res, ref32, ref64, farnn, crf, tol=1e-4):
     for n in names:
         got = res['d' + n].reshape(g64[n].shape)
         assert_float_path(got, g32[n], g64[n], tol, 'd' + n)
+        sliced = n == 'Vgen' and x is not None
+        check_grad(case, 'd' + n, got, g32[n], g64[n], tol, slices=0 if sliced else None,
+                   present=present_words(x, lengths, got.shape[0]) if sliced else None)
 
 
 @pytest.mark.parametrize('S,R,K,V,B,L,nl,farnn,crf,prio', [
@@ -187,7 +192,7 @@ def test_c_abi_vs_float64_restatement(S, R, K, V, B, L, nl, farnn, crf, prio):
     """The C-ABI entry point with empty and full-length sequences, against the float64 restatement."""
     w, x, lengths, labels, ref32, ref64 = gapped_case(S, R, K, V, B, L, nl, farnn, crf, prio, seed0=S + R + farnn)
     res, tc = run_library(w, x, lengths, labels, nl, farnn, crf, steps=2)          # twice: the workspace is reused
-    check_against(res, ref32, ref64, farnn, crf)
+    check_against(res, ref32, ref64, farnn, crf, x=x, lengths=lengths, case='max S{} R{} K{} farnn{} crf{}'.format(S, R, K, farnn, int(crf)))
     t = res['tags']
     mask = np.arange(L)[None, :] < lengths[:, None]
     assert (t[~mask] == -1).all()
@@ -204,7 +209,7 @@ def test_ties_with_a_onehot_start_and_relu():
     S, R, K, V, B, L = 16, 8, 6, 12, 5, 7
     w, x, lengths, labels, ref32, ref64 = gapped_case(S, R, K, V, B, L, 'relu', 0, False, False, seed0=5, onehot_h=True)
     res, _ = run_library(w, x, lengths, labels, 'relu', 0, False)
-    check_against(res, ref32, ref64, 0, False)
+    check_against(res, ref32, ref64, 0, False, x=x, lengths=lengths, case='max ties')
 
 
 def test_steps_repeat_and_the_context_switches_back_to_sum():

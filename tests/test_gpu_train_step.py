@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 from oracle import farnn_train_oracle as to  # noqa: E402
+from util import assert_grad_path, check_grad, present_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -36,6 +37,27 @@ def load():
     with open(os.path.join(GOLDEN, 'decomp_train_small.json')) as f:
         meta = json.load(f)
     return meta, np.load(os.path.join(GOLDEN, 'decomp_train_small.npz')), np.load(os.path.join(GOLDEN, 'decomp_small.npz'))
+
+
+def dvgen_refs(p, x, lengths, labels, nl, farnn, sig_k, prio=False):
+    """d loss / d Vgen (leaf = to.generalized_table(p), the table the library is given) from the batched oracle in float32 and
+    in float64, and the words that occur at a valid position"""
+    table = to.generalized_table(p).detach()
+    ref = []
+    for dtype in (torch.float32, torch.float64):
+        q = {k: v.to(dtype) if v.dtype.is_floating_point else v for k, v in p.items()}
+        q.update(V_embed=table.to(dtype), beta_vec=torch.ones_like(q['beta_vec']))          # Vgen = V_embed exactly
+        _, g, _ = to.train_step_batched(q, torch.from_numpy(x), torch.from_numpy(lengths), torch.from_numpy(labels), nl=nl,
+                                        use_priority=prio, farnn=farnn, sig_k=sig_k)
+        ref.append(g['V_embed'].numpy())
+    return ref[0], ref[1], present_words(x, lengths, table.shape[0])
+
+
+def check_dvgen(case, got, p, x, lengths, labels, nl, farnn, sig_k, prio=False, slices=True):
+    """dVgen under the gradient rule (tests/util.py:assert_grad_path): at the tensor's scale and, with slices, row by row at
+    each present word's scale and exactly zero for the words that occur at no valid position."""
+    ref32, ref64, present = dvgen_refs(p, x, lengths, labels, nl, farnn, sig_k, prio)
+    check_grad(case, 'dVgen', got, ref32, ref64, slices=0 if slices else None, present=present if slices else None)
 
 
 def close(got, ref, name, rtol=2e-3, atol=2e-6, frac=2e-4):
@@ -351,7 +373,7 @@ def test_train_step_full_size_vs_batched_oracle(farnn, crf):
     w.update({n: p[n].to(dev).contiguous() for n in gate_names})
     trd = p['crf.transitions'].to(dev) if crf else None
     tc = _lib.TrainContext(V, S, R, K, nl='tanh', threshold=0.5, o_idx=1, use_crf=crf, farnn=farnn, sigmoid_exponent=3.0)
-    out = {'d' + n: torch.empty_like(t) for n, t in w.items()}
+    out = {'d' + n: torch.full_like(t, 7.0) for n, t in w.items()}           # the library must zero them itself
     dtr = torch.empty_like(trd) if crf else None
     loss = torch.empty(1, device=dev)
     tags = torch.empty((B, L), dtype=torch.int32, device=dev)
@@ -367,6 +389,23 @@ def test_train_step_full_size_vs_batched_oracle(farnn, crf):
         close(out['d' + n].cpu().numpy(), grads_ref[key].numpy().reshape(out['d' + n].shape), 'd' + n, rtol=5e-3)
     if crf:
         close(dtr.cpu().numpy(), grads_ref['crf.transitions'].numpy(), 'dtrans', rtol=5e-3)
+    case = 'full-size farnn{} crf{}'.format(farnn, int(crf))
+    if not crf:
+        check_dvgen(case, out['dVgen'].cpu().numpy(), p, x, lengths, labels, 'tanh', farnn, 3.0)
+    else:
+        # float32 carries log Z of a 75-tag CRF to about eps x log Z: 1e-5 relative once a sequence passes ~30 tokens, which is
+        # the rule's own bar for its float32 oracle (3.5 % of this batch's words sit beyond it, 1 % is the cap).  So the whole
+        # batch is held to the tensor clause, and the word clause runs on a second step of the same context with every
+        # sequence cut to 24 tokens, where the oracle is inside the rule's conditions.
+        check_dvgen(case, out['dVgen'].cpu().numpy(), p, x, lengths, labels, 'tanh', farnn, 3.0, slices=False)
+        short = np.minimum(lengths, 24)
+        sd = torch.from_numpy(short).to(dev)
+        tc.step(dict({n: t.data_ptr() for n, t in w.items()}, P=None, crf_trans=trd.data_ptr()),
+                xd.data_ptr(), sd.data_ptr(), labd.data_ptr(), B, L, int(short.sum()),
+                dict({n: t.data_ptr() for n, t in out.items()}, loss=loss.data_ptr(), tags=tags.data_ptr(), dtrans=dtr.data_ptr()))
+        torch.cuda.synchronize()
+        check_dvgen(case + ' 24 tokens', out['dVgen'].cpu().numpy(), p, x, short, labels, 'tanh', farnn, 3.0)
+    tc.close()
 
 
 def test_train_step_random_configurations_soak():
@@ -374,6 +413,7 @@ def test_train_step_random_configurations_soak():
     (FARNN_TRAIN_SOAK_ITERS configurations, default 8; 1500 ran, incl. 300 through the four-sequence through-L2 kernels)."""
     from re2nn_seq_amd import _lib
     iters = int(os.environ.get('FARNN_TRAIN_SOAK_ITERS', '8'))
+    badly_drawn = []
     rng = np.random.RandomState(int(os.environ.get('FARNN_TRAIN_SOAK_SEED', '123')))
     dev = torch.device('cuda')
     for it in range(iters):
@@ -413,7 +453,7 @@ def test_train_step_random_configurations_soak():
         P = p['priority_mat'].to(dev) if prio else None
         trd = p['crf.transitions'].to(dev) if crf else None
         tc = _lib.TrainContext(V, S, R, K, nl=nl, threshold=0.5, o_idx=0, use_crf=crf, farnn=farnn, sigmoid_exponent=2.0)
-        out = {'d' + n: torch.empty_like(t) for n, t in w.items()}
+        out = {'d' + n: torch.full_like(t, 7.0) for n, t in w.items()}       # the library must zero them itself
         dtr = torch.empty_like(trd) if crf else None
         loss = torch.empty(1, device=dev)
         tags = torch.empty((B, L), dtype=torch.int32, device=dev)
@@ -434,7 +474,21 @@ def test_train_step_random_configurations_soak():
             close(out['d' + n].cpu().numpy(), grads_ref[key].numpy().reshape(out['d' + n].shape), tag + ' d' + n, rtol=5e-3, frac=frac)
         if crf:
             close(dtr.cpu().numpy(), grads_ref['crf.transitions'].numpy(), tag + ' dtrans', rtol=5e-3, frac=frac)
+        # dVgen under the gradient rule.  Its conditions on the two oracles (float32 within 1e-5 of float64 at the tensor's
+        # scale, at most 1 % of the words beyond that at their own) fail for about one random configuration in twelve: a
+        # relu kink within float noise, or a long CRF sequence.  That is decided from the oracles alone, before the
+        # library's result is looked at; such a configuration keeps the comparisons above and is named at the end.
+        ref32, ref64, present = dvgen_refs(p, x, lengths, labels, nl, farnn, 2.0, prio)
+        try:
+            assert_grad_path(ref32, ref32, ref64, slices=0, present=present)
+        except AssertionError as e:
+            badly_drawn.append('{}: {}'.format(tag, e))
+        else:
+            check_grad('soak ' + tag, 'dVgen', out['dVgen'].cpu().numpy(), ref32, ref64, slices=0, present=present)
         tc.close()
+    print('soak: dVgen not held to the gradient rule in {} of {} configurations (badly drawn oracles): {}'.format(
+        len(badly_drawn), iters, badly_drawn))
+    assert len(badly_drawn) <= max(1, iters // 4), badly_drawn   # the soak must not quietly stop checking dVgen this way
 
 
 @pytest.mark.parametrize('mode', ['1', '2', '1n4'])
@@ -484,7 +538,7 @@ def test_train_step_rank_250_gated_crf_vs_batched_oracle(R):
     w.update({n: p[n].to(dev).contiguous() for n in gate_names})
     trd = p['crf.transitions'].to(dev)
     tc = _lib.TrainContext(V, S, R, K, nl='tanh', threshold=0.5, o_idx=1, use_crf=True, farnn=farnn, sigmoid_exponent=3.0)
-    out = {'d' + n: torch.empty_like(t) for n, t in w.items()}
+    out = {'d' + n: torch.full_like(t, 7.0) for n, t in w.items()}           # the library must zero them itself
     dtr = torch.empty_like(trd)
     loss = torch.empty(1, device=dev)
     tags = torch.empty((B, L), dtype=torch.int32, device=dev)
@@ -498,6 +552,8 @@ def test_train_step_rank_250_gated_crf_vs_batched_oracle(R):
             tuple((n, n) for n in gate_names):
         close(out['d' + n].cpu().numpy(), grads_ref[key].numpy().reshape(out['d' + n].shape), 'd' + n, rtol=5e-3)
     close(dtr.cpu().numpy(), grads_ref['crf.transitions'].numpy(), 'dtrans', rtol=5e-3)
+    check_dvgen('rank-{} farnn2 crf'.format(R), out['dVgen'].cpu().numpy(), p, x, lengths, labels, 'tanh', farnn, 3.0)
+    tc.close()
 
 
 def test_train_step_reports_out_of_range_labels_and_crf_size_limits():
