@@ -391,7 +391,9 @@ int  farnn_train_create(const farnn_train_dims *dims, int device, farnn_train_ct
 void farnn_train_destroy(farnn_train_ctx *ctx);
 /* One step on the given stream: zeroes the outputs, runs both chains with the state stash, the loss, the
  * back-propagation through time and the parameter-gradient reductions.  x, lengths, labels: int64
- * [B][L], [B], [B][L] (labels outside 0..K-1 are treated as 0; they only matter at valid positions). */
+ * [B][L], [B], [B][L] (labels outside 0..K-1 are treated as 0; they only matter at valid positions).
+ * Every FARNN_ERANGE (the CRF limit, more than 512 states or rank, the 2^30 element bound, a launch above 160 KiB of LDS) is
+ * returned before anything is enqueued: a refused step leaves the output buffers untouched. */
 int  farnn_decomp_ifst_train_step(farnn_train_ctx *ctx, const farnn_train_weights *w, const int64_t *x,
                                   const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                   int64_t valid_tokens, const farnn_train_outputs *out, void *stream);

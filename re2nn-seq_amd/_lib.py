@@ -515,16 +515,54 @@ def create_decomp_fst(Vgen, Cemb, S1, S2, Cw, S1w, S2w, WW, h0, hT, P=None, farn
                    (Vgen, Cemb, S1, S2, Cw, S1w, S2w, WW, h0, hT, P, crf_trans, g))
 
 
-class TrainContext:
+class _TrainContextBase:
+    """Owns one training context of the C-ABI (include/farnn.h).  A subclass names its five C symbols and its two struct types."""
+    _create = _destroy = _step = _set_profiling = _time = None
+    _weights = _outputs = None
+    _raw = None
+
+    def _open(self, dims, device):
+        out = C.c_void_p()
+        check(getattr(load(), self._create)(C.byref(dims), int(device), C.byref(out)), self._create)
+        self._raw = out
+
+    def close(self):
+        if self._raw:
+            getattr(load(), self._destroy)(self._raw)
+            self._raw = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, weights, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, stream=None):
+        """weights / outputs: dicts of device pointers (ints) keyed like the C structs."""
+        w = self._weights(**{k: (weights.get(k) or None) for k, _ in self._weights._fields_})
+        o = self._outputs(**{k: outputs.get(k) for k, _ in self._outputs._fields_})
+        check(getattr(load(), self._step)(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, int(B), int(L),
+                                          int(valid_tokens), C.byref(o), stream), self._step)
+
+    def set_profiling(self, enable):
+        check(getattr(load(), self._set_profiling)(self._raw, int(enable)), self._set_profiling)
+
+    def time(self):
+        ms, n = C.c_double(0), C.c_int64(0)
+        check(getattr(load(), self._time)(self._raw, C.byref(ms), C.byref(n)), self._time)
+        return ms.value, n.value
+
+
+class TrainContext(_TrainContextBase):
     """Owns one farnn_train_ctx* (training step of the decomposed i-FST, include/farnn.h)."""
+    _create, _destroy, _step = 'farnn_train_create', 'farnn_train_destroy', 'farnn_decomp_ifst_train_step'
+    _set_profiling, _time = 'farnn_train_set_profiling', 'farnn_train_time'
+    _weights, _outputs = TrainWeights, TrainOutputs
 
     def __init__(self, V, S, R, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0,
                  sigmoid_exponent=5.0, semiring='sum'):
-        d = TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
-                      float(sigmoid_exponent), int(bool(use_crf)))
-        out = C.c_void_p()
-        check(load().farnn_train_create(C.byref(d), int(device), C.byref(out)), 'farnn_train_create')
-        self._raw = out
+        self._open(TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
+                             float(sigmoid_exponent), int(bool(use_crf))), device)
         self.dims = (int(V), int(S), int(R), int(K))
         if semiring != 'sum':
             self.set_semiring(semiring)
@@ -533,67 +571,13 @@ class TrainContext:
         """'sum' or 'max' (the reference's --train_mode) for the following steps."""
         check(load().farnn_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_train_set_semiring')
 
-    def close(self):
-        if self._raw:
-            load().farnn_train_destroy(self._raw)
-            self._raw = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def step(self, weights, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, stream=None):
-        """weights / outputs: dicts of device pointers (ints) keyed like the C structs."""
-        w = TrainWeights(**{k: (weights.get(k) or None) for k, _ in TrainWeights._fields_})
-        o = TrainOutputs(**{k: outputs.get(k) for k, _ in TrainOutputs._fields_})
-        check(load().farnn_decomp_ifst_train_step(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, int(B), int(L),
-                                                  int(valid_tokens), C.byref(o), stream),
-              'farnn_decomp_ifst_train_step')
-
-    def set_profiling(self, enable):
-        check(load().farnn_train_set_profiling(self._raw, int(enable)), 'farnn_train_set_profiling')
-
-    def time(self):
-        ms, n = C.c_double(0), C.c_int64(0)
-        check(load().farnn_train_time(self._raw, C.byref(ms), C.byref(n)), 'farnn_train_time')
-        return ms.value, n.value
-
-
-class OnehotTrainContext:
+class OnehotTrainContext(_TrainContextBase):
     """Owns one farnn_onehot_train_ctx* (training step of the onehot i-FST, include/farnn.h)."""
+    _create, _destroy, _step = 'farnn_onehot_train_create', 'farnn_onehot_train_destroy', 'farnn_onehot_ifst_train_step'
+    _set_profiling, _time = 'farnn_onehot_train_set_profiling', 'farnn_onehot_train_time'
+    _weights, _outputs = OnehotTrainWeights, OnehotTrainOutputs
 
     def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
-        d = OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx))
-        out = C.c_void_p()
-        check(load().farnn_onehot_train_create(C.byref(d), int(device), C.byref(out)), 'farnn_onehot_train_create')
-        self._raw = out
+        self._open(OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
         self.dims = (int(V), int(S), int(n_cols))
-
-    def close(self):
-        if self._raw:
-            load().farnn_onehot_train_destroy(self._raw)
-            self._raw = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def step(self, weights, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, stream=None):
-        """weights / outputs: dicts of device pointers (ints) keyed like the C structs."""
-        w = OnehotTrainWeights(**{k: (weights.get(k) or None) for k, _ in OnehotTrainWeights._fields_})
-        o = OnehotTrainOutputs(**{k: outputs.get(k) for k, _ in OnehotTrainOutputs._fields_})
-        check(load().farnn_onehot_ifst_train_step(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, int(B), int(L),
-                                                  int(valid_tokens), C.byref(o), stream),
-              'farnn_onehot_ifst_train_step')
-
-    def set_profiling(self, enable):
-        check(load().farnn_onehot_train_set_profiling(self._raw, int(enable)), 'farnn_onehot_train_set_profiling')
-
-    def time(self):
-        ms, n = C.c_double(0), C.c_int64(0)
-        check(load().farnn_onehot_train_time(self._raw, C.byref(ms), C.byref(n)), 'farnn_onehot_train_time')
-        return ms.value, n.value

@@ -89,13 +89,18 @@ inline int tun(TunId id) {
     return (g_tun ? g_tun : &defaults_at_load)->v[id];
 }
 
+// The refusal of a launch whose dynamic LDS cannot fit a workgroup (pure: a step can ask before it enqueues anything)
+inline int lds_fits(size_t bytes) {
+    return bytes > 160 * 1024 ? fail(FARNN_ERANGE, "kernel needs more than 160 KiB of LDS%s%s") : FARNN_OK;
+}
+
 // Raise a kernel's dynamic-LDS limit (needed above 48 KiB).  The attribute is sticky, so it is set
 // only when a kernel needs more than it was last given (a host API call per launch otherwise).
 template <typename KernelT>
 inline int raise_lds_limit(KernelT kern, size_t bytes) {
     static std::map<std::pair<int, const void *>, size_t> granted;    // (device, kernel) -> bytes
     static std::mutex granted_mu;                                     // (handles on different threads share the map)
-    if (bytes > 160 * 1024) return fail(FARNN_ERANGE, "kernel needs more than 160 KiB of LDS%s%s");
+    if (int rc = lds_fits(bytes)) return rc;
     if (bytes <= 48 * 1024) return FARNN_OK;
     int dev = 0;
     (void)hipGetDevice(&dev);

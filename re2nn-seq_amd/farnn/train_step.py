@@ -24,29 +24,38 @@ from .. import _lib
 GATE_NAMES = ('Wss1', 'Wrs1', 'bs1', 'Wss2', 'Wrs2', 'bs2')
 
 
+def _f32(t):
+    return None if t is None else t.detach().contiguous().float()
+
+
+def _step_inputs(ref, ntok, x, lengths, labels):
+    """What both steps do before the library call: the device check on `ref` (a weight), the token count, x / lengths /
+    labels on the device, the loss and tags outputs.  Returns (dev, ntok, x, lengths, labels, loss, tags)."""
+    dev = ref.device
+    if dev.type != 'cuda':
+        raise _lib.FarnnError('the training step runs on the HIP device only (no CPU fallback)')
+    B, L = x.shape
+    if ntok is None:            # counted on the host when the lengths live there (no device round trip in the step)
+        ntok = int(lengths.clamp(0, L).sum())
+    x, lengths, labels = (t.to(dev).contiguous() for t in (x, lengths, labels))
+    if ntok <= 0:
+        raise ValueError('empty batch')
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    tags = torch.empty((B, L), dtype=torch.int32, device=dev)
+    return dev, ntok, x, lengths, labels, loss, tags
+
+
 class _DecompIfstTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cmat, h0, hT, trans, *gates):
-        dev = Vgen.device
-        if dev.type != 'cuda':
-            raise _lib.FarnnError('the training step runs on the HIP device only (no CPU fallback)')
-        ws = [t.detach().contiguous().float() for t in (Vgen, S1, S2, W, Cmat, h0, hT)]
-        Pc = None if P is None else P.detach().contiguous().float()
-        tr = None if trans is None else trans.detach().contiguous().float()
-        gs = [g.detach().contiguous().float() for g in gates]
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(Vgen, ntok, x, lengths, labels)
         B, L = x.shape
-        if ntok is None:            # counted on the host when the lengths live there (no device round trip in the step)
-            ntok = int(lengths.clamp(0, L).sum())
-        x = x.to(dev).contiguous()
-        lengths = lengths.to(dev).contiguous()
-        labels = labels.to(dev).contiguous()
-        if ntok <= 0:
-            raise ValueError('empty batch')
+        ws = [_f32(t) for t in (Vgen, S1, S2, W, Cmat, h0, hT)]
+        Pc, tr = _f32(P), _f32(trans)
+        gs = [_f32(g) for g in gates]
         grads = [torch.empty_like(t) for t in ws]
         gtr = None if tr is None else torch.empty_like(tr)
         ggs = [torch.empty_like(g) for g in gs]
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        tags = torch.empty((B, L), dtype=torch.int32, device=dev)
         names = ('Vgen', 'S1', 'S2', 'W', 'C', 'h0', 'hT')
         weights = {n: t.data_ptr() for n, t in zip(names, ws)}
         weights['P'] = None if Pc is None else Pc.data_ptr()
@@ -91,22 +100,11 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
 class _OnehotIfstTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
-        dev = T.device
-        if dev.type != 'cuda':
-            raise _lib.FarnnError('the training step runs on the HIP device only (no CPU fallback)')
-        ws = {n: t.detach().contiguous().float() for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
-        Pc = None if P is None else P.detach().contiguous().float()
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T, ntok, x, lengths, labels)
         B, L = x.shape
-        if ntok is None:            # counted on the host when the lengths live there (no device round trip in the step)
-            ntok = int(lengths.clamp(0, L).sum())
-        x = x.to(dev).contiguous()
-        lengths = lengths.to(dev).contiguous()
-        labels = labels.to(dev).contiguous()
-        if ntok <= 0:
-            raise ValueError('empty batch')
+        ws = {n: _f32(t) for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
+        Pc = _f32(P)
         dT = torch.empty_like(ws['T'])
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        tags = torch.empty((B, L), dtype=torch.int32, device=dev)
         weights = {n: t.data_ptr() for n, t in ws.items()}
         weights['P'] = None if Pc is None else Pc.data_ptr()
         outputs = {'loss': loss.data_ptr(), 'dT': dT.data_ptr(), 'tags': tags.data_ptr()}

@@ -1,6 +1,6 @@
 """The three HIP training steps at every kernel form and size limit their C-ABI accepts, against high-precision references.
 
-The host code (csrc/farnn_train.hip) picks a template instantiation per step from S, R, K, L, B and the device's CU count.
+The host code (csrc/farnn_train.hip, with the shared pieces of csrc/train_host.hip.h) picks a template instantiation per step from S, R, K, L, B and the device's CU count.
 Each case below is shaped to reach one form, named in its comment:
   decomposed sum step  train_forward_kernel / train_backward_kernel <LDSW, GATED, S slots, R slots, NSEQ> (weights in LDS
                        when vec + mat <= 160 KiB, else through L2 with nss of the S x S matrices in LDS; four sequences per
@@ -221,8 +221,8 @@ def _expect_erange(call, match):
 
 def test_sum_step_refusals_leave_the_context_usable():
     """On one live context (S = R = 512, farnn 2): a batch with B (L+1) max(S, R) >= 2^30 is refused before anything is
-    enqueued; a sequence length whose forward chain kernel needs more than 160 KiB of LDS is refused by raise_lds_limit
-    after the step's preparation kernels were enqueued.  A valid step on the same context then matches the oracle."""
+    enqueued; so is a sequence length whose forward chain kernel needs more than 160 KiB of LDS (the step's plan refuses
+    it).  Both leave the pre-filled output buffers as they were.  A valid step on the same context then matches the oracle."""
     from re2nn_seq_amd import _lib
     S = R = 512
     K, V, farnn, nl = 12, 40, 2, 'tanh'
@@ -234,7 +234,16 @@ def test_sum_step_refusals_leave_the_context_usable():
     def refused_step(B, L):
         # inputs of the full size, so that nothing could be read past an end even if the refusal were missing
         big = SumRun(p, np.zeros((B, L), np.int64), np.full(B, L, np.int64), np.zeros((B, L), np.int64), farnn, False)
-        return lambda: big.step(tc)
+
+        def call():
+            try:
+                big.step(tc)
+            finally:        # a refused step has enqueued nothing: the outputs still hold what SumRun filled them with
+                torch.cuda.synchronize(dev)
+                assert float(big.loss) == 3.0
+                for n, t in big.out.items():
+                    assert bool((t == 7.0).all()), n
+        return call
 
     B, L = 2048, 1024
     assert B * (L + 1) * max(S, R) >= 1 << 30
