@@ -1,9 +1,11 @@
 // Host-side helpers shared by the translation units of libfarnn_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdlib.h>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include "common.hip.h"
 
@@ -113,5 +115,45 @@ inline int raise_lds_limit(KernelT kern, size_t bytes) {
     }
     return FARNN_OK;
 }
+
+// The one way a kernel with dynamic LDS is launched: raise its LDS limit if it needs that, then enqueue it (the kernel is named once).
+template <typename... Params, typename... Args>
+inline int launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t s, Args &&...args) {
+    if (int rc = raise_lds_limit(kern, lds)) return rc;
+    kern<<<grid, block, lds, s>>>(std::forward<Args>(args)...);
+    return FARNN_OK;
+}
+// The same with the event pair of a timer that rides on the kernel's own dispatch packet (both null: a plain launch).
+template <typename... Params, typename... Args>
+inline int launch_timed(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+                        Args &&...args) {
+    if (int rc = raise_lds_limit(kern, lds)) return rc;
+    if (e0 && e1) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, e0, e1, 0, std::forward<Args>(args)...);
+    else kern<<<grid, block, lds, s>>>(std::forward<Args>(args)...);
+    return FARNN_OK;
+}
+template <int N>
+using int_c = std::integral_constant<int, N>;
+inline int device_cus(int device) {      // compute units (256 if the device does not say)
+    int ncu = 0;
+    return hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0 ? ncu : 256;
+}
+
+// A device buffer that only grows.  A too-small one is freed after a device synchronize (an earlier step's kernels may still
+// use it).  `what` is the whole message of a failed allocation: it names the step and the buffer, and ends in "%s%s" (fail()).
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    ~DevBuf() { release(); }
+    int ensure(size_t need, const char *what) {
+        if (need <= n) return FARNN_OK;
+        if (p) { FARNN_HIP_TRY(hipDeviceSynchronize()); release(); }
+        if (hipMalloc((void **)&p, need * sizeof(T)) != hipSuccess) { p = nullptr; return fail(FARNN_ENOMEM, what); }
+        n = need;
+        return FARNN_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+};
 
 }  // namespace farnn

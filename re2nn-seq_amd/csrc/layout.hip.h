@@ -151,3 +151,70 @@ __global__ void materialise_blocks_kernel(const float *Vgen, const float *S1, co
 }
 
 }  // namespace farnn
+
+// ---- create-time and staging kernels of farnn_hip.hip: at global scope, as they have always been (their names stay as they are) ----
+// the word table and --normalize_automata on the device
+// avg[c] = ||M[:, c]||_ord / rows   (utils.get_average, '-rank' modes; reference utils.py:202-225)
+__global__ void col_avg_norm_kernel(const float *M, int rows, int cols, int ld, int ord, float *avg) {
+    const int c = blockIdx.x;
+    __shared__ float red[256];
+    float acc = 0.0f;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        const float v = M[(long long)r * ld + c];
+        acc += ord == 1 ? fabsf(v) : v * v;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) avg[c] = (ord == 1 ? red[0] : sqrtf(red[0])) / (float)rows;
+}
+
+// factor = cbrt(v_avg s1_avg s2_avg); scale[0][c] = factor / v_avg, [1][c] = factor / s1_avg, [2][c] = factor / s2_avg  (init_params.py:285-297)
+__global__ void norm_scales_kernel(const float *avg /*[3][R]*/, float *scale /*[3][R]*/, int R) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= R) return;
+    const float f = cbrtf(avg[c] * avg[R + c] * avg[2 * R + c]);
+    scale[c] = f / avg[c]; scale[R + c] = f / avg[R + c]; scale[2 * R + c] = f / avg[2 * R + c];
+}
+
+// G[i][j] = sum_r M[r][i] M[r][j]  (the Gram matrix of the columns, doubles: its largest eigenvalue is the squared spectral norm)
+__global__ void gram_kernel(const float *M, int rows, int cols, double *G) {
+    const int i = blockIdx.x, j = blockIdx.y;
+    if (j > i) return;
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) acc += (double)M[(long long)r * cols + i] * (double)M[(long long)r * cols + j];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) { G[(long long)i * cols + j] = red[0]; G[(long long)j * cols + i] = red[0]; }
+}
+
+__global__ void scale_cols_kernel(float *M, long long n, int cols, const float *scale) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) M[i] *= scale[i % cols];
+}
+
+// Vgen[w][r] = V[w][r] cv[r] beta[r] + nl_add( sum_d E[w][d] G[d][r] cv[r] ) (1 - beta[r])      (model_decompose.py:222-241)
+// cv = the normalisation scale of V_embed's columns (1 without): G = pinv(E) V_embed is linear in V_embed's columns
+__global__ void fold_vgen_kernel(const float *Vemb, const float *E, const float *G, const float *beta, const float *cv,
+                                 float *Vgen, int V, int R, int D, int add_nl) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)V * R) return;
+    const int w = (int)(idx / R), r = (int)(idx % R);
+    float g = 0.0f;
+    for (int d = 0; d < D; d++) g = fmaf(E[(long long)w * D + d], G[(long long)d * R + r], g);
+    const float c = cv ? cv[r] : 1.0f;
+    const float b = beta[r];
+    Vgen[idx] = Vemb[idx] * c * b + farnn::apply_nl(g * c, add_nl) * (1.0f - b);
+}
+
+// [x | lengths] from the pinned (device-mapped) staging buffer into device memory, by a kernel on the tagging stream: an
+// SDMA copy on the same stream costs an engine hand-over before and after the recurrence (measured: 38 us of copies and
+// hand-overs per 256 x 64 batch against ~6 us for this kernel; the flat predictions need no copy at all: the decode
+// epilogue stores them straight into mapped host memory)
+__global__ void stage_in_kernel(const int64_t *__restrict__ src, int64_t *__restrict__ dst, long long n) {
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 2;
+    if (i + 1 < n) *reinterpret_cast<int4 *>(dst + i) = *reinterpret_cast<const int4 *>(src + i);
+    else if (i < n) dst[i] = src[i];
+}

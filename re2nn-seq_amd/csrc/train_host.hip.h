@@ -1,8 +1,7 @@
-// Host-side pieces shared by the training steps (farnn_train.hip): the grow-only device buffer, the carver that sizes and lays
-// out a workspace with one piece of code, step profiling, the pinned error word, and the launches both steps make.
+// Host-side pieces shared by the training steps (farnn_train.hip): the carver that sizes and lays out a workspace with one piece
+// of code, step profiling, the pinned error word, and the launches both steps make (DevBuf and launch: host_util.hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <type_traits>
 #include <utility>
 #include <vector>
 #include "host_util.hip.h"
@@ -10,23 +9,6 @@
 #include "onehot_train.hip.h"
 
 namespace farnn {
-
-// A device buffer that only grows.  A too-small one is freed after a device synchronize (an earlier step's kernels may still
-// use it).  `what` is the whole message of a failed allocation: it names the step and the buffer, and ends in "%s%s" (fail()).
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    int ensure(size_t need, const char *what) {
-        if (need <= n) return FARNN_OK;
-        if (p) { FARNN_HIP_TRY(hipDeviceSynchronize()); release(); }
-        if (hipMalloc((void **)&p, need * sizeof(T)) != hipSuccess) { p = nullptr; return fail(FARNN_ENOMEM, what); }
-        n = need;
-        return FARNN_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 // One piece of code gives a workspace's size and its layout: a carve function calls take() once per array.  Run on a null base
 // it only counts (`off` is the total); run on the buffer it hands out the pointers.  A sum cannot drift from its walk.
@@ -100,20 +82,6 @@ struct ErrWord {
         return FARNN_OK;
     }
 };
-
-// The one way a kernel with dynamic LDS is launched: raise its LDS limit if it needs that, then enqueue it (the kernel is named once).
-template <typename... Params, typename... Args>
-inline int launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t s, Args &&...args) {
-    if (int rc = raise_lds_limit(kern, lds)) return rc;
-    kern<<<grid, block, lds, s>>>(std::forward<Args>(args)...);
-    return FARNN_OK;
-}
-template <int N>
-using int_c = std::integral_constant<int, N>;
-inline int device_cus(int device) {      // compute units (256 if the device does not say)
-    int ncu = 0;
-    return hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0 ? ncu : 256;
-}
 
 // ---- the positions of a batch bucketed by word (onehot_train.hip.h) ------------------------------------------------------
 struct Buckets {
