@@ -450,6 +450,44 @@ int  farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *ctx, const farnn_oneho
 int  farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *ctx, int32_t enable);
 int  farnn_onehot_train_time(farnn_onehot_train_ctx *ctx, double *total_ms, int64_t *steps);
 
+/* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
+ * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,
+ * no weight decay, no amsgrad:
+ *     exp_avg    += (grad - exp_avg) (1 - beta1)
+ *     exp_avg_sq  = beta2 exp_avg_sq + (1 - beta2) grad^2
+ *     param      -= (lr / bc1) exp_avg / (sqrt(exp_avg_sq) / sqrt(bc2) + eps),   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
+ * with t the tensor's OWN step count, kept by the handle on the host (bc1, bc2 in double); SGD: param -= lr grad.
+ * The handle owns the chunk table of the tensors' sizes and the step counts, nothing else: parameters, gradients and both
+ * moments are the caller's device memory (float32, contiguous), handed over per step and never retained.
+ * farnn_optim_step must NOT be captured into a HIP graph: the bias corrections are computed on the host per call and travel
+ * as kernel arguments, so a replayed capture would repeat the corrections of the step it was captured at. */
+typedef struct farnn_optim farnn_optim;
+#define FARNN_OPTIM_SGD   0
+#define FARNN_OPTIM_ADAM  1
+
+typedef struct {
+    int32_t kind;               /* FARNN_OPTIM_SGD or FARNN_OPTIM_ADAM                                        */
+    double  lr;                 /* >= 0                                                                        */
+    double  beta1, beta2;       /* Adam: in [0, 1) (torch's defaults: 0.9, 0.999); SGD: ignored                */
+    double  eps;                /* Adam: >= 0 (torch's default: 1e-8); SGD: ignored                            */
+} farnn_optim_desc;
+
+/* numel[n]: the element count of each tensor, in the order every later call lists them.  FARNN_EINVAL: an unknown kind, n <= 0,
+ * a numel <= 0, lr / betas / eps outside the ranges above. */
+int  farnn_optim_create(const farnn_optim_desc *desc, const int64_t *numel, int32_t n, int device, farnn_optim **out);
+void farnn_optim_destroy(farnn_optim *opt);
+/* One step on the given stream (hipStream_t as void*, NULL = the default stream; enqueued, not awaited).  params, grads, exp_avg,
+ * exp_avg_sq: HOST arrays of n DEVICE pointers; exp_avg and exp_avg_sq may be NULL for SGD.  A tensor whose grads[i] is NULL is
+ * skipped: its memory is untouched and its step count does not advance (torch's behaviour for `grad is None`).  FARNN_EINVAL
+ * (a NULL params[i], or a NULL moment under Adam, for a tensor that has a gradient) is returned before anything is enqueued
+ * or counted. */
+int  farnn_optim_step(farnn_optim *opt, float *const *params, const float *const *grads, float *const *exp_avg,
+                      float *const *exp_avg_sq, void *stream);
+int  farnn_optim_set_lr(farnn_optim *opt, double lr);
+/* the step count of tensor i (the steps in which it had a gradient); farnn_optim_set_steps restores it from saved state */
+int  farnn_optim_steps(const farnn_optim *opt, int32_t i, int64_t *out);
+int  farnn_optim_set_steps(farnn_optim *opt, int32_t i, int64_t steps);
+
 /* ---- introspection / measurement ----------------------------------------------------- */
 int  farnn_abi_version(void);
 /* 1: the A/B (profiling) build of the library (csrc/build.py --probes): it also carries the forms the production build left behind --

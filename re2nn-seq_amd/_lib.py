@@ -131,7 +131,21 @@ class OnehotTrainOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT', 'tags')]
 
 
+class OptimDesc(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
+
+
+OPTIM_SGD, OPTIM_ADAM = 0, 1
+OPTIM_CHUNK, OPTIM_MAX_TENSORS = 2048, 32      # csrc/optim.hip.h: elements per workgroup, tensors per launch
+
 SIGNATURES = {
+    'farnn_optim_create': (C.c_int, [C.POINTER(OptimDesc), C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_optim_destroy': (None, [C.c_void_p]),
+    'farnn_optim_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), C.c_void_p]),
+    'farnn_optim_set_lr': (C.c_int, [C.c_void_p, C.c_double]),
+    'farnn_optim_steps': (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    'farnn_optim_set_steps': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     'farnn_onehot_train_create': (C.c_int, [C.POINTER(OnehotTrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_onehot_train_destroy': (None, [C.c_void_p]),
     'farnn_onehot_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(OnehotTrainWeights), C.c_void_p, C.c_void_p,
@@ -581,3 +595,53 @@ class OnehotTrainContext(_TrainContextBase):
     def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
         self._open(OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
         self.dims = (int(V), int(S), int(n_cols))
+
+
+class Optim:
+    """Owns one farnn_optim* (the multi-tensor optimizer step, include/farnn.h): the chunk table of the tensors' sizes and
+    their step counts.  Parameters, gradients and moments stay the caller's; step() takes their device pointers."""
+
+    def __init__(self, kind, numel, lr, beta1=0.9, beta2=0.999, eps=1e-8, device=0):
+        self._raw = None
+        self.n = len(numel)
+        self.lr = float(lr)
+        sizes = (C.c_int64 * max(self.n, 1))(*[int(v) for v in numel])
+        out = C.c_void_p()
+        check(load().farnn_optim_create(C.byref(OptimDesc(int(kind), self.lr, float(beta1), float(beta2), float(eps))), sizes,
+                                        self.n, int(device), C.byref(out)), 'farnn_optim_create')
+        self._raw = out
+        self._arrays = tuple((C.c_void_p * self.n)() for _ in range(4))      # params, grads, exp_avg, exp_avg_sq
+
+    def close(self):
+        if self._raw:
+            load().farnn_optim_destroy(self._raw)
+            self._raw = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, params, grads, exp_avg=None, exp_avg_sq=None, stream=None):
+        """params / grads / exp_avg / exp_avg_sq: sequences of device pointers (ints; None or 0 in grads: that tensor is
+        skipped).  exp_avg and exp_avg_sq are None for SGD."""
+        P, G, M, V = self._arrays
+        for i in range(self.n):
+            P[i], G[i] = params[i], grads[i]
+            if exp_avg is not None:
+                M[i], V[i] = exp_avg[i], exp_avg_sq[i]
+        check(load().farnn_optim_step(self._raw, P, G, None if exp_avg is None else M, None if exp_avg is None else V, stream),
+              'farnn_optim_step')
+
+    def set_lr(self, lr):
+        check(load().farnn_optim_set_lr(self._raw, float(lr)), 'farnn_optim_set_lr')
+        self.lr = float(lr)
+
+    def steps(self, i):
+        n = C.c_int64(0)
+        check(load().farnn_optim_steps(self._raw, int(i), C.byref(n)), 'farnn_optim_steps')
+        return n.value
+
+    def set_steps(self, i, n):
+        check(load().farnn_optim_set_steps(self._raw, int(i), int(n)), 'farnn_optim_set_steps')

@@ -1,9 +1,10 @@
 // libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h) and the onehot
-// i-FST (farnn_onehot_train_*).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
+// i-FST (farnn_onehot_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
 // loss) compile once, beside the tagging path.  Each step is a sequence of named stages (the static functions below, in the
 // order they run); what both steps share on the host side is in train_host.hip.h.
 #include <hip/hip_runtime.h>
 #include <assert.h>
+#include <math.h>
 #include <algorithm>
 #include <vector>
 
@@ -11,6 +12,7 @@
 #include "host_util.hip.h"
 #include "train_host.hip.h"
 #include "train_max.hip.h"
+#include "optim.hip.h"
 
 using namespace farnn;
 
@@ -617,5 +619,130 @@ extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const far
         (rc = t.dT())) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     c->prof.end(t.s);
+    return FARNN_OK;
+}
+
+// ---- the optimizer step (farnn_optim_*; optim.hip.h) -------------------------------------------------------------------
+struct farnn_optim {
+    farnn_optim_desc d;
+    int device = 0;
+    std::vector<int64_t> numel, steps;        // per tensor: elements; the steps in which it had a gradient
+    struct Launch { int t0, nt; size_t c0; unsigned nchunks; };   // tensors t0 .. t0 + nt - 1, their chunks in the table
+    std::vector<Launch> launches;
+    DevBuf<OptChunk> chunks;                  // the chunk table, written once by create
+};
+
+static int optim_check_desc(const farnn_optim_desc *d) {
+    if (d->kind != FARNN_OPTIM_SGD && d->kind != FARNN_OPTIM_ADAM) return fail(FARNN_EINVAL, "optim_create: kind must be FARNN_OPTIM_SGD or FARNN_OPTIM_ADAM%s%s");
+    if (!(d->lr >= 0.0) || d->lr > 3.0e38) return fail(FARNN_EINVAL, "optim_create: lr must be a finite number >= 0%s%s");
+    if (d->kind == FARNN_OPTIM_ADAM && (!(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0) ||
+                                        !(d->eps >= 0.0) || d->eps > 3.0e38))
+        return fail(FARNN_EINVAL, "optim_create: betas must lie in [0, 1) and eps must be a finite number >= 0%s%s");
+    return FARNN_OK;
+}
+
+extern "C" int farnn_optim_create(const farnn_optim_desc *desc, const int64_t *numel, int32_t n, int device, farnn_optim **out) {
+    if (!desc || !numel || !out) return fail(FARNN_EINVAL, "optim_create: null argument%s%s");
+    *out = nullptr;
+    int rc;
+    if ((rc = optim_check_desc(desc))) return rc;
+    if (n <= 0) return fail(FARNN_EINVAL, "optim_create: no tensors%s%s");
+    for (int i = 0; i < n; i++)
+        if (numel[i] <= 0) return fail(FARNN_EINVAL, "optim_create: every numel must be positive%s%s");
+    // the chunk table: OPT_MAX_TENSORS tensors per launch, one workgroup per chunk
+    std::vector<OptChunk> table;
+    std::vector<farnn_optim::Launch> launches;
+    for (int t0 = 0; t0 < n; t0 += OPT_MAX_TENSORS) {
+        farnn_optim::Launch l = {t0, std::min<int>(OPT_MAX_TENSORS, n - t0), table.size(), 0u};
+        size_t nchunks = 0;
+        for (int t = 0; t < l.nt; t++) nchunks += (size_t)((numel[t0 + t] + OPT_CHUNK - 1) / OPT_CHUNK);
+        if (nchunks > (size_t)0x7fffffff) return fail(FARNN_ERANGE, "optim_create: more than 2^31 chunks in one launch%s%s");
+        for (int t = 0; t < l.nt; t++)
+            for (int64_t off = 0; off < numel[t0 + t]; off += OPT_CHUNK)
+                table.push_back({t, (int32_t)std::min<int64_t>(OPT_CHUNK, numel[t0 + t] - off), off});
+        l.nchunks = (unsigned)nchunks;
+        launches.push_back(l);
+    }
+    if ((rc = select_device(device))) return rc;
+    farnn_optim *o = new farnn_optim();
+    o->d = *desc; o->device = device;
+    o->numel.assign(numel, numel + n); o->steps.assign(n, 0);
+    o->launches = launches;
+    if ((rc = o->chunks.ensure(table.size(), "optim_create: out of device memory for the chunk table%s%s"))) { delete o; return rc; }
+    if (hipMemcpy(o->chunks.p, table.data(), table.size() * sizeof(OptChunk), hipMemcpyHostToDevice) != hipSuccess) {
+        delete o;
+        return fail(FARNN_EIO, "optim_create: copying the chunk table to the device failed%s%s");
+    }
+    *out = o;
+    return FARNN_OK;
+}
+
+extern "C" void farnn_optim_destroy(farnn_optim *o) {
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    (void)hipDeviceSynchronize();
+    delete o;
+}
+
+extern "C" int farnn_optim_set_lr(farnn_optim *o, double lr) {
+    if (!o) return fail(FARNN_EINVAL, "optim_set_lr: null handle%s%s");
+    if (!(lr >= 0.0) || lr > 3.0e38) return fail(FARNN_EINVAL, "optim_set_lr: lr must be a finite number >= 0%s%s");
+    o->d.lr = lr;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_optim_steps(const farnn_optim *o, int32_t i, int64_t *out) {
+    if (!o || !out) return fail(FARNN_EINVAL, "optim_steps: null argument%s%s");
+    if (i < 0 || (size_t)i >= o->steps.size()) return fail(FARNN_EINVAL, "optim_steps: tensor index out of range%s%s");
+    *out = o->steps[i];
+    return FARNN_OK;
+}
+
+extern "C" int farnn_optim_set_steps(farnn_optim *o, int32_t i, int64_t steps) {
+    if (!o) return fail(FARNN_EINVAL, "optim_set_steps: null handle%s%s");
+    if (i < 0 || (size_t)i >= o->steps.size()) return fail(FARNN_EINVAL, "optim_set_steps: tensor index out of range%s%s");
+    if (steps < 0) return fail(FARNN_EINVAL, "optim_set_steps: a step count cannot be negative%s%s");
+    o->steps[i] = steps;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_optim_step(farnn_optim *o, float *const *params, const float *const *grads, float *const *exp_avg,
+                                float *const *exp_avg_sq, void *stream) {
+    if (!o || !params || !grads) return fail(FARNN_EINVAL, "optim_step: null argument%s%s");
+    const bool adam = o->d.kind == FARNN_OPTIM_ADAM;
+    if (adam && (!exp_avg || !exp_avg_sq)) return fail(FARNN_EINVAL, "optim_step: Adam needs exp_avg and exp_avg_sq%s%s");
+    const int n = (int)o->numel.size();
+    // everything is checked before anything is enqueued or counted
+    for (int i = 0; i < n; i++) {
+        if (!grads[i]) continue;
+        if (!params[i]) return fail(FARNN_EINVAL, "optim_step: a tensor with a gradient has no parameter pointer%s%s");
+        if (adam && (!exp_avg[i] || !exp_avg_sq[i])) return fail(FARNN_EINVAL, "optim_step: a tensor with a gradient has no exp_avg / exp_avg_sq (Adam)%s%s");
+    }
+    FARNN_HIP_TRY(hipSetDevice(o->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    for (const farnn_optim::Launch &l : o->launches) {
+        OptArgs a = {};
+        bool any = false;
+        for (int t = 0; t < l.nt; t++) {
+            const int i = l.t0 + t;
+            if (!grads[i]) continue;          // a.g[t] stays null: the kernel leaves the tensor's chunks alone
+            any = true;
+            a.p[t] = params[i]; a.g[t] = grads[i];
+            if (adam) {
+                const double step = (double)++o->steps[i];
+                a.m[t] = exp_avg[i]; a.v[t] = exp_avg_sq[i];
+                a.step_size[t] = (float)(o->d.lr / (1.0 - pow(o->d.beta1, step)));
+                a.bc2_sqrt[t] = (float)sqrt(1.0 - pow(o->d.beta2, step));
+            } else {
+                ++o->steps[i];
+                a.step_size[t] = (float)o->d.lr;
+            }
+        }
+        if (!any) continue;
+        a.w1 = (float)(1.0 - o->d.beta1); a.beta2 = (float)o->d.beta2; a.w2 = (float)(1.0 - o->d.beta2); a.eps = (float)o->d.eps;
+        if (adam) optim_step_kernel<true><<<l.nchunks, OPT_THREADS, 0, s>>>(o->chunks.p + l.c0, a);
+        else optim_step_kernel<false><<<l.nchunks, OPT_THREADS, 0, s>>>(o->chunks.p + l.c0, a);
+    }
+    FARNN_HIP_TRY(hipGetLastError());
     return FARNN_OK;
 }

@@ -68,6 +68,7 @@ def check_trainable(model):
 def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
     """The epoch loop of the reference (train_decompose.py:161-221): forward_local(train=True), loss.backward(),
     optimizer.step() per batch, then the three evaluations and the best-model record."""
+    import os
     import time
 
     import torch
@@ -75,10 +76,13 @@ def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
 
     model.enable_training()                       # raises for the configurations the HIP training step does not cover
     params = list(model.parameters())
+    optim = torch.optim
+    if os.environ.get('RE2NN_NATIVE_OPTIM', '') == '1':      # opt-in: the library's one-launch optimizer step
+        from .farnn import optim
     if args.optimizer == 'SGD':
-        optimizer = torch.optim.SGD(params, lr=args.lr, weight_decay=0)
+        optimizer = optim.SGD(params, lr=args.lr, weight_decay=0)
     else:
-        optimizer = torch.optim.Adam(params, lr=args.lr, weight_decay=0)
+        optimizer = optim.Adam(params, lr=args.lr, weight_decay=0)
     print('ALL TRAINABLE PARAMETERS: {}'.format(sum(p.numel() for p in params)))
     for epoch in range(1, args.epoch + 1):
         model.train()

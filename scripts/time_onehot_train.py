@@ -4,7 +4,8 @@ bench.py's `ifst` workload does).  Prints one JSON line:
 
   lib_us_per_step     HIP-event time of the library step (farnn_onehot_train_time)
   step_us_per_step    the whole step as a training loop runs it: zero_grad, forward_local(train=True), backward, Adam
-                      (torch events around the loop)
+                      (torch events around the loop); `optimizer` says which Adam: torch's, or with RE2NN_NATIVE_OPTIM=1
+                      the library's one-launch step
   tokens_per_s        valid trained tokens per second of the whole step
   cpu_ms_per_step     the float32 torch restatement (tests/onehot_train_ref.py) forward + backward on 16 CPU threads:
                       the reference trains this model on the CPU (train_onehot.py:75-76)
@@ -55,7 +56,12 @@ def main():
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
     tc = _lib.OnehotTrainContext(V, S, C, nl='none', device=0)
-    opt = torch.optim.Adam([Tt], lr=1e-3, weight_decay=0)
+    native = os.environ.get('RE2NN_NATIVE_OPTIM', '') == '1'      # as train_onehot.train_epochs picks its optimizer
+    if native:
+        from re2nn_seq_amd.farnn import optim
+    else:
+        optim = torch.optim
+    opt = optim.Adam([Tt], lr=1e-3, weight_decay=0)
 
     def one(i):
         opt.zero_grad()
@@ -78,6 +84,7 @@ def main():
     step_ms = e0.elapsed_time(e1) / a.steps
     lib_ms, n = tc.time()
     out = dict(workload='onehot_train', V=V, S=S, C=C, B=B, L=L, valid_tokens=ntok, steps=a.steps,
+               optimizer='farnn.optim.Adam' if native else 'torch.optim.Adam',
                lib_us_per_step=round(1e3 * lib_ms / max(n, 1), 2), step_us_per_step=round(1e3 * step_ms, 2),
                tokens_per_s=round(ntok / (step_ms * 1e-3), 1), final_loss=float(loss.detach()))
     if a.cpu_steps > 0:
