@@ -410,7 +410,7 @@ int  farnn_train_set_semiring(farnn_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the onehot i-FST (FARNN_S_O_I_S, --method onehot --independent 2) -----------------
  * Replaces FARNN_S_O_I_S.forward_local(train=True) + loss.backward() (model_onehot.py:131-146,351-428,
- * train_onehot.py:156-206) for the sum semiring and the CE1 loss: cross-entropy (mean over the valid tokens) of
+ * train_onehot.py:156-206) for the sum or the max semiring (farnn_onehot_train_set_semiring) and the CE1 loss: cross-entropy (mean over the valid tokens) of
  * the scores output_mat (alpha * beta) [. P], and its gradient with respect to language_tensor, the only tensor the
  * reference trains (model_onehot.py:326-337).  M_w = T[w] + W; the state mask is output_mat.sum(0).
  * Limits: S <= 128 (farnn_onehot_train_create returns FARNN_ERANGE above), B L < 2^30 (the step returns FARNN_ERANGE
@@ -449,6 +449,15 @@ int  farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *ctx, const farnn_oneho
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *ctx, int32_t enable);
 int  farnn_onehot_train_time(farnn_onehot_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* The semiring of both chains (the reference's --train_mode: semiring_func = _maxmul, model_onehot.py:57, used at :377 and
+ * :394; utils.py:192-195): FARNN_SEMIRING_SUM (the default) or FARNN_SEMIRING_MAX, where a step is
+ * y[s] = max_j f[j] M_w[j,s] (forward chain) and q[s] = max_j (b o)[j] M_w[s,j] (backward chain), torch.max's first maximal j
+ * taking the whole adjoint.  Scores, loss, decode and every limit are the same in both; the step stays free of float
+ * atomics.  Returns FARNN_EINVAL for any other value.  The max step's extra workspace (an index byte and the winning matrix
+ * entry per step and state) is allocated by its first step; a context switched back to FARNN_SEMIRING_SUM computes exactly
+ * what one that never left it does.  The Python mirror keeps this semiring opt-in for its first release: FARNN_S_O_I_S
+ * trains with --train_mode max only when RE2NN_ONEHOT_MAX_TRAIN=1 is set. */
+int  farnn_onehot_train_set_semiring(farnn_onehot_train_ctx *ctx, int32_t semiring);
 
 /* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
  * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,

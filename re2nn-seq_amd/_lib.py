@@ -153,6 +153,7 @@ SIGNATURES = {
                                                C.POINTER(OnehotTrainOutputs), C.c_void_p]),
     'farnn_onehot_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_onehot_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_onehot_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -592,9 +593,17 @@ class OnehotTrainContext(_TrainContextBase):
     _set_profiling, _time = 'farnn_onehot_train_set_profiling', 'farnn_onehot_train_time'
     _weights, _outputs = OnehotTrainWeights, OnehotTrainOutputs
 
-    def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
+    def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0, semiring='sum'):
+        if semiring not in SEMIRING:             # before the native context exists: a bad name leaves no handle behind
+            raise ValueError('semiring must be one of {}, not {!r}'.format(sorted(SEMIRING), semiring))
         self._open(OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
         self.dims = (int(V), int(S), int(n_cols))
+        if semiring != 'sum':
+            self.set_semiring(semiring)
+
+    def set_semiring(self, semiring):
+        """'sum' or 'max' (the reference's --train_mode) for the following steps."""
+        check(load().farnn_onehot_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_onehot_train_set_semiring')
 
 
 class Optim:

@@ -12,6 +12,7 @@
 #include "host_util.hip.h"
 #include "train_host.hip.h"
 #include "train_max.hip.h"
+#include "onehot_train_max.hip.h"
 #include "optim.hip.h"
 
 using namespace farnn;
@@ -462,7 +463,9 @@ struct farnn_onehot_train_ctx {
     farnn_onehot_train_dims d;
     int device = 0;
     int n_cu = 256;
-    DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, MT, o, loss partials, dT partial tiles
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_onehot_train_set_semiring
+    DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, MT, o, loss partials, dT partial tiles; the max
+                                  // semiring's index and winning-entry stashes behind them (grown by the first max step)
     DevBuf<int> iws;              // per-batch int workspace: bucket counts / offsets, per-word tables, the sorted positions
     StepProfile prof;
     ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
@@ -498,24 +501,36 @@ extern "C" int farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *c, int32
     return FARNN_OK;
 }
 
+extern "C" int farnn_onehot_train_set_semiring(farnn_onehot_train_ctx *c, int32_t semiring) {
+    if (!c) return fail(FARNN_EINVAL, "onehot_train_set_semiring: null context%s%s");
+    if (semiring != FARNN_SEMIRING_SUM && semiring != FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "onehot_train_set_semiring: semiring must be FARNN_SEMIRING_SUM or FARNN_SEMIRING_MAX%s%s");
+    c->semiring = semiring;
+    return FARNN_OK;
+}
+
 extern "C" int farnn_onehot_train_time(farnn_onehot_train_ctx *c, double *total_ms, int64_t *steps) {
     if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "onehot_train_time: null argument%s%s");
     return c->prof.time(c->device, total_ms, steps);
 }
 // One step: the plan (onehot_plan: sizes from the dimensions alone) and what the stages hand on
 struct OhStep {
+    bool mx;                      // the max semiring (onehot_train_max.hip.h): its own chain, BPTT and dT stages
     int B, L;
     size_t S, K, V, N1, N0;
     unsigned lgrid;               // workgroups of the loss kernel
     size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_onehot_ws / carve_onehot_ints
-    size_t lds_tok;               // LDS bytes of the chain kernels
+    size_t lds_tok, lds_mdt;      // LDS bytes of the chain kernels and of the max semiring's dT kernel
     farnn_onehot_train_ctx *c; const farnn_onehot_train_weights *w; const farnn_onehot_train_outputs *o; hipStream_t s;
     OhTrainParams q;
+    OhMaxParams mq;
     float *DS, *AB, *M, *MT, *osum, *loss_part, *partial;
     Buckets bk;
     int carve(const int64_t *x, const int64_t *lengths);
     int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int dT();
     template <bool BPTT> int chains();
+    int max_chains(); int max_dT();
+    int max_bptt() { return launch(onehot_max_bptt_kernel, dim3(B, 2), OT_THREADS, 0, s, q, mq); }
 };
 
 static size_t carve_onehot_ws(float *base, OhStep &t) {
@@ -527,6 +542,13 @@ static size_t carve_onehot_ws(float *base, OhStep &t) {
     t.osum = a.take((t.S + 3) & ~(size_t)3);
     t.loss_part = a.take((size_t)t.lgrid * 8);
     t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // partial tiles of the words with several runs
+    if (t.mx) {
+        // the max semiring, behind everything the sum step lays out: the winning entries, and the indices as bytes.  The
+        // per-step dM entries take the rows the sum step's BPTT writes (UF, DQ), which the max step does not use.
+        t.mq.WINf = a.take(nS); t.mq.WINb = a.take(nS);
+        t.mq.IDXf = (uint8_t *)a.take((nS + 3) / 4); t.mq.IDXb = (uint8_t *)a.take((nS + 3) / 4);
+        t.mq.GMf = t.q.UF; t.mq.GMb = t.q.DQ;
+    }
     return a.off;
 }
 static size_t carve_onehot_ints(int *base, OhStep &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
@@ -535,14 +557,16 @@ static size_t carve_onehot_ints(int *base, OhStep &t) { Carver<int> a(base); car
 static int onehot_plan(const farnn_onehot_train_ctx *c, int B, int L, OhStep &t) {
     // positions are 32-bit flat indices b L + i in the bucketing and dT kernels
     if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "onehot_train_step: B (L+1) must stay below 2^30%s%s");
+    t.mx = c->semiring == FARNN_SEMIRING_MAX;
     t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
     t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
     // the loss kernel's persistent workgroups: three per compute unit (48 KiB of LDS each at ATIS size; one per unit left
     // the position loop latency-bound: 127 us)
     t.lgrid = (unsigned)std::min<size_t>(3 * (size_t)c->n_cu, (t.N0 + 7) / 8);
-    t.lds_tok = (size_t)(L + 1) * sizeof(int);
+    t.lds_tok = (size_t)(L + 1) * sizeof(int); t.lds_mdt = onehot_max_dT_lds_bytes(t.S);
     t.need = carve_onehot_ws(nullptr, t); t.ineed = carve_onehot_ints(nullptr, t);
-    return lds_fits(t.lds_tok);
+    if (int rc = lds_fits(t.lds_tok)) return rc;
+    return t.mx ? lds_fits(t.lds_mdt) : FARNN_OK;
 }
 // Stage 3: grow the buffers, lay the workspaces out, fill the chain kernels' parameters
 int OhStep::carve(const int64_t *x, const int64_t *lengths) {
@@ -573,6 +597,11 @@ int OhStep::chains() {
     auto go = [&](auto RS) { return launch(onehot_train_chain_kernel<RS(), BPTT>, dim3(B, 2), OT_THREADS, lds_tok, s, q); };
     return S <= 64 ? go(int_c<8>()) : S <= 72 ? go(int_c<18>()) : S <= 96 ? go(int_c<24>()) : go(int_c<32>());
 }
+// Stage 6, max semiring: both chains with the state, arg-max index and winning-entry stash (the sum kernel's register slots by S)
+int OhStep::max_chains() {
+    auto go = [&](auto RS) { return launch(onehot_max_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_tok, s, q, mq); };
+    return S <= 64 ? go(int_c<8>()) : S <= 72 ? go(int_c<18>()) : S <= 96 ? go(int_c<24>()) : go(int_c<32>());
+}
 // Stage 7: scores, cross-entropy, decode, d loss / d alpha, d loss / d beta: the decomposed step's kernel (PHASE 0) with
 // output_mat in C_output_mat's place, the loss as per-wavefront partials
 int OhStep::loss(const int64_t *labels, int64_t valid_tokens) {
@@ -598,6 +627,15 @@ int OhStep::dT() {
     return FARNN_OK;
 }
 
+// Stage 9, max semiring: the per-step dM entries added per word in bucket order, the sum step's runs and its reduction
+int OhStep::max_dT() {
+    const unsigned ngrid = (unsigned)(V + (N0 + OT_G - 1) / OT_G);
+    if (int rc = launch(onehot_max_dT_kernel, ngrid, 256, lds_mdt, s, q, mq, bk.list, bk.wstart, bk.wcount, bk.itoff, bk.psoff,
+                        o->dT, partial)) return rc;
+    onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((S * S + 255) / 256)), 256, 0, s>>>(bk.itoff, bk.psoff, partial, o->dT, (int)S);
+    return FARNN_OK;
+}
+
 extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const farnn_onehot_train_weights *w, const int64_t *x,
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_onehot_train_outputs *o, void *stream) {
@@ -615,8 +653,8 @@ extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const far
                                                  : "onehot_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
     if ((rc = t.carve(x, lengths))) return rc;
     StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = t.chains<false>()) || (rc = t.loss(labels, valid_tokens)) || (rc = t.chains<true>()) ||
-        (rc = t.dT())) return rc;
+    if ((rc = t.prepare()) || (rc = t.mx ? t.max_chains() : t.chains<false>()) || (rc = t.loss(labels, valid_tokens)) ||
+        (rc = t.mx ? t.max_bptt() : t.chains<true>()) || (rc = t.mx ? t.max_dT() : t.dT())) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     c->prof.end(t.s);
     return FARNN_OK;

@@ -8,6 +8,8 @@ HIP library through the C-ABI (include/farnn.h).
   FARNN_S_O_I    two 3-D tensors          (--independent 1)   ref :184-306
   FARNN_S_O_I_S  i-FST, T[V,S,S] + O[C,S] (--independent 2)   ref :310-428
 """
+import os
+
 import numpy as np
 import torch
 
@@ -114,9 +116,10 @@ class FARNN_S_O_I_S(_OnehotBase):
     def _check_trainable(self):
         """The cases the HIP training step does not cover, refused before any device work."""
         a = self.args
-        if a.train_mode != 'sum':
-            raise NotImplementedError('training the onehot i-FST covers the sum semiring only; --train_mode {} is not '
-                                      'built (DESIGN.md, row f5)'.format(a.train_mode))
+        if a.train_mode != 'sum' and not (a.train_mode == 'max' and self._max_train_enabled()):
+            raise NotImplementedError('training the onehot i-FST covers the sum semiring only by default; --train_mode max '
+                                      'is opt-in (set RE2NN_ONEHOT_MAX_TRAIN=1), --train_mode {} was asked for '
+                                      '(DESIGN.md, row f5)'.format(a.train_mode))
         if a.local_loss_func != 'CE1':
             raise NotImplementedError('training the onehot i-FST covers the CE1 loss only (main.py:127)')
         if self.use_crf:
@@ -126,6 +129,11 @@ class FARNN_S_O_I_S(_OnehotBase):
         if world()[1] > 1:
             raise NotImplementedError('multi-GPU data-parallel training of the onehot i-FST is not built; train on one '
                                       'GPU (DESIGN.md, row f5)')
+
+    @staticmethod
+    def _max_train_enabled():
+        """RE2NN_ONEHOT_MAX_TRAIN=1: the max-semiring training step (opt-in for its first release, as RE2NN_NATIVE_OPTIM)"""
+        return os.environ.get('RE2NN_ONEHOT_MAX_TRAIN', '') == '1'
 
     def enable_training(self):
         """Device-resident tensors (language_tensor the only one with requires_grad, as in the reference :326-337) and
@@ -145,7 +153,8 @@ class FARNN_S_O_I_S(_OnehotBase):
             if self.args.use_priority else None
         V, S, _ = self._tp['language_tensor'].shape
         self._tc = _lib.OnehotTrainContext(V, S, self.C, nl=self.args.update_nonlinear, threshold=self.args.threshold,
-                                           o_idx=self.o_idx, device=self.device_index)
+                                           o_idx=self.o_idx, device=self.device_index,
+                                           semiring='max' if self.args.train_mode == 'max' else 'sum')
         self._dirty = False
         return self
 

@@ -10,7 +10,10 @@ bench.py's `ifst` workload does).  Prints one JSON line:
   cpu_ms_per_step     the float32 torch restatement (tests/onehot_train_ref.py) forward + backward on 16 CPU threads:
                       the reference trains this model on the CPU (train_onehot.py:75-76)
 
-    python scripts/time_onehot_train.py [--steps 50] [--warmup 5] [--cpu-steps 3] [--states 71]
+    python scripts/time_onehot_train.py [--steps 50] [--warmup 5] [--cpu-steps 3] [--states 71] [--semiring max]
+
+--semiring max times the max-semiring step (farnn_onehot_train_set_semiring; the CPU figure is then tests/onehot_train_max_ref.py)
+and adds "semiring": "max" to the line; the default line is unchanged.
 
 Each GPU step of a job script runs it under its own time limit (timeout -k 10 ...)."""
 import argparse
@@ -32,6 +35,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--cpu-steps', type=int, default=3)
     ap.add_argument('--states', type=int, default=71)
+    ap.add_argument('--semiring', choices=('sum', 'max'), default='sum')
     a = ap.parse_args()
     import torch
     from re2nn_seq_amd import _lib, synth
@@ -56,6 +60,8 @@ def main():
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
     tc = _lib.OnehotTrainContext(V, S, C, nl='none', device=0)
+    if a.semiring != 'sum':
+        tc.set_semiring(a.semiring)
     native = os.environ.get('RE2NN_NATIVE_OPTIM', '') == '1'      # as train_onehot.train_epochs picks its optimizer
     if native:
         from re2nn_seq_amd.farnn import optim
@@ -87,8 +93,13 @@ def main():
                optimizer='farnn.optim.Adam' if native else 'torch.optim.Adam',
                lib_us_per_step=round(1e3 * lib_ms / max(n, 1), 2), step_us_per_step=round(1e3 * step_ms, 2),
                tokens_per_s=round(ntok / (step_ms * 1e-3), 1), final_loss=float(loss.detach()))
+    if a.semiring != 'sum':
+        out['semiring'] = a.semiring
     if a.cpu_steps > 0:
-        import onehot_train_ref as otr
+        if a.semiring == 'max':
+            import onehot_train_max_ref as otr
+        else:
+            import onehot_train_ref as otr
         torch.set_num_threads(16)
         otr.step(T, W, O, h0, hT, None, xs[0], lengths, labels[0], dtype=torch.float32)
         t0 = time.perf_counter()
