@@ -483,7 +483,7 @@ static int launch_score_decode(farnn_model *m, const int64_t *len, int B, int fu
         // K2l: the output matrix is a label map and only tags are asked for -- S multiply-adds and a scan per token, one workgroup
         // per sequence (score_decode.hip.h).  FARNN_NOLABELMAP=1 (no label map is built then) keeps the matrix form.
         KernelTimer kt(m, KERN_SCORE, s);
-        label_map_score_kernel<<<B, LMS_WAVES * 64, 0, s>>>(p);
+        label_map_score_kernel<LMS_WAVES><<<B, LMS_WAVES * 64, 0, s>>>(p);
         FARNN_HIP_TRY(hipGetLastError());
         m->last_lm_score = true;
         return FARNN_OK;
