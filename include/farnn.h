@@ -459,6 +459,52 @@ int  farnn_onehot_train_time(farnn_onehot_train_ctx *ctx, double *total_ms, int6
  * trains with --train_mode max only when RE2NN_ONEHOT_MAX_TRAIN=1 is set. */
 int  farnn_onehot_train_set_semiring(farnn_onehot_train_ctx *ctx, int32_t semiring);
 
+/* ---- training step of the onehot FST (FARNN_S_O, --method onehot --independent 0) ------------------------
+ * Replaces FARNN_S_O.forward_local(train=True) + loss.backward() (model_onehot.py:66-146, train_onehot.py:156-206) for
+ * the sum semiring and the CE1 loss.  A[w,c] = T4[w,c] + W4[c] (:87), M[w] = sum_c T4[w,c] + sum_c W4[c] (:82); both chains
+ * use relu, whatever update_nonlinear says (:94, :101), and have no output mask; score_i[c] = sum_{s,j} relu(A[x_i,c,s,j]
+ * alpha_i[s] beta_{i+1}[j]) [. P] with alpha_i the state BEFORE token i (:115-127); the loss is the cross-entropy, mean over
+ * the valid tokens (:60, :142); the tags are local_decode's (:172-176).  language_tensor is always trained (:34),
+ * wildcard_tensor with --train_wildcard (:35): its gradient is the sum of language_tensor's over the words, as both enter
+ * only through A and M.  wildcard_wildcard_mat is not read under CE1 (:81-82).
+ * Limits: S <= 128 (the chains' kernels, as farnn_onehot_train_create), C <= 2400 (the loss kernel of this step keeps two
+ * score vectors per wavefront, 8 x 2 x C floats, within 150 KiB of LDS), V C <= 2^47 so that every byte offset into
+ * [V][C][S][S] fits 63 bits (farnn_fst4_train_create returns FARNN_ERANGE outside), B (L + 1) < 2^30 (the step returns
+ * FARNN_ERANGE before enqueuing anything and leaves the outputs untouched).  All pointers are DEVICE pointers; tensors are
+ * row-major and unpadded. */
+typedef struct farnn_fst4_train_ctx farnn_fst4_train_ctx;
+
+typedef struct {
+    int32_t V, S, C;            /* vocabulary rows of T4, states, score columns (labels + 1)        */
+    float   threshold;          /* decode clamp of column C-1 (model_onehot.py:172-176)             */
+    int32_t o_idx;              /* label written for column C-1 (:176)                              */
+} farnn_fst4_train_dims;
+
+typedef struct {
+    const float *T4;            /* [V][C][S][S] language_tensor */
+    const float *W4;            /* [C][S][S]    wildcard_tensor */
+    const float *h0, *hT;       /* [S]                          */
+    const float *P;             /* [C][C] priority matrix or NULL (args.use_priority = 0) */
+} farnn_fst4_train_weights;
+
+typedef struct {
+    float *loss;                /* [1]                                                                    */
+    float *dT4;                 /* [V][C][S][S] (rows of words absent from the batch are written as zero) */
+    float *dW4;                 /* [C][S][S] or NULL (train_wildcard = 0)                                 */
+    int32_t *tags;              /* [B][L] decoded labels of this forward pass, -1 at pad positions        */
+} farnn_fst4_train_outputs;
+
+int  farnn_fst4_train_create(const farnn_fst4_train_dims *dims, int device, farnn_fst4_train_ctx **out);
+void farnn_fst4_train_destroy(farnn_fst4_train_ctx *ctx);
+/* One step on the given stream: writes all outputs (no float atomics: bit-identical across runs).  x, lengths, labels,
+ * valid_tokens and the handling of bad labels / words: as farnn_onehot_ifst_train_step. */
+int  farnn_fst4_train_step(farnn_fst4_train_ctx *ctx, const farnn_fst4_train_weights *w, const int64_t *x,
+                           const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                           int64_t valid_tokens, const farnn_fst4_train_outputs *out, void *stream);
+/* as farnn_train_set_profiling / farnn_train_time */
+int  farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *ctx, int32_t enable);
+int  farnn_fst4_train_time(farnn_fst4_train_ctx *ctx, double *total_ms, int64_t *steps);
+
 /* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
  * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,
  * no weight decay, no amsgrad:

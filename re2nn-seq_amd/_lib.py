@@ -131,6 +131,18 @@ class OnehotTrainOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT', 'tags')]
 
 
+class Fst4TrainDims(C.Structure):
+    _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('C', C.c_int32), ('threshold', C.c_float), ('o_idx', C.c_int32)]
+
+
+class Fst4TrainWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('T4', 'W4', 'h0', 'hT', 'P')]
+
+
+class Fst4TrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT4', 'dW4', 'tags')]
+
+
 class OptimDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
@@ -154,6 +166,13 @@ SIGNATURES = {
     'farnn_onehot_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_onehot_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_onehot_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_fst4_train_create': (C.c_int, [C.POINTER(Fst4TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_fst4_train_destroy': (None, [C.c_void_p]),
+    'farnn_fst4_train_step': (C.c_int, [C.c_void_p, C.POINTER(Fst4TrainWeights), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                        C.POINTER(Fst4TrainOutputs), C.c_void_p]),
+    'farnn_fst4_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_fst4_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -604,6 +623,17 @@ class OnehotTrainContext(_TrainContextBase):
     def set_semiring(self, semiring):
         """'sum' or 'max' (the reference's --train_mode) for the following steps."""
         check(load().farnn_onehot_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_onehot_train_set_semiring')
+
+
+class Fst4TrainContext(_TrainContextBase):
+    """Owns one farnn_fst4_train_ctx* (training step of the onehot FST, include/farnn.h)."""
+    _create, _destroy, _step = 'farnn_fst4_train_create', 'farnn_fst4_train_destroy', 'farnn_fst4_train_step'
+    _set_profiling, _time = 'farnn_fst4_train_set_profiling', 'farnn_fst4_train_time'
+    _weights, _outputs = Fst4TrainWeights, Fst4TrainOutputs
+
+    def __init__(self, V, S, n_cols, threshold=0.5, o_idx=0, device=0):
+        self._open(Fst4TrainDims(int(V), int(S), int(n_cols), float(threshold), int(o_idx)), device)
+        self.dims = (int(V), int(S), int(n_cols))
 
 
 class Optim:

@@ -1,5 +1,5 @@
-// libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h) and the onehot
-// i-FST (farnn_onehot_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
+// libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
+// i-FST (farnn_onehot_train_*) and the onehot FST (farnn_fst4_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
 // loss) compile once, beside the tagging path.  Each step is a sequence of named stages (the static functions below, in the
 // order they run); what both steps share on the host side is in train_host.hip.h.
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include "train_host.hip.h"
 #include "train_max.hip.h"
 #include "onehot_train_max.hip.h"
+#include "fst4_train.hip.h"
 #include "optim.hip.h"
 
 using namespace farnn;
@@ -593,10 +594,12 @@ int OhStep::prepare() {
 }
 // Stages 6 and 8: both chains (BPTT = false: with the state stash; true: back-propagation through time), rows per share by S
 template <bool BPTT>
-int OhStep::chains() {
-    auto go = [&](auto RS) { return launch(onehot_train_chain_kernel<RS(), BPTT>, dim3(B, 2), OT_THREADS, lds_tok, s, q); };
-    return S <= 64 ? go(int_c<8>()) : S <= 72 ? go(int_c<18>()) : S <= 96 ? go(int_c<24>()) : go(int_c<32>());
+static int launch_onehot_chains(const OhTrainParams &q, size_t lds_tok, hipStream_t s) {
+    auto go = [&](auto RS) { return launch(onehot_train_chain_kernel<RS(), BPTT>, dim3(q.B, 2), OT_THREADS, lds_tok, s, q); };
+    return q.S <= 64 ? go(int_c<8>()) : q.S <= 72 ? go(int_c<18>()) : q.S <= 96 ? go(int_c<24>()) : go(int_c<32>());
 }
+template <bool BPTT>
+int OhStep::chains() { return launch_onehot_chains<BPTT>(q, lds_tok, s); }
 // Stage 6, max semiring: both chains with the state, arg-max index and winning-entry stash (the sum kernel's register slots by S)
 int OhStep::max_chains() {
     auto go = [&](auto RS) { return launch(onehot_max_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_tok, s, q, mq); };
@@ -616,16 +619,18 @@ int OhStep::loss(const int64_t *labels, int64_t valid_tokens) {
     return FARNN_OK;
 }
 // Stage 9: d loss / d language_tensor, word by word from the sorted positions; tiles per workgroup by S
-int OhStep::dT() {
+static int launch_onehot_dT(const OhTrainParams &q, const Buckets &bk, float *dT, float *partial, hipStream_t s) {
+    const size_t V = q.V, S = q.S, N0 = (size_t)q.B * q.L;
     const unsigned ngrid = (unsigned)(V + (N0 + OT_G - 1) / OT_G);   // bound on the runs: sum_w max(1, ceil(n_w / G))
     auto go = [&](auto NT) {
         return launch(onehot_dT_kernel<NT()>, ngrid, 256, 4 * (size_t)OT_G * S * sizeof(float), s, q, bk.list, bk.wstart, bk.wcount,
-                      bk.itoff, bk.psoff, o->dT, partial);
+                      bk.itoff, bk.psoff, dT, partial);
     };
     if (int rc = S <= 32 ? go(int_c<2>()) : S <= 64 ? go(int_c<4>()) : S <= 96 ? go(int_c<6>()) : go(int_c<8>())) return rc;
-    onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((S * S + 255) / 256)), 256, 0, s>>>(bk.itoff, bk.psoff, partial, o->dT, (int)S);
+    onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((S * S + 255) / 256)), 256, 0, s>>>(bk.itoff, bk.psoff, partial, dT, (int)S);
     return FARNN_OK;
 }
+int OhStep::dT() { return launch_onehot_dT(q, bk, o->dT, partial, s); }
 
 // Stage 9, max semiring: the per-step dM entries added per word in bucket order, the sum step's runs and its reduction
 int OhStep::max_dT() {
@@ -655,6 +660,189 @@ extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const far
     StepProfile::Guard timing = c->prof.begin(t.s);
     if ((rc = t.prepare()) || (rc = t.mx ? t.max_chains() : t.chains<false>()) || (rc = t.loss(labels, valid_tokens)) ||
         (rc = t.mx ? t.max_bptt() : t.chains<true>()) || (rc = t.mx ? t.max_dT() : t.dT())) return rc;
+    FARNN_HIP_TRY(hipGetLastError());
+    c->prof.end(t.s);
+    return FARNN_OK;
+}
+
+// ---- training step of the onehot FST (FARNN_S_O; fst4_train.hip.h) ----------------------------------------
+struct farnn_fst4_train_ctx {
+    farnn_fst4_train_dims d;
+    int device = 0;
+    DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, M / MT / dM, the partials
+    DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
+    StepProfile prof;
+    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
+};
+
+extern "C" int farnn_fst4_train_create(const farnn_fst4_train_dims *d, int device, farnn_fst4_train_ctx **out) {
+    if (!d || !out) return fail(FARNN_EINVAL, "fst4_train_create: null argument%s%s");
+    *out = nullptr;
+    if (d->V <= 0 || d->S <= 0 || d->C <= 0) return fail(FARNN_EINVAL, "fst4_train_create: bad dimensions%s%s");
+    if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "fst4_train_create: more than 128 states%s%s");
+    // fst4_loss_kernel keeps two score vectors per wavefront in LDS (fst4_loss_lds_bytes): C <= 2400
+    if (fst4_loss_lds_bytes(d->C) > 150 * 1024) return fail(FARNN_ERANGE, "fst4_train_create: too many score columns%s%s");
+    // byte offsets into [V][C][S][S] stay inside 63 bits
+    if ((unsigned long long)d->V * (unsigned long long)d->C > (1ull << 47))
+        return fail(FARNN_ERANGE, "fst4_train_create: V C S S is not addressable%s%s");
+    int rc;
+    if ((rc = select_device(device))) return rc;
+    farnn_fst4_train_ctx *c = new farnn_fst4_train_ctx();
+    c->d = *d; c->device = device;
+    if (!c->err.create()) { farnn_fst4_train_destroy(c); return fail(FARNN_ENOMEM, "fst4_train_create: out of memory%s%s"); }
+    *out = c;
+    return FARNN_OK;
+}
+
+extern "C" void farnn_fst4_train_destroy(farnn_fst4_train_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    delete c;
+}
+
+extern "C" int farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *c, int32_t enable) {
+    if (!c) return fail(FARNN_EINVAL, "fst4_train_set_profiling: null context%s%s");
+    c->prof.enabled = enable;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_fst4_train_time(farnn_fst4_train_ctx *c, double *total_ms, int64_t *steps) {
+    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "fst4_train_time: null argument%s%s");
+    return c->prof.time(c->device, total_ms, steps);
+}
+
+// One step: the plan (fst4_plan: sizes from the dimensions alone) and what the stages hand on
+struct Fst4Step {
+    int B, L, ngrp, cpg;          // label groups per word of the score kernels, label columns per group
+    size_t S, K, V, N1, N0;
+    unsigned lgrid;               // workgroups of the loss kernel
+    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_fst4_ws / carve_fst4_ints
+    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
+    farnn_fst4_train_ctx *c; const farnn_fst4_train_weights *w; const farnn_fst4_train_outputs *o; hipStream_t s;
+    OhTrainParams q;
+    Fst4TrainParams f;
+    float *SC, *DS, *M, *MT, *dM, *Wsum, *ones, *loss_part, *partial, *part;
+    Buckets bk;
+    int carve(const int64_t *x, const int64_t *lengths);
+    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words(); int wildcard();
+    template <int MODE> int scores();
+};
+
+static size_t carve_fst4_ws(float *base, Fst4Step &t) {
+    Carver<float> a(base);
+    const size_t nS = t.N1 * t.S, SS = t.S * t.S;
+    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
+    t.SC = a.take(t.N0 * t.K); t.DS = a.take(t.N0 * t.K);
+    t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS);
+    t.Wsum = a.take((SS + 3) & ~(size_t)3);
+    t.ones = a.take((t.S + 3) & ~(size_t)3);
+    t.loss_part = a.take((size_t)t.lgrid * 8);
+    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dM: partial tiles of the words with several runs
+    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and label group
+    return a.off;
+}
+static size_t carve_fst4_ints(int *base, Fst4Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
+
+// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
+static int fst4_plan(const farnn_fst4_train_ctx *c, int B, int L, Fst4Step &t) {
+    // positions are 32-bit flat indices b L + i in the bucketing, dM and score kernels
+    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "fst4_train_step: B (L+1) must stay below 2^30%s%s");
+    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
+    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
+    // a word's label columns are split over enough workgroups to fill the chip when the batch has few distinct words
+    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.K, (size_t)F4_MAX_GROUPS});
+    t.cpg = (int)((t.K + want - 1) / want); t.ngrp = (int)((t.K + t.cpg - 1) / t.cpg);
+    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
+    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
+    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
+    t.lds_tok = (size_t)(L + 1) * sizeof(int);
+    t.lds_sc = fst4_train_lds_floats(SP, CPR, GW) * sizeof(float);
+    t.lds_loss = fst4_loss_lds_bytes(t.K);
+    t.need = carve_fst4_ws(nullptr, t); t.ineed = carve_fst4_ints(nullptr, t);
+    int rc;
+    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
+    return lds_fits(t.lds_loss);
+}
+// Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
+int Fst4Step::carve(const int64_t *x, const int64_t *lengths) {
+    int rc;
+    if ((rc = c->ws.ensure(need, "fst4_train_step: out of device memory for the workspace%s%s")) ||
+        (rc = c->iws.ensure(ineed, "fst4_train_step: out of device memory for the index workspace%s%s"))) return rc;
+    [[maybe_unused]] const size_t carved = carve_fst4_ws(c->ws.p, *this), icarved = carve_fst4_ints(c->iws.p, *this);
+    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
+    // the chains always use relu and have no output mask (model_onehot.py:93-94, :100-101): a mask of ones
+    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
+    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = FARNN_NL_RELU;
+    f.T4 = w->T4; f.W4 = w->W4; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
+    f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
+    f.SC = SC; f.DS = DS; f.part = part; f.dM = dM; f.dT4 = o->dT4;
+    f.L = L; f.S = (int)S; f.C = (int)K; f.cpg = cpg; f.ngrp = ngrp;
+    return FARNN_OK;
+}
+// Stages 4 and 5: the positions bucketed by word; W4.sum(0); M[w] = T4[w].sum(0) + W4.sum(0) and its transpose for the words of
+// the batch only (the bucket counts say which: the blocks of the other words are never read)
+int Fst4Step::prepare() {
+    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
+    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    const unsigned nt = (unsigned)((S + 31) / 32);
+    fst4_premix_kernel<<<dim3(1, nt * nt), 256, 0, s>>>(w->W4, nullptr, nullptr, Wsum, nullptr, (int)S, (int)K);
+    fst4_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(w->T4, Wsum, bk.wcount, M, MT, (int)S, (int)K);
+    return FARNN_OK;
+}
+// Stages 7, 9 and 12: the score kernels in bucket order (MODE 0: the scores, 1: the partials of d alpha / d beta, 2: dT4);
+// register rows per thread by S
+template <int MODE>
+int Fst4Step::scores() {
+    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
+    auto go = [&](auto RPT) { return launch(fst4_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), F4_THREADS, lds_sc, s, f); };
+    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
+                                                                                                             : go(int_c<16>());
+}
+// Stage 8: priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront partials
+int Fst4Step::loss(const int64_t *labels, int64_t valid_tokens) {
+    if (int rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
+                        (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens)) return rc;
+    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    return FARNN_OK;
+}
+// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the label groups' partials added in group order
+int Fst4Step::adjoints() {
+    if (int rc = scores<1>()) return rc;
+    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
+    return FARNN_OK;
+}
+// Stage 11: dM[w] of the chains, the i-FST step's per-word reduction
+int Fst4Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
+// Stage 13 (asked for): d loss / d wildcard_tensor
+int Fst4Step::wildcard() {
+    if (!o->dW4) return FARNN_OK;
+    const size_t CSS = K * S * S;
+    fst4_dW_kernel<<<(unsigned)((CSS + 255) / 256), 256, 0, s>>>(o->dT4, bk.wcount, o->dW4, (int)V, CSS);
+    return FARNN_OK;
+}
+
+extern "C" int farnn_fst4_train_step(farnn_fst4_train_ctx *c, const farnn_fst4_train_weights *w, const int64_t *x,
+                                     const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                     int64_t valid_tokens, const farnn_fst4_train_outputs *o, void *stream) {
+    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "fst4_train_step: null argument%s%s");
+    if (!w->T4 || !w->W4 || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "fst4_train_step: null weight%s%s");
+    if (!o->loss || !o->dT4 || !o->tags) return fail(FARNN_EINVAL, "fst4_train_step: null output%s%s");
+    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "fst4_train_step: B, L and valid_tokens must be positive%s%s");
+    Fst4Step t = {};
+    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
+    int rc, bad = 0;
+    if ((rc = fst4_plan(c, B, L, t))) return rc;
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->err.take(t.s, &bad))) return rc;
+    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "fst4_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
+                                                 : "fst4_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
+    if ((rc = t.carve(x, lengths))) return rc;
+    StepProfile::Guard timing = c->prof.begin(t.s);
+    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
+        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
+        (rc = t.dM_words()) || (rc = t.scores<2>()) || (rc = t.wildcard())) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     c->prof.end(t.s);
     return FARNN_OK;

@@ -1,5 +1,5 @@
-"""The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step and
-farnn_onehot_ifst_train_step (include/farnn.h).
+"""The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step,
+farnn_onehot_ifst_train_step and farnn_fst4_train_step (include/farnn.h).
 
 What the reference does in FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
 (model_decompose_single.py:207-304, train_decompose.py:186-190) is split like this: the word table
@@ -15,6 +15,9 @@ negative log-likelihood.
 
 The onehot i-FST (FARNN_S_O_I_S, model_onehot.py:351-428 + train_onehot.py:156-206) trains only
 language_tensor: one library call computes the loss, the tags and d loss / d language_tensor.
+
+The onehot FST (FARNN_S_O, model_onehot.py:66-146) trains language_tensor [V,C,S,S] and, with
+--train_wildcard, wildcard_tensor [C,S,S]: again one library call.
 """
 import torch
 
@@ -125,3 +128,35 @@ def onehot_ifst_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tok
     but receive no gradient (the reference's requires_grad=False, model_onehot.py:326-337).  valid_tokens: the sum of
     the clamped lengths if the caller already has it."""
     return _OnehotIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
+
+
+class _OnehotFst4TrainStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tc, ntok, x, lengths, labels, P, h0, hT, T4, W4):
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T4, ntok, x, lengths, labels)
+        B, L = x.shape
+        ws = {n: _f32(t) for n, t in (('T4', T4), ('W4', W4), ('h0', h0), ('hT', hT))}
+        Pc = _f32(P)
+        dT4 = torch.empty_like(ws['T4'])
+        dW4 = torch.empty_like(ws['W4']) if W4.requires_grad else None
+        weights = {n: t.data_ptr() for n, t in ws.items()}
+        weights['P'] = None if Pc is None else Pc.data_ptr()
+        outputs = {'loss': loss.data_ptr(), 'dT4': dT4.data_ptr(), 'dW4': None if dW4 is None else dW4.data_ptr(),
+                   'tags': tags.data_ptr()}
+        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
+                torch.cuda.current_stream(dev).cuda_stream)
+        ctx.has_w = dW4 is not None
+        ctx.save_for_backward(*([dT4] + ([dW4] if dW4 is not None else [])))
+        ctx.mark_non_differentiable(tags)
+        return loss.reshape(()), tags
+
+    @staticmethod
+    def backward(ctx, gloss, _gtags):
+        saved = ctx.saved_tensors
+        return (None,) * 8 + (saved[0] * gloss, saved[1] * gloss if ctx.has_w else None)
+
+
+def onehot_fst4_train_step(tc, T4, W4, h0, hT, P, x, lengths, labels, valid_tokens=None):
+    """Returns (loss scalar tensor with grad towards T4 and, if it requires grad, W4; tags int32 [B,L] with -1 at pads).
+    h0, hT and P are read but receive no gradient (model_onehot.py:32-33)."""
+    return _OnehotFst4TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, h0, hT, T4, W4)
