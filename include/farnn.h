@@ -38,6 +38,9 @@
  *   FARNN_NOREGS=1          the LDS-ring recurrence kernel where the register-fed one (S <= 128) would run
  *   FARNN_NODEST=1          [A/B build only] S <= 72, sum semiring: round 3's compute wavefronts (a block split by SOURCE rows,
  *                           partial sums reduced across the wavefronts) instead of the destination-split ones (chain_dest.hip.h)
+ *   FARNN_NOHALF=1          onehot i-FST, S <= 72, sum semiring: the recurrence reads the f32 blocks even where every block entry is an
+ *                           IEEE f16 exactly (a 0/1 or small-integer automaton: the default there reads a 16-bit image of the blocks,
+ *                           the same f32 arithmetic in the same order, bit-identical results); no image is built at create
  *   FARNN_NOLABELMAP=1      scores on the matrix cores even when the output matrix is a label map (one state, one label, weight 1)
  *   FARNN_CV_ONE=1          [A/B build only] a CRF on the onehot i-FST, S <= 108: recurrence + scores + Viterbi in ONE launch
  *                           (chain_viterbi_kernel).  Two launches are faster at every measured shape

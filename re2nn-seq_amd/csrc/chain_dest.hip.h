@@ -36,9 +36,12 @@
 namespace farnn {
 
 // What a compute wavefront carries from its priming (before the workgroup's set-up barrier) into the step loop
-template <int D, int LPR>
+// H16: the ring holds the block's 16-bit image (layout.hip.h, half_image_kernel): TWO 16-byte chunks per lane and step, each the
+// f16 values of two of the lane's four f32 chunks -- half the load instructions and half the bytes of a step
+template <int D, int LPR, bool H16 = false>
 struct DestRing {
-    static constexpr int NC = 20 / LPR;
+    static_assert(!H16 || LPR == 5, "the 16-bit image is laid out for five lanes per row");
+    static constexpr int NC = H16 ? 2 : 20 / LPR;
     v4f r[D][NC];                // the register ring: D steps x NC chunks
     unsigned voff[NC];           // this lane's chunk offsets inside a block
     int tkw_lo, tkw_hi;          // byte offsets of 64 steps' blocks (lane l: step window + l)
@@ -67,6 +70,12 @@ __device__ __forceinline__ void dest_lane(const int lane, int &rj, int &rs, bool
                          "global_load_dwordx4 %4, %9, %10" FARNN_RD_CPOL                                     \
                          : "=&v"(ring_.r[d][0]), "=&v"(ring_.r[d][1]), "=&v"(ring_.r[d][2]), "=&v"(ring_.r[d][3]), "=&v"(ring_.r[d][NC - 1]) \
                          : "v"(ring_.voff[0]), "v"(ring_.voff[1]), "v"(ring_.voff[2]), "v"(ring_.voff[3]), "v"(ring_.voff[NC - 1]), "s"(bp_)); \
+        else if constexpr (NC == 2)                                                            \
+            asm volatile("s_nop 4\n\t"                                                         \
+                         "global_load_dwordx4 %0, %2, %4" FARNN_RD_CPOL "\n\t"                                  \
+                         "global_load_dwordx4 %1, %3, %4" FARNN_RD_CPOL                                      \
+                         : "=&v"(ring_.r[d][0]), "=&v"(ring_.r[d][NC - 1])                      \
+                         : "v"(ring_.voff[0]), "v"(ring_.voff[NC - 1]), "s"(bp_));              \
         else                                                                                   \
             asm volatile("s_nop 4\n\t"                                                         \
                          "global_load_dwordx4 %0, %4, %8" FARNN_RD_CPOL "\n\t"                                  \
@@ -81,10 +90,10 @@ __device__ __forceinline__ void dest_lane(const int lane, int &rj, int &rs, bool
 // offsets of the first 64 steps straight from the token ids in global memory (the set-up writes them to LDS for the later windows
 // and for nobody's first loads), and the first D steps' pieces requested -- an L2 / Infinity-Cache round trip at the launch's start,
 // when all 512 workgroups ask at once, that used to begin only behind the barrier.
-template <int D, int LPR>
+template <int D, int LPR, bool H16>
 __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int dir, const int w, const int lane, const int nsteps,
-                                                const int len, const int b, DestRing<D, LPR> &ring) {
-    constexpr int NC = DestRing<D, LPR>::NC;
+                                                const int len, const int b, DestRing<D, LPR, H16> &ring) {
+    constexpr int NC = DestRing<D, LPR, H16>::NC;
     const int S = p.S, SP = p.SP, CPR = p.CPR;
     const int RW = (S + RG_NWC - 1) / RG_NWC;
     int rj, rs;
@@ -97,15 +106,20 @@ __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int d
         const int ci = rs + LPR * i;
         // a chunk beyond the row (or a lane without a row) loads the lane's first chunk again -- the same line, no traffic;
         // its state chunk is zeros
-        ring.voff[i] = ((unsigned)(my_valid ? my_row : 0) * (unsigned)SP + (unsigned)((my_valid && ci < CPR) ? ci : rs < CPR ? rs : 0) * 4u) * 4u;
+        if constexpr (H16)       // chunks rs and rs + 5 of the image's 160-byte row (zeros behind the row's columns: every chunk exists)
+            ring.voff[i] = (unsigned)(my_valid ? my_row : 0) * (unsigned)(RD_XS * 2) + (unsigned)ci * 16u;
+        else
+            ring.voff[i] = ((unsigned)(my_valid ? my_row : 0) * (unsigned)SP + (unsigned)((my_valid && ci < CPR) ? ci : rs < CPR ? rs : 0) * 4u) * 4u;
     }
+    (void)SP; (void)CPR;
     {
         const int t = lane < nsteps ? lane : nsteps - 1;
         const int idx = (dir == 0) ? t : (t < len ? len - 1 - t : t);
-        const long long o_ = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * p.blk * 4;
+        const long long o_ = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
         ring.tkw_lo = (int)(unsigned)o_; ring.tkw_hi = (int)(unsigned)(o_ >> 32);
     }
-    const char *Mbase = reinterpret_cast<const char *>(dir == 0 ? p.Mb : p.Mf);      // rows = outputs
+    const char *Mbase = H16 ? reinterpret_cast<const char *>(dir == 0 ? p.Mb16 : p.Mf16)
+                            : reinterpret_cast<const char *>(dir == 0 ? p.Mb : p.Mf);      // rows = outputs
 #pragma unroll
     for (int d = 0; d < D; d++) {
 #pragma unroll
@@ -117,10 +131,25 @@ __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int d
     }
 }
 
-template <bool NLX, int D, int LPR>
+// one multiply-add of the 16-bit form: acc += (float)half(blk, HI) * st -- v_fma_mix_f32, a fused f32 multiply-add that reads its
+// first operand as the low / high half of a register and widens it exactly; the same product into the same accumulator as the
+// f32 form's v_pk_fma_f32 lane
+// (FIRST: the accumulator starts at +0 -- the inline constant as the addend, no register to clear)
+template <bool HI, bool FIRST>
+__device__ __forceinline__ void fma_h16(float &acc, const float blk, const float st) {
+    if constexpr (FIRST) {
+        if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(acc) : "v"(blk), "v"(st));
+        else              asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(acc) : "v"(blk), "v"(st));
+    } else {
+        if constexpr (HI) asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(blk), "v"(st));
+        else              asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[1,0,0]" : "+v"(acc) : "v"(blk), "v"(st));
+    }
+}
+
+template <bool NLX, int D, int LPR, bool H16>
 __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int dir, const int w, const int lane_in, const int nsteps,
                                                   const long long *tokoff, float *flags, const float *ol, float *hist, float *xd,
-                                                  const bool probe, const int b, DestRing<D, LPR> &ring) {
+                                                  const bool probe, const int b, DestRing<D, LPR, H16> &ring) {
     static_assert(D == 2 || D == 4, "an even ring depth that divides 64 (the exchange row's parity and the address window)");
     static_assert(LPR == 4 || LPR == 5, "four or five lanes per output row");
     // LPR lanes per output row, NC chunks of the row per lane and step (LPR x NC = 20 chunks = RD_XS floats >= the padded row):
@@ -129,8 +158,11 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
     //   LPR = 5: three rows per DPP row of sixteen lanes (lane = 16 a + 5 b + q, lane 15 of each DPP row idle), the five lanes joined
     //            by three DPP adds (row_shr 1, 2 and 4), four chunks -- 60 of 64 lanes carry 4 loads each (88 %): what the texture
     //            addresser handles per step is what bounds two workgroups on a compute unit, and this form asks for a fifth less.
-    constexpr int NC = 20 / LPR;                         // 16-byte chunks per lane and step
-    static_assert(LPR * NC * 4 == RD_XS, "the exchange row holds every lane's chunks");
+    //   H16 (LPR = 5): the block's 16-bit image -- TWO loads per lane and step (image chunks q and q + 5, each the f16 values of two
+    //            of the lane's four f32 chunks: q, q + 5 | q + 10, q + 15), the same four state chunks, sixteen v_fma_mix_f32.
+    constexpr int NC = DestRing<D, LPR, H16>::NC;        // 16-byte chunks of the block per lane and step
+    constexpr int NS = 20 / LPR;                         // 16-byte chunks of the state per lane and step
+    static_assert(LPR * NS * 4 == RD_XS, "the exchange row holds every lane's chunks");
     int lane = lane_in;
     const int S = p.S, SP = p.SP, CPR = p.CPR;
     const int RW = (S + RG_NWC - 1) / RG_NWC;            // outputs per wavefront (<= 12)
@@ -142,7 +174,8 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
     const bool my_writer = my_valid && rs == (LPR == 4 ? 0 : 4);      // the lane the row's sum ends up in
     const bool is_flane = lane == 63;                    // (never a row's lane: RW <= 12 rows take lanes 0 .. 47 / the lanes != 15 mod 16)
     (void)CPR;
-    const char *Mbase = reinterpret_cast<const char *>(dir == 0 ? p.Mb : p.Mf);      // rows = outputs
+    const char *Mbase = H16 ? reinterpret_cast<const char *>(dir == 0 ? p.Mb16 : p.Mf16)
+                            : reinterpret_cast<const char *>(dir == 0 ? p.Mb : p.Mf);      // rows = outputs
     const float my_o = my_valid ? ol[my_row] : 1.0f;
     const float c_pre = dir == 0 ? my_o : 1.0f, c_post = dir == 0 ? 1.0f : my_o;     // (:377-386) / (:393-402)
     float *xbuf = xd;                                    // [2][RD_XS]
@@ -188,6 +221,9 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
         if constexpr (NC == 5)                                                                 \
             asm volatile(FARNN_RD_WAITSTR : "+v"(r[d][0]), "+v"(r[d][1]), "+v"(r[d][2]), "+v"(r[d][3]), "+v"(r[d][NC - 1]) \
                          : [rem] "s"(rem_), [dm1] "n"(D - 1), [cnt] "n"((D - 1) * NC) : "scc"); \
+        else if constexpr (NC == 2)                                                            \
+            asm volatile(FARNN_RD_WAITSTR : "+v"(r[d][0]), "+v"(r[d][NC - 1])                  \
+                         : [rem] "s"(rem_), [dm1] "n"(D - 1), [cnt] "n"((D - 1) * NC) : "scc"); \
         else                                                                                   \
             asm volatile(FARNN_RD_WAITSTR : "+v"(r[d][0]), "+v"(r[d][1]), "+v"(r[d][2]), "+v"(r[d][3]) \
                          : [rem] "s"(rem_), [dm1] "n"(D - 1), [cnt] "n"((D - 1) * NC) : "scc"); \
@@ -211,11 +247,11 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
             constexpr int dummy = 0; (void)dummy;
             const int roff = (d & 1) * RD_XS;                // the exchange buffer this step reads (t and d have the same parity)
             // the partners' flags FIRST, this lane's five state chunks behind them in the same batch
-            v4f st[NC];
+            v4f st[NS];
             {
                 int fl = lds_flag_get(pflag);
 #pragma unroll
-                for (int i = 0; i < NC; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
+                for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
                 asm volatile("" ::: "memory");
                 if (__ballot(fl < t + 1) != 0ull) {
                     // a partner is late: poll the flags alone (one 4-byte read per round -- re-reading the chunks with every poll
@@ -223,7 +259,7 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
                     // compute unit), then the chunks once more
                     do { fl = lds_flag_get(pflag); } while (__ballot(fl < t + 1) != 0ull);
 #pragma unroll
-                    for (int i = 0; i < NC; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
+                    for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
                     asm volatile("" ::: "memory");
                 }
             }
@@ -235,13 +271,32 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
             // shuffled the operands of every chunk into that pairing: 28 v_mov_b32 per step beside 8 v_pk_fma, seen in the ISA.
             // The compute wavefronts of a compute unit share four SIMDs: the step is their VALU instruction count.)  Same
             // products into the same accumulators in the same order: bit-identical.
-            v2f a01 = v2f{0.f, 0.f}, a23 = v2f{0.f, 0.f};
+            float sa, sb;
+            if constexpr (H16) {
+                // f32 chunk i of the lane lies in image chunk i >> 1, registers 2 (i & 1) and 2 (i & 1) + 1: (x, y) and (z, w) as halves
+                float a0, a1, a2, a3;
+                fma_h16<false, true>(a0, r[d][0].x, st[0].x);
+                fma_h16<true, true>(a1, r[d][0].x, st[0].y);
+                fma_h16<false, true>(a2, r[d][0].y, st[0].z);
+                fma_h16<true, true>(a3, r[d][0].y, st[0].w);
 #pragma unroll
-            for (int i = 0; i < NC; i++) {
-                a01 = __builtin_elementwise_fma(st[i].xy, r[d][i].xy, a01);
-                a23 = __builtin_elementwise_fma(st[i].zw, r[d][i].zw, a23);
+                for (int i = 1; i < NS; i++) {
+                    const float bxy = (i & 1) ? r[d][i >> 1].z : r[d][i >> 1].x, bzw = (i & 1) ? r[d][i >> 1].w : r[d][i >> 1].y;
+                    fma_h16<false, false>(a0, bxy, st[i].x);
+                    fma_h16<true, false>(a1, bxy, st[i].y);
+                    fma_h16<false, false>(a2, bzw, st[i].z);
+                    fma_h16<true, false>(a3, bzw, st[i].w);
+                }
+                sa = a0 + a1; sb = a2 + a3;
+            } else {
+                v2f a01 = v2f{0.f, 0.f}, a23 = v2f{0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < NS; i++) {
+                    a01 = __builtin_elementwise_fma(st[i].xy, r[d][i].xy, a01);
+                    a23 = __builtin_elementwise_fma(st[i].zw, r[d][i].zw, a23);
+                }
+                sa = a01.x + a01.y; sb = a23.x + a23.y;
             }
-            float sa = a01.x + a01.y, sb = a23.x + a23.y;
             asm volatile("" : "+v"(sa), "+v"(sb));            // (two scalar adds: packed into one v_pk_add they cost three v_mov)
             float s = sa + sb;
             if constexpr (LPR == 4) s = quad_sum(s);

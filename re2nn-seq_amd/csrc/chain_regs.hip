@@ -1,7 +1,8 @@
 // libfarnn_hip.so -- K1r, the register-fed recurrence with the score + decode stage beside it (chain_regs.hip.h), and its launcher.
 // build-flags: -fno-slp-vectorize
-// build-check: ring-registers ELb1EEEvNS_10RegsParamsE
-// (the destination-split kernels -- last template argument true -- keep a ring of in-flight global loads in ordinary asm outputs
+// build-check: ring-registers Lb1ELb0EEEvNS_10RegsParamsE
+// build-check: ring-registers Lb1ELb1EEEvNS_10RegsParamsE
+// (the destination-split kernels -- template arguments <.., DEST = true, H16 = false | true> -- keep a ring of in-flight global loads in ordinary asm outputs
 //  (chain_dest.hip.h): csrc/build.py fails the build if the compiler ever copies or spills one of them while its load is in flight)
 // (the step's sixteen FMAs and its add tree stay scalar: hipcc's SLP pass packs them into v_pk_fma_f32 / v_pk_add_f32, which
 //  one wavefront alone issues far slower than the scalar pairs -- MI355X_MICROARCH.md, packed f32 VALU: "an anti-lever")
@@ -19,17 +20,24 @@ int launch_chain_regs(const RegsParams &p, bool maxsr, bool score, hipStream_t s
     const bool dest = p.dest && !maxsr;                                   // the destination-split compute wavefronts (chain_dest.hip.h)
     const size_t lds = (size_t)regs_lds(p.L, p.SP, NP, p.sp.c16, p.sp.Kc, score, RG_RQ, score && bs_label_map_path(p.sp), dest).total * sizeof(float);
     const dim3 grid(2 * p.B), block(RG_WAVES * 64);
+    const bool half = dest && !score && p.half && p.Mf16 && p.Mb16;      // (farnn_hip.hip, launch_chain, decides; here: what the kernel needs)
     int rc;
     // NLX: tanh / relu-tanh / sigmoid between the steps (the kernel's none / relu form has no branch in the step)
     const bool nlx = p.nl != FARNN_NL_NONE && p.nl != FARNN_NL_RELU;
     const bool lmo = score && bs_label_map_path(p.sp);                     // the label-map instantiation (no matrix-core tile code)
+#define FARNN_LAUNCH_REGS6(MX, SC, NX, LM, DS, HF)                                             \
+    do {                                                                                       \
+        if ((rc = raise_lds_limit(chain_regs_kernel<MX, SC, NX, LM, DS, HF>, lds))) return rc; \
+        if (e0 && e1)                                                                          \
+            hipExtLaunchKernelGGL((chain_regs_kernel<MX, SC, NX, LM, DS, HF>), grid, block, (uint32_t)lds, s, e0, e1, 0, p); \
+        else                                                                                   \
+            chain_regs_kernel<MX, SC, NX, LM, DS, HF><<<grid, block, lds, s>>>(p);            \
+    } while (0)
+    // (the 16-bit image: the destination split's recurrence-only launch -- two more kernels, NLX false / true)
 #define FARNN_LAUNCH_REGS5(MX, SC, NX, LM, DS)                                                 \
     do {                                                                                       \
-        if ((rc = raise_lds_limit(chain_regs_kernel<MX, SC, NX, LM, DS>, lds))) return rc;     \
-        if (e0 && e1)                                                                          \
-            hipExtLaunchKernelGGL((chain_regs_kernel<MX, SC, NX, LM, DS>), grid, block, (uint32_t)lds, s, e0, e1, 0, p); \
-        else                                                                                   \
-            chain_regs_kernel<MX, SC, NX, LM, DS><<<grid, block, lds, s>>>(p);                \
+        if (DS && !SC && half) FARNN_LAUNCH_REGS6(MX, SC, NX, LM, DS, (DS && !SC));            \
+        else FARNN_LAUNCH_REGS6(MX, SC, NX, LM, DS, false);                                    \
     } while (0)
     // (the sum semiring's source-split compute wavefronts -- round 3's, FARNN_NODEST=1 -- live in the A/B build: six kernels the
     //  production library's dispatch cannot reach; the max semiring keeps the source split, its only form)
@@ -52,6 +60,7 @@ int launch_chain_regs(const RegsParams &p, bool maxsr, bool score, hipStream_t s
 #undef FARNN_LAUNCH_REGS3
 #undef FARNN_LAUNCH_REGS4
 #undef FARNN_LAUNCH_REGS5
+#undef FARNN_LAUNCH_REGS6
     FARNN_HIP_TRY(hipGetLastError());
     return FARNN_OK;
 }

@@ -121,10 +121,12 @@ __device__ long long g_wg_stamps[16 * WG_STAMP_MAX];    // FARNN_DBG & 2048 (cha
 // unit); RQ > RG_RQ the wide form (chain_wide.hip.h: 72 < S <= 128, one workgroup per compute unit, launch order longest first).
 // LMO: label-map path only (the paired wide form): the matrix-core tile code is compiled out.
 // DEST: the compute wavefronts split the block by destination (chain_dest.hip.h; narrow form, sum semiring).
-template <bool MAXSR, bool SCORE, bool NLX, int RQ = RG_RQ, int D = RG_D, bool LMO = false, bool DEST = false>
+// H16: ... and read the blocks' 16-bit image (recurrence-only launch of a model whose every block entry is an f16 exactly).
+template <bool MAXSR, bool SCORE, bool NLX, int RQ = RG_RQ, int D = RG_D, bool LMO = false, bool DEST = false, bool H16 = false>
 __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem, const int tid, const int item, int *b_out) {
     constexpr bool WIDE = RQ != RG_RQ;
     static_assert(!DEST || (!WIDE && !MAXSR), "the destination-split form exists for the narrow kernel and the sum semiring");
+    static_assert(!H16 || (DEST && !SCORE), "the 16-bit image is read by the destination split's recurrence-only launch");
     constexpr int PSTR = WIDE ? rgw_part_stride(RQ) : RG_PART_STRIDE;     // floats between the two partial-sum buffers
     constexpr int NG = WIDE ? RGW_NG : RG_NG;                         // state groups of 16 the scoring stage reaches
     const int lane = tid & 63;
@@ -161,13 +163,13 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
     // (destination split: the compute wavefronts request their first blocks BEFORE the set-up -- chain_dest.hip.h, regs_dest_prime)
     // (not in the instantiation that carries the matrix-core tile code: with the ring live across the set-up it spilled 20 VGPRs)
     constexpr bool PRIME_EARLY = DEST && (!SCORE || LMO);
-    DestRing<RD_D, RD_LPR> dring;
+    DestRing<RD_D, RD_LPR, H16> dring;
     if constexpr (PRIME_EARLY)
-        if (w < RG_NWC && nsteps > 0) regs_dest_prime<RD_D, RD_LPR>(p, dir, w, lane, nsteps, len, b, dring);
+        if (w < RG_NWC && nsteps > 0) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
     // ---- set-up ----------------------------------------------------------------------------------------------------------
     for (int k = tid; k < nsteps; k += nthreads) {
         const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
-        tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * p.blk * 4;
+        tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
     }
     for (int j = tid; j < SP; j += nthreads) ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
     for (int j = tid; j < (nsteps + 1) * SP; j += nthreads) hist[j] = (j < S) ? hinit[j] : 0.0f;     // row 0; pad columns zero
@@ -228,8 +230,8 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
 #else
                 const bool probe_ = false;
 #endif
-                if constexpr (!PRIME_EARLY) regs_dest_prime<RD_D, RD_LPR>(p, dir, w, lane, nsteps, len, b, dring);
-                regs_compute_dest<NLX, RD_D, RD_LPR>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, smem + lds.xd, probe_, b, dring);
+                if constexpr (!PRIME_EARLY) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
+                regs_compute_dest<NLX, RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, smem + lds.xd, probe_, b, dring);
                 __builtin_amdgcn_s_setprio(0);
                 if (w == 0) FARNN_RG_STAMP(2);
 #if defined(FARNN_PROBES)
@@ -668,7 +670,7 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
 
 // LMO: the instantiation for the label-map path (scores on, the output matrix a label map, tags only): the matrix-core tile
 // code is not compiled in -- a quarter of the instructions, 40 instead of 260 spilled SGPRs
-template <bool MAXSR, bool SCORE, bool NLX, bool LMO = false, bool DEST = false>
+template <bool MAXSR, bool SCORE, bool NLX, bool LMO = false, bool DEST = false, bool H16 = false>
 __global__ void __launch_bounds__(RG_WAVES * 64, 4)          // 4 waves per SIMD = 128 VGPRs: two workgroups per compute unit
 chain_regs_kernel(const RegsParams p) {
     extern __shared__ __align__(16) float smem[];
@@ -679,7 +681,7 @@ chain_regs_kernel(const RegsParams p) {
     long long w0r = 0, w0c = 0;
     if ((p.dbg & 2048) && threadIdx.x == 0) { w0r = (long long)__builtin_amdgcn_s_memrealtime(); w0c = (long long)__builtin_amdgcn_s_memtime(); }
     int b_probe = -1;
-    chain_regs_body<MAXSR, SCORE, NLX, RG_RQ, RG_D, LMO, DEST>(p, smem, (int)threadIdx.x, (int)blockIdx.x, &b_probe);
+    chain_regs_body<MAXSR, SCORE, NLX, RG_RQ, RG_D, LMO, DEST, H16>(p, smem, (int)threadIdx.x, (int)blockIdx.x, &b_probe);
     if ((p.dbg & 2048) && threadIdx.x == 0 && blockIdx.x < WG_STAMP_MAX) {
         const long long w1r = (long long)__builtin_amdgcn_s_memrealtime(), w1c = (long long)__builtin_amdgcn_s_memtime();
         unsigned hwid, xcc;
@@ -690,7 +692,7 @@ chain_regs_kernel(const RegsParams p) {
         o[5] = xcc & 15u; o[6] = (hwid >> 13) & 7u; o[7] = (hwid >> 8) & 15u;
     }
 #else
-    chain_regs_body<MAXSR, SCORE, NLX, RG_RQ, RG_D, LMO, DEST>(p, smem, (int)threadIdx.x, (int)blockIdx.x, nullptr);
+    chain_regs_body<MAXSR, SCORE, NLX, RG_RQ, RG_D, LMO, DEST, H16>(p, smem, (int)threadIdx.x, (int)blockIdx.x, nullptr);
 #endif
 }
 

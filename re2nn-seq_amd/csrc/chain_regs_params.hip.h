@@ -34,6 +34,8 @@ constexpr int RD_XD_FLOATS = 2 * RD_XS + 128;  // the two exchange rows + two du
 struct RegsParams {
     const float *Mf, *Mb;        // [V][SR][SP] blocks and their transposes (layout.hip.h)
     long long blk;               // floats per block
+    const unsigned short *Mf16, *Mb16;   // [V][SP][RD_XS] f16: the blocks' 16-bit image, when every entry is one exactly (layout.hip.h); else null
+    long long blk16;             // BYTES per block of the image
     const float *o, *h0, *hT;
     const int64_t *x, *len;
     const int *order;            // launch order or nullptr
@@ -54,6 +56,7 @@ struct RegsParams {
     int dbg;                     // FARNN_DBG ablation / probe mask: read by the profiling build (-DFARNN_PROBES) only
     int solo_margin;             // the scorer starts a tile alone only if the chain has at least this many steps left after it
     int dest;                    // 1: the destination-split form of the compute wavefronts (chain_dest.hip.h; narrow form, sum semiring)
+    int half;                    // 1: ... reading the 16-bit image (recurrence-only launch; Mf16 / Mb16 set)
     ScoreParams sp;
 };
 constexpr int RG_NG = 5;         // state groups of 16 the scoring stage of this kernel reaches (S <= 72 -> c16 <= 5)

@@ -137,7 +137,8 @@ extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
             if (m->compact_on) return m->last_fused ? "compact_tag_kernel<fused: both chains + label-map scores + decode>" : "compact_chain_kernel";
             if (m->last_regs && m->last_fused && m->use_crf) return "chain_viterbi_kernel<fused: recurrence + scores + CRF decode>";
             if (m->last_regs && m->rgeom.wide) return m->last_fused ? "chain_wide_kernel<fused: scores + decode beside the recurrence>" : "chain_wide_kernel";
-            if (m->last_regs) return m->last_fused ? "chain_regs_kernel<fused: scores + decode beside the recurrence>" : "chain_regs_kernel";
+            if (m->last_regs) return m->last_fused ? "chain_regs_kernel<fused: scores + decode beside the recurrence>"
+                                                   : (m->last_half ? "chain_regs_kernel<f16 blocks>" : "chain_regs_kernel");
             if (m->dense_decomp) return "chain_kernel";
             if (m->kind == KIND_DECOMP && m->last_fused && m->last_wave) return "decomp_regs_kernel<fused: scores + decode beside the recurrence>";
             if (m->kind == KIND_DECOMP || m->kind == KIND_DECOMP1 || m->kind == KIND_DECOMP0)
@@ -167,6 +168,7 @@ static RegsParams make_regs_params(farnn_model *m, const int64_t *x, const int64
     rp.G = rg.G; rp.RPG = rg.RPG; rp.RQ = rg.RQ; rp.D = rg.D; rp.PS = rg.PS; rp.pair = rg.wide ? 0 : 1;
     rp.nl = m->nl; rp.full = full; rp.dbg = tun(TUN_DBG);
     rp.dest = (!rg.wide && m->semiring != FARNN_SEMIRING_MAX && !tun(TUN_NODEST)) ? 1 : 0;     // chain_dest.hip.h
+    rp.Mf16 = m->Mf16; rp.Mb16 = m->Mb16; rp.blk16 = (long long)m->SP * RD_XS * 2;              // (null: no image, build_half_image)
     return rp;
 }
 
@@ -187,6 +189,7 @@ static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, in
     const ChainGeom &g = m->geom;
     if (fused) *fused = false;
     m->last_regs = false;
+    m->last_half = false;
     // ---- the register-fed kernel (chain_regs.hip.h) where its geometry applies: S <= 72, two workgroups per compute unit, or
     // its wide form (chain_wide.hip.h): 72 < S <= 128, one workgroup per compute unit.
     // With fuse_sp (threshold/argmax decode, K <= 256) the scores and the decode run beside the recurrence: ONE launch.
@@ -226,6 +229,9 @@ static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, in
                 rp.sp = *fuse_sp;
                 if (fused) *fused = true;
             }
+            // the 16-bit image where the handle has one (an eligible model, build_half_image): the recurrence-only launch of the
+            // destination split reads half the bytes with half the load instructions; FARNN_NOHALF=1 keeps the f32 blocks
+            rp.half = (rp.dest && !score && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF)) ? 1 : 0;
             KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
             if (paired && score) { rp.D = 2; rp.pair = 1; }
             const int rc = (paired && score) ? launch_chain_wide_paired(rp, m->semiring == FARNN_SEMIRING_MAX, s, kt.e0, kt.e1)
@@ -233,6 +239,7 @@ static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, in
                                      : launch_chain_regs(rp, m->semiring == FARNN_SEMIRING_MAX, score, s, kt.e0, kt.e1);
             if (rc) return rc;
             m->last_regs = true;
+            m->last_half = rp.half != 0;
             return FARNN_OK;
         }
     }
@@ -871,7 +878,9 @@ extern "C" double farnn_kernel_algorithmic_bytes(const farnn_model *m, int32_t w
         if (m->compact_on) return (2.0 * S * m->bmNS * 8 + 8) * n;      // one bit-packed block per direction + the token id
         if (!m->dense_decomp && (m->kind == KIND_DECOMP || m->kind == KIND_DECOMP1 || m->kind == KIND_DECOMP0))
             return (R * 4 + 8) * n + (2.0 * S * R + S * S) * 4;
-        // one block per direction + the token id (+ the tag when the decode is this kernel's epilogue)
+        // one block per direction + the token id (+ the tag when the decode is this kernel's epilogue); the 16-bit image: what the
+        // launched form requests
+        if (m->last_regs && m->last_half) return (2.0 * S * S * 2 + 8) * n;
         return (2.0 * S * S * 4 + 8 + (m->last_fused ? 4 : 0)) * n + (m->last_fused ? K * S * 4 : 0);
     }
     if (which == KERN_SCORE) {

@@ -6,6 +6,8 @@
 // row then starts on a dwordx4 boundary) and a transposed copy is written for the backward chain.
 #pragma once
 #include "common.hip.h"
+#include "half_exact.h"
+#include "chain_regs_params.hip.h"
 
 namespace farnn {
 
@@ -44,6 +46,29 @@ __global__ void premix_kernel(const float *T, const float *W, const float *mask,
     }
     Mf[v * SR * SP + idx] = f;
     if (Mb) Mb[v * SR * SP + idx] = bwd;
+}
+
+// ---- the 16-bit image of the blocks (chain_dest.hip.h, H16) ----
+// *bad = 1 if any of the n floats is not an f16 exactly (half_exact.h): the whole of Mf / Mb, pad rows and columns included
+__global__ void half_eligible_kernel(const float *M, long long n, int *bad) {
+    bool no = false;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        no |= !half_exact(M[i]);
+    if (no) atomicExch(bad, 1);
+}
+
+// img[v][r][80] f16, r < SP: a row is ten 16-byte chunks.  Chunk c = q + 5 h holds the f32 row's 16-byte chunks q + 10 h and
+// q + 10 h + 5 (columns 4 k .. 4 k + 3 of chunk k; zeros behind the row): lane q of the destination split's five lanes per row
+// multiplies ITS four f32 chunks q, q + 5, q + 10, q + 15 -- the same products in the same order as the f32 form -- from two loads.
+// grid = (ceil(SP * 80 / 256), V)
+__global__ void half_image_kernel(const float *M, unsigned short *img, int SP, int SR) {
+    const long long v = blockIdx.y;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= SP * RD_XS) return;
+    const int r = idx / RD_XS, j = idx - r * RD_XS, c = j >> 3, e = j & 7;
+    const int k = (c % 5) + 10 * (c / 5) + (e >= 4 ? 5 : 0), col = 4 * k + (e & 3);
+    const float x = (r < SR && col < SP) ? M[(v * SR + r) * SP + col] : 0.0f;
+    img[v * SP * RD_XS + idx] = half_bits_exact(x);
 }
 
 // SR >= S: rows allocated per block (extra rows zero-filled; see chain.hip.h)

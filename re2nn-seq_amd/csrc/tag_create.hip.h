@@ -49,6 +49,9 @@ static int onehot_geometry(farnn_model *m) {
     return m->geom.NCH > 4 ? fail(FARNN_ERANGE, "more than 1024 states%s%s") : FARNN_OK;
 }
 
+// (Mf / Mb are written by the stages of a create alone -- premix_chain_blocks, launch_premix_fst4, build_dense_blocks -- and the
+//  16-bit image of an eligible handle, build_half_image, is derived from them once.  Whatever ever rewrites the blocks of a LIVE
+//  handle must drop m->Mf16 / m->Mb16, or re-run build_half_image, before the next tag call: a stale image is a silent wrong answer.)
 static int alloc_chain_blocks(farnn_model *m) {
     const size_t nM = (size_t)m->V * m->geom.SR * m->SP;
     if (int rc = dev_alloc(m, (void **)&m->Mf, nM * 4)) return rc;
@@ -59,6 +62,33 @@ static int alloc_chain_blocks(farnn_model *m) {
 static int premix_chain_blocks(farnn_model *m, const float *T, const float *W, const float *mask) {
     if (int rc = alloc_chain_blocks(m)) return rc;
     return launch_premix(T, W, mask, m->Mf, m->Mb, m->V, m->S, m->SP, m->geom.SR);
+}
+
+// The blocks' 16-bit image for the destination split's recurrence-only launch (chain_dest.hip.h, H16): built only for a handle
+// that launch serves (S <= 72: the narrow register-fed form; sum semiring) and only if EVERY entry of Mf and Mb is an f16 exactly.
+// Nothing rewrites the blocks of a live handle (every writer of Mf / Mb is a stage of a create), so the image never goes stale.
+static int build_half_image(farnn_model *m) {
+    if (!m->Mf || !m->Mb || !m->rgeom.ok || m->rgeom.wide || m->semiring == FARNN_SEMIRING_MAX || m->SP > RG_MAXSP || tun(TUN_NOHALF))
+        return FARNN_OK;
+    const long long nM = (long long)m->V * m->geom.SR * m->SP;
+    DevTmp tmp;
+    int *bad = nullptr, bad_h = 0;
+    if (int rc = tmp.zeros(&bad, 1)) return rc;
+    const unsigned nb = (unsigned)std::min<long long>((nM + 255) / 256, 4096);
+    half_eligible_kernel<<<nb, 256>>>(m->Mf, nM, bad);
+    half_eligible_kernel<<<nb, 256>>>(m->Mb, nM, bad);
+    FARNN_HIP_TRY(hipGetLastError());
+    FARNN_HIP_TRY(hipMemcpy(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad_h) return FARNN_OK;
+    const size_t bytes = (size_t)m->V * m->SP * RD_XS * sizeof(unsigned short);
+    if (int rc = dev_alloc(m, (void **)&m->Mf16, bytes)) return rc;
+    if (int rc = dev_alloc(m, (void **)&m->Mb16, bytes)) return rc;
+    const dim3 grid((m->SP * RD_XS + 255) / 256, m->V);
+    half_image_kernel<<<grid, 256>>>(m->Mf, m->Mf16, m->SP, m->geom.SR);
+    half_image_kernel<<<grid, 256>>>(m->Mb, m->Mb16, m->SP, m->geom.SR);
+    FARNN_HIP_TRY(hipGetLastError());
+    FARNN_HIP_TRY(hipDeviceSynchronize());
+    return FARNN_OK;
 }
 
 // h0 / hT (dw's aliases are read by the decomposed kinds only)
@@ -274,6 +304,7 @@ static int ifst_create_impl(const farnn_onehot_ifst_desc *d, int device, farnn_m
         if ((rc = tmp.view(&T, d->T, (size_t)m->V * m->S * m->S, od))) return rc;
         if ((rc = tmp.view(&W, d->W, (size_t)m->S * m->S, od))) return rc;
         if ((rc = premix_chain_blocks(m, T, W, nullptr))) return rc;
+        if ((rc = build_half_image(m))) return rc;
         if ((rc = alloc_bitmaps(m))) return rc;
         if (m->bmNS && (rc = build_bitmaps(m, T, W, nullptr))) return rc;
     }

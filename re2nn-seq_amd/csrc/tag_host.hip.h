@@ -56,6 +56,8 @@ struct farnn_model {
     float threshold = 0.5f, sig_k = 1.0f;
     // device-resident, library-owned weights
     float *Mf = nullptr, *Mb = nullptr;     // chain blocks [V][S][SP] (+ transposed)
+    unsigned short *Mf16 = nullptr, *Mb16 = nullptr;   // their 16-bit image [V][SP][80] f16, when every entry is an f16 exactly (build_half_image)
+    bool last_half = false;                 // the last recurrence read the 16-bit image
     u64 *bmF = nullptr, *bmB = nullptr, *bmWF = nullptr, *bmWB = nullptr;   // compact form: bit-packed blocks (compact.hip.h)
     int bmNS = 0;                           // 64-bit words per bitmap row; 0: no compact form
     u64 *bmMF = nullptr, *bmMB = nullptr, *bmXF = nullptr, *bmXB = nullptr;   // K1t's planes: T | W, T & W (merge_planes_kernel; S <= 128)

@@ -15,7 +15,7 @@ For every kernel of a device assembly file (hipcc -save-temps=obj: <unit>-hip-am
 Arithmetic that consumes a ring register (v_fma, v_pk_fma, ...) is what the kernel does behind its waits and is not a finding.
 
     python scripts/check_ring_registers.py <file.s> [--kernels SUBSTRING] [--verbose]
-Exit status 1 on a finding.  csrc/build.py runs it on every unit that asks for it (`// build-check: ring-registers <substring>`).
+Exit status 1 on a finding, and when a --kernels pattern matches no kernel with a load ring.  csrc/build.py runs it on every unit that asks for it (`// build-check: ring-registers <substring>`).
 """
 import re
 import sys
@@ -189,6 +189,9 @@ def main():
     for name, no, text in findings:
         print('{}:{}: `{}` touches a register whose asm-issued load is still in flight, in {}'.format(args[0], no, text, name))
     print('# ring-register check: {} kernel(s) with an asm-issued load ring, {} finding(s)'.format(checked, len(findings)))
+    if only and not checked:                               # a --kernels pattern that matches nothing has checked nothing
+        print('# no kernel with an asm-issued load ring matches --kernels {}'.format(only))
+        return 1
     return 1 if (findings or incomplete) else 0
 
 
