@@ -229,6 +229,10 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
                          : [rem] "s"(rem_), [dm1] "n"(D - 1), [cnt] "n"((D - 1) * NC) : "scc"); \
     } while (0)
 
+    // ... and the STEADY state's (16-bit form): D - 1 younger steps are in flight for certain -- no compare, no branch
+#define FARNN_RD_WAIT_STEADY(d)                                                                \
+    asm volatile("s_waitcnt vmcnt(%[cnt])" : "+v"(r[d][0]), "+v"(r[d][NC - 1]) : [cnt] "n"((D - 1) * NC))
+
     unsigned nlo = 0, nhi = 0;              // (the ring is primed: regs_dest_prime, before the set-up barrier)
 #if defined(FARNN_PROBES)
     long long ph[4] = {0, 0, 0, 0}, pt = 0;
@@ -238,92 +242,113 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
 #define FARNN_RD_PHASE(i) do { } while (0)
     (void)probe; (void)b;
 #endif
+    // ONE step.  CK (checked): the sequence may end within the ring's reach -- the wait drains the last D - 1 steps, the issue of step
+    // t + D is conditional.  Unchecked: the caller guarantees t + D < nsteps (the steady state below).
+    auto step = [&](auto checked, const int d, const int t) __attribute__((always_inline)) {
+        constexpr bool CK = decltype(checked)::value;
+        const int roff = (d & 1) * RD_XS;                // the exchange buffer this step reads (t and d have the same parity)
+        // the partners' flags FIRST, this lane's five state chunks behind them in the same batch
+        v4f st[NS];
+        {
+            int fl = lds_flag_get(pflag);
+#pragma unroll
+            for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
+            asm volatile("" ::: "memory");
+            if (__ballot(fl < t + 1) != 0ull) {
+                // a partner is late: poll the flags alone (one 4-byte read per round -- re-reading the chunks with every poll
+                // would keep the LDS busy with 16-byte reads of stale data, at the expense of the other workgroup on the
+                // compute unit), then the chunks once more
+                do { fl = lds_flag_get(pflag); } while (__ballot(fl < t + 1) != 0ull);
+#pragma unroll
+                for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
+                asm volatile("" ::: "memory");
+            }
+        }
+        FARNN_RD_PHASE(0);                               // the partners' entries of this step's state
+        if constexpr (CK) FARNN_RD_WAIT(d, nsteps - 1 - t);     // steps issued after this one: min(D - 1, nsteps - 1 - t)
+        else FARNN_RD_WAIT_STEADY(d);                       // ... D - 1: a plain counted wait
+        FARNN_RD_PHASE(1);                               // this step's block pieces
+        // The four accumulators as TWO register pairs, multiplied pair by pair: v_pk_fma_f32 on the halves of the 16-byte chunks as
+        // they lie in the registers.  (Written as four scalar fmaf the compiler packed them too -- but as (x, z) / (y, w), and
+        // shuffled the operands of every chunk into that pairing: 28 v_mov_b32 per step beside 8 v_pk_fma, seen in the ISA.
+        // The compute wavefronts of a compute unit share four SIMDs: the step is their VALU instruction count.)  Same
+        // products into the same accumulators in the same order: bit-identical.
+        float sa, sb;
+        if constexpr (H16) {
+            // f32 chunk i of the lane lies in image chunk i >> 1, registers 2 (i & 1) and 2 (i & 1) + 1: (x, y) and (z, w) as halves
+            float a0, a1, a2, a3;
+            fma_h16<false, true>(a0, r[d][0].x, st[0].x);
+            fma_h16<true, true>(a1, r[d][0].x, st[0].y);
+            fma_h16<false, true>(a2, r[d][0].y, st[0].z);
+            fma_h16<true, true>(a3, r[d][0].y, st[0].w);
+#pragma unroll
+            for (int i = 1; i < NS; i++) {
+                const float bxy = (i & 1) ? r[d][i >> 1].z : r[d][i >> 1].x, bzw = (i & 1) ? r[d][i >> 1].w : r[d][i >> 1].y;
+                fma_h16<false, false>(a0, bxy, st[i].x);
+                fma_h16<true, false>(a1, bxy, st[i].y);
+                fma_h16<false, false>(a2, bzw, st[i].z);
+                fma_h16<true, false>(a3, bzw, st[i].w);
+            }
+            sa = a0 + a1; sb = a2 + a3;
+        } else {
+            v2f a01 = v2f{0.f, 0.f}, a23 = v2f{0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < NS; i++) {
+                a01 = __builtin_elementwise_fma(st[i].xy, r[d][i].xy, a01);
+                a23 = __builtin_elementwise_fma(st[i].zw, r[d][i].zw, a23);
+            }
+            sa = a01.x + a01.y; sb = a23.x + a23.y;
+        }
+        asm volatile("" : "+v"(sa), "+v"(sb));            // (two scalar adds: packed into one v_pk_add they cost three v_mov)
+        float s = sa + sb;
+        if constexpr (LPR == 4) s = quad_sum(s);
+        else {
+            // the five lanes of a row: lane q = 4 ends up with x4 + x3 + x2 + x1 (+ x0): row_shr 1, row_shr 2, row_shr 4 of the
+            // ORIGINAL value (the other lanes' sums mix rows and are never used)
+            const float s1 = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x111, 0xf, 0xf, true));
+            const float s2 = s1 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s1), 0x112, 0xf, 0xf, true));
+            s = s2 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x114, 0xf, 0xf, true));
+        }
+        const float pre = s * c_pre;
+        float hn;
+        if (NLX) hn = apply_nl(pre, nl_mode);            // tanh, relu-tanh, sigmoid
+        else     hn = nl_relu ? fmaxf(pre, 0.0f) : pre;  // none / relu: no branch in the step
+        const float hx = is_flane ? __int_as_float(t + 2) : hn * c_post;      // what the next step multiplies with; lane 63: the flag
+        asm volatile("" ::: "memory");
+        *hptr = hn;                                      // row t + 1 of `hist` (or a dump slot)
+        hptr += hstep;
+        if (d & 1) *xw0 = hx; else *xw1 = hx;            // the exchange row of parity (t + 1) & 1, the flag behind it in the same store
+        asm volatile("" ::: "memory");
+        // the slot's registers are dead: the block of step t + D
+        // (16-bit form: the slot's old values are named here as inputs, which keeps them live up to the issue, so the compiler finds no
+        //  free register there for the step's temporaries -- the tanh kernel parked some in them, and the build's ring-register check
+        //  cannot tell such a temporary from a copy of a register whose load is in flight.  This is a NUDGE, not a binding: nothing ties
+        //  the issue's "=&v" outputs to these registers; what holds is that scripts/check_ring_registers.py passes on the built kernel.)
+        if constexpr (H16) asm volatile("" :: "v"(r[d][0]), "v"(r[d][NC - 1]));
+        if (!CK || t + D < nsteps) FARNN_RD_ISSUE(d, nlo, nhi);
+        // where the block of step (t + 1) + D is, while the partners finish theirs (chain_regs.hip.h)
+        if (d == D - 1 && ((t + 1 + D) & 63) == 0 && t + 1 + D < nsteps) FARNN_RD_WINDOW(t + 1 + D);
+        FARNN_RD_BASE(t + 1 + D, nlo, nhi);
+        asm volatile("" : "+s"(nlo), "+s"(nhi));
+        FARNN_RD_PHASE(2);                               // FMAs, reduce, stores, next loads issued
+    };
     if (D < nsteps) FARNN_RD_BASE(D, nlo, nhi);            // step 0's look-ahead (the window of steps 0 .. 63 is loaded)
-    for (int t0 = 0; t0 < nsteps; t0 += D) {
+    int t0 = 0;
+    // The STEADY state (16-bit form): every group of D steps with t0 + 2 D <= nsteps -- each of its steps t has t + D < nsteps, so
+    // there is no end-of-sequence test, the issue of step t + D is unconditional and the wait is the plain counted one.  The
+    // checked body below takes the rest of the sequence (at most 2 D - 1 steps) from the same ring, slot by slot as before.
+    if constexpr (H16) {
+        for (; t0 + 2 * D <= nsteps; t0 += D) {
+#pragma unroll
+            for (int d = 0; d < D; d++) step(std::false_type{}, d, t0 + d);
+        }
+    }
+    for (; t0 < nsteps; t0 += D) {
 #pragma unroll
         for (int d = 0; d < D; d++) {
             const int t = t0 + d;
             if (t >= nsteps) break;
-            constexpr int dummy = 0; (void)dummy;
-            const int roff = (d & 1) * RD_XS;                // the exchange buffer this step reads (t and d have the same parity)
-            // the partners' flags FIRST, this lane's five state chunks behind them in the same batch
-            v4f st[NS];
-            {
-                int fl = lds_flag_get(pflag);
-#pragma unroll
-                for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
-                asm volatile("" ::: "memory");
-                if (__ballot(fl < t + 1) != 0ull) {
-                    // a partner is late: poll the flags alone (one 4-byte read per round -- re-reading the chunks with every poll
-                    // would keep the LDS busy with 16-byte reads of stale data, at the expense of the other workgroup on the
-                    // compute unit), then the chunks once more
-                    do { fl = lds_flag_get(pflag); } while (__ballot(fl < t + 1) != 0ull);
-#pragma unroll
-                    for (int i = 0; i < NS; i++) st[i] = *reinterpret_cast<const v4f *>(xr + roff + 4 * LPR * i);
-                    asm volatile("" ::: "memory");
-                }
-            }
-            FARNN_RD_PHASE(0);                               // the partners' entries of this step's state
-            FARNN_RD_WAIT(d, nsteps - 1 - t);                // steps issued after this one: min(D - 1, nsteps - 1 - t)
-            FARNN_RD_PHASE(1);                               // this step's block pieces
-            // The four accumulators as TWO register pairs, multiplied pair by pair: v_pk_fma_f32 on the halves of the 16-byte chunks as
-            // they lie in the registers.  (Written as four scalar fmaf the compiler packed them too -- but as (x, z) / (y, w), and
-            // shuffled the operands of every chunk into that pairing: 28 v_mov_b32 per step beside 8 v_pk_fma, seen in the ISA.
-            // The compute wavefronts of a compute unit share four SIMDs: the step is their VALU instruction count.)  Same
-            // products into the same accumulators in the same order: bit-identical.
-            float sa, sb;
-            if constexpr (H16) {
-                // f32 chunk i of the lane lies in image chunk i >> 1, registers 2 (i & 1) and 2 (i & 1) + 1: (x, y) and (z, w) as halves
-                float a0, a1, a2, a3;
-                fma_h16<false, true>(a0, r[d][0].x, st[0].x);
-                fma_h16<true, true>(a1, r[d][0].x, st[0].y);
-                fma_h16<false, true>(a2, r[d][0].y, st[0].z);
-                fma_h16<true, true>(a3, r[d][0].y, st[0].w);
-#pragma unroll
-                for (int i = 1; i < NS; i++) {
-                    const float bxy = (i & 1) ? r[d][i >> 1].z : r[d][i >> 1].x, bzw = (i & 1) ? r[d][i >> 1].w : r[d][i >> 1].y;
-                    fma_h16<false, false>(a0, bxy, st[i].x);
-                    fma_h16<true, false>(a1, bxy, st[i].y);
-                    fma_h16<false, false>(a2, bzw, st[i].z);
-                    fma_h16<true, false>(a3, bzw, st[i].w);
-                }
-                sa = a0 + a1; sb = a2 + a3;
-            } else {
-                v2f a01 = v2f{0.f, 0.f}, a23 = v2f{0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < NS; i++) {
-                    a01 = __builtin_elementwise_fma(st[i].xy, r[d][i].xy, a01);
-                    a23 = __builtin_elementwise_fma(st[i].zw, r[d][i].zw, a23);
-                }
-                sa = a01.x + a01.y; sb = a23.x + a23.y;
-            }
-            asm volatile("" : "+v"(sa), "+v"(sb));            // (two scalar adds: packed into one v_pk_add they cost three v_mov)
-            float s = sa + sb;
-            if constexpr (LPR == 4) s = quad_sum(s);
-            else {
-                // the five lanes of a row: lane q = 4 ends up with x4 + x3 + x2 + x1 (+ x0): row_shr 1, row_shr 2, row_shr 4 of the
-                // ORIGINAL value (the other lanes' sums mix rows and are never used)
-                const float s1 = s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x111, 0xf, 0xf, true));
-                const float s2 = s1 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s1), 0x112, 0xf, 0xf, true));
-                s = s2 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x114, 0xf, 0xf, true));
-            }
-            const float pre = s * c_pre;
-            float hn;
-            if (NLX) hn = apply_nl(pre, nl_mode);            // tanh, relu-tanh, sigmoid
-            else     hn = nl_relu ? fmaxf(pre, 0.0f) : pre;  // none / relu: no branch in the step
-            const float hx = is_flane ? __int_as_float(t + 2) : hn * c_post;      // what the next step multiplies with; lane 63: the flag
-            asm volatile("" ::: "memory");
-            *hptr = hn;                                      // row t + 1 of `hist` (or a dump slot)
-            hptr += hstep;
-            if (d & 1) *xw0 = hx; else *xw1 = hx;            // the exchange row of parity (t + 1) & 1, the flag behind it in the same store
-            asm volatile("" ::: "memory");
-            // the slot's registers are dead: the block of step t + D
-            if (t + D < nsteps) FARNN_RD_ISSUE(d, nlo, nhi);
-            // where the block of step (t + 1) + D is, while the partners finish theirs (chain_regs.hip.h)
-            if (d == D - 1 && ((t + 1 + D) & 63) == 0 && t + 1 + D < nsteps) FARNN_RD_WINDOW(t + 1 + D);
-            FARNN_RD_BASE(t + 1 + D, nlo, nhi);
-            asm volatile("" : "+s"(nlo), "+s"(nhi));
-            FARNN_RD_PHASE(2);                               // FMAs, reduce, stores, next loads issued
+            step(std::true_type{}, d, t);
         }
     }
     // (the last step stored nsteps + 1: writer / scorer count the rows of `hist` by these flags)
@@ -333,6 +358,7 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
                b, dir, ph[0] / nsteps, ph[1] / nsteps, ph[2] / nsteps);
 #endif
 #undef FARNN_RD_PHASE
+#undef FARNN_RD_WAIT_STEADY
 #undef FARNN_RD_WAIT
 #undef FARNN_RD_WAITSTR
 #undef FARNN_RD_ISSUE

@@ -11,7 +11,7 @@ For every kernel of a device assembly file (hipcc -save-temps=obj: <unit>-hip-am
   ring registers = the destination VGPRs of every `global_load_dword*` that sits INSIDE an inline-asm block (;;#ASMSTART .. ;;#ASMEND);
   a finding      = a compiler-generated instruction (outside every asm block) that moves or spills a ring register:
                    v_mov_b32 / v_mov_b64 / v_swap_b32 / v_accvgpr_write / v_accvgpr_read / scratch_* / buffer_store* with a ring
-                   register as source or destination.
+                   register as a SOURCE (a copy or spill reads the stale value; a compiler write to such a register is not looked for).
 Arithmetic that consumes a ring register (v_fma, v_pk_fma, ...) is what the kernel does behind its waits and is not a finding.
 
     python scripts/check_ring_registers.py <file.s> [--kernels SUBSTRING] [--verbose]
