@@ -439,7 +439,12 @@ inline ChainGeom chain_geometry_nw(int S, int nw, int nld) {
     if (gm.CPR <= 64) {
         gm.NCH = 1; gm.LPR = gm.CPR; gm.G = 64 / gm.CPR;
         if (gm.G > CHAIN_MAX_G) gm.G = CHAIN_MAX_G;
-    } else { gm.NCH = (gm.CPR + 63) / 64; gm.LPR = 64; gm.G = 1; }
+    } else {
+        // the chunks per lane AS INSTANTIATED (chain_kernel<1 | 2 | 4>): three run in the four-chunk kernel, whose ring holds
+        // PER = 16 pieces per 4-row chunk -- the host's phase_bytes() must size the ring the kernel walks
+        gm.NCH = (gm.CPR + 63) / 64; gm.LPR = 64; gm.G = 1;
+        if (gm.NCH == 3) gm.NCH = 4;
+    }
     gm.NLD = nld;
     gm.NW = nw;
     int ng = gm.NW * gm.G;

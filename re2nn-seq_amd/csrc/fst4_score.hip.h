@@ -151,6 +151,13 @@ fst4_score_kernel(const Fst4Params p) {
     }
 }
 
+// K3's dynamic LDS: alpha [SP], two score rows [Kp] and, for independent=1, Z [S][SP] (Kp = the label columns as the launcher gets
+// them, a multiple of 64).  The creates and the launcher agree through this one function.
+inline size_t fst4_score_lds_bytes(int S, int SP, int Kp, bool ind1) {
+    return ((size_t)SP + 2 * (size_t)Kp + (ind1 ? (size_t)S * SP : 0)) * sizeof(float);
+}
+constexpr size_t FST4_SCORE_LDS_LIMIT = 160 * 1024;
+
 inline int launch_fst4_score(const float *blocks, const float *A, const float *Bk, const float *P,
                              const int64_t *x, const int64_t *len, const int64_t *offs, int32_t *tags,
                              int64_t *flat, float *scores, int B, int L, int S, int SP, int C, int Kp,
@@ -165,8 +172,9 @@ inline int launch_fst4_score(const float *blocks, const float *A, const float *B
     int nch;
     if (p.CPR <= 64) { nch = 1; p.LPR = p.CPR; p.G = 64 / p.CPR; }
     else { nch = (p.CPR + 63) / 64; p.LPR = 64; p.G = 1; }
-    size_t lds = ((size_t)SP + 2 * (size_t)Kp + (Oten ? (size_t)S * SP : 0)) * sizeof(float);
-    if (lds > 160 * 1024) return fail(FARNN_ERANGE, "independent=1 scoring needs S*S*4 bytes of LDS%s%s");
+    const size_t lds = fst4_score_lds_bytes(S, SP, Kp, Oten != nullptr);
+    // (farnn_onehot_ind1_create refuses the same condition: no handle reaches this line with it; kept as a guard)
+    if (lds > FST4_SCORE_LDS_LIMIT) return fail(FARNN_ERANGE, "independent=1 scoring needs S*S*4 bytes of LDS%s%s");
     dim3 grid(L, B), block(256);
 #define FARNN_LAUNCH_FST4(N)                                                                          \
     do {                                                                                              \

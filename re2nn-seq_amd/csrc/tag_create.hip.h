@@ -379,6 +379,9 @@ extern "C" int farnn_onehot_ind1_create(const farnn_onehot_ind1_desc *d, int dev
     m->mask_by_output = d->mask_by_output;
     if (m->K > 1024) return fail(FARNN_ERANGE, "more than 1024 label columns%s%s");
     if ((rc = onehot_geometry(m))) return rc;
+    // K3 keeps (alpha beta^T) .* Tf[x_i] of a token in LDS: refused here, where S and the label columns are known, not at farnn_tag
+    if (fst4_score_lds_bytes(m->S, m->SP, m->Kc, true) > FST4_SCORE_LDS_LIMIT)
+        return fail(FARNN_ERANGE, "onehot_ind1: independent=1 scoring needs S*S*4 bytes of LDS per token (S too large)%s%s");
     const int od = d->weights_on_device;
     {
         DevTmp tmp;

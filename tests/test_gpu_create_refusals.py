@@ -54,6 +54,12 @@ def test_refused_creates_free_their_handle_and_temporaries():
     # 257 label columns: refused after the handle exists
     O257 = np.zeros((257, S), np.float32)
     d_edges, d_257 = base(NC), base(257, T, W, O257)
+    # independent=1 over 201 states: (alpha beta^T) .* Tf[x_i] does not fit 160 KiB of LDS -- refused after the handle exists
+    S1 = 201
+    T1, W1, O1 = np.zeros((5, S1, S1), np.float32), np.zeros((S1, S1), np.float32), np.zeros((NC, S1, S1), np.float32)
+    e1 = np.ones(S1, np.float32)
+    d_ind1 = _lib.OnehotInd1Desc(5, S1, NC, _lib.ptr(T1), _lib.ptr(W1), _lib.ptr(O1), _lib.ptr(e1), _lib.ptr(e1), None,
+                                 _lib.SEMIRING['sum'], 0, 0.5, 0, 0)
 
     torch.cuda.synchronize()
     free_before = torch.cuda.mem_get_info()[0]
@@ -63,6 +69,7 @@ def test_refused_creates_free_their_handle_and_temporaries():
         _refused('farnn_onehot_ifst_create_compact', (C.byref(d_edges), C.byref(half)), EINVAL,
                  'onehot_ifst compact form: an edge is out of range or has a weight other than 1')
         _refused('farnn_onehot_ifst_create', (C.byref(d_257),), ERANGE, 'more than 256 label columns')
+        _refused('farnn_onehot_ind1_create', (C.byref(d_ind1),), ERANGE, 'independent=1 scoring needs S*S*4 bytes of LDS')
     torch.cuda.synchronize()
     dropped = free_before - torch.cuda.mem_get_info()[0]
     print('device memory free before - after %d refused creates of each kind: %.1f MB' % (ROUNDS, dropped / 2.0 ** 20))
