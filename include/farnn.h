@@ -508,6 +508,52 @@ int  farnn_fst4_train_step(farnn_fst4_train_ctx *ctx, const farnn_fst4_train_wei
 int  farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *ctx, int32_t enable);
 int  farnn_fst4_train_time(farnn_fst4_train_ctx *ctx, double *total_ms, int64_t *steps);
 
+/* ---- training step of the onehot independent=1 model (FARNN_S_O_I, --method onehot --independent 1) --------
+ * Replaces FARNN_S_O_I.forward_local(train=True) + loss.backward() (model_onehot.py:184-306, train_onehot.py:156-206) for
+ * the sum semiring and the CE1 loss.  N[w] = T[w] + W (:250); Mc[w] = N[w], or N[w] * output_tensor.sum(0) with
+ * mask_by_output (args.independent == 2, :252, :260, :272); both chains run on Mc and use relu, whatever update_nonlinear
+ * says (:266, :278); score_i[c] = sum_{s,j} O[c,s,j] alpha_i[s] beta_{i+1}[j] N[x_i][s,j] [. P] with alpha_i the state BEFORE
+ * token i, N and not Mc, and no relu (:229-233, :293-304); the loss is the cross-entropy, mean over the valid tokens (:60,
+ * :142); the tags are local_decode's (:172-176).  language_tensor is the only tensor trained (:213-223);
+ * output_wildcard_mat is not read under CE1 (:251-252).
+ * Limits: S <= 128 (the chains' kernels, as farnn_onehot_train_create), C <= 2400 (the loss kernel keeps two score vectors
+ * per wavefront, 8 x 2 x C floats, within 150 KiB of LDS; farnn_ind1_train_create returns FARNN_ERANGE outside),
+ * B (L + 1) < 2^30 (the step returns FARNN_ERANGE before enqueuing anything and leaves the outputs untouched).  All
+ * pointers are DEVICE pointers; tensors are row-major and unpadded. */
+typedef struct farnn_ind1_train_ctx farnn_ind1_train_ctx;
+
+typedef struct {
+    int32_t V, S, C;            /* vocabulary rows of T, states, score columns (labels + 1)         */
+    int32_t mask_by_output;     /* args.independent == 2: the chains run on N * O.sum(0) (:260)     */
+    float   threshold;          /* decode clamp of column C-1 (model_onehot.py:172-176)             */
+    int32_t o_idx;              /* label written for column C-1 (:176)                              */
+} farnn_ind1_train_dims;
+
+typedef struct {
+    const float *T;             /* [V][S][S] language_tensor (:213) */
+    const float *W;             /* [S][S]    wildcard_mat (:216)    */
+    const float *O;             /* [C][S][S] output_tensor (:219)   */
+    const float *h0, *hT;       /* [S] (:209-212)                   */
+    const float *P;             /* [C][C] priority matrix or NULL (args.use_priority = 0, :301) */
+} farnn_ind1_train_weights;
+
+typedef struct {
+    float *loss;                /* [1]                                                                 */
+    float *dT;                  /* [V][S][S] (rows of words absent from the batch are written as zero) */
+    int32_t *tags;              /* [B][L] decoded labels of this forward pass, -1 at pad positions     */
+} farnn_ind1_train_outputs;
+
+int  farnn_ind1_train_create(const farnn_ind1_train_dims *dims, int device, farnn_ind1_train_ctx **out);
+void farnn_ind1_train_destroy(farnn_ind1_train_ctx *ctx);
+/* One step on the given stream: writes all outputs (no float atomics: bit-identical across runs).  x, lengths, labels,
+ * valid_tokens and the handling of bad labels / words: as farnn_onehot_ifst_train_step. */
+int  farnn_ind1_train_step(farnn_ind1_train_ctx *ctx, const farnn_ind1_train_weights *w, const int64_t *x,
+                           const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                           int64_t valid_tokens, const farnn_ind1_train_outputs *out, void *stream);
+/* as farnn_train_set_profiling / farnn_train_time */
+int  farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *ctx, int32_t enable);
+int  farnn_ind1_train_time(farnn_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);
+
 /* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
  * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,
  * no weight decay, no amsgrad:

@@ -143,6 +143,19 @@ class Fst4TrainOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT4', 'dW4', 'tags')]
 
 
+class Ind1TrainDims(C.Structure):
+    _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('C', C.c_int32), ('mask_by_output', C.c_int32),
+                ('threshold', C.c_float), ('o_idx', C.c_int32)]
+
+
+class Ind1TrainWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('T', 'W', 'O', 'h0', 'hT', 'P')]
+
+
+class Ind1TrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT', 'tags')]
+
+
 class OptimDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
@@ -173,6 +186,13 @@ SIGNATURES = {
                                         C.POINTER(Fst4TrainOutputs), C.c_void_p]),
     'farnn_fst4_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_fst4_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_ind1_train_create': (C.c_int, [C.POINTER(Ind1TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_ind1_train_destroy': (None, [C.c_void_p]),
+    'farnn_ind1_train_step': (C.c_int, [C.c_void_p, C.POINTER(Ind1TrainWeights), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                        C.POINTER(Ind1TrainOutputs), C.c_void_p]),
+    'farnn_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -633,6 +653,18 @@ class Fst4TrainContext(_TrainContextBase):
 
     def __init__(self, V, S, n_cols, threshold=0.5, o_idx=0, device=0):
         self._open(Fst4TrainDims(int(V), int(S), int(n_cols), float(threshold), int(o_idx)), device)
+        self.dims = (int(V), int(S), int(n_cols))
+
+
+class Ind1TrainContext(_TrainContextBase):
+    """Owns one farnn_ind1_train_ctx* (training step of the onehot independent=1 model, include/farnn.h)."""
+    _create, _destroy, _step = 'farnn_ind1_train_create', 'farnn_ind1_train_destroy', 'farnn_ind1_train_step'
+    _set_profiling, _time = 'farnn_ind1_train_set_profiling', 'farnn_ind1_train_time'
+    _weights, _outputs = Ind1TrainWeights, Ind1TrainOutputs
+
+    def __init__(self, V, S, n_cols, mask_by_output=False, threshold=0.5, o_idx=0, device=0):
+        self._open(Ind1TrainDims(int(V), int(S), int(n_cols), int(bool(mask_by_output)), float(threshold), int(o_idx)),
+                   device)
         self.dims = (int(V), int(S), int(n_cols))
 
 

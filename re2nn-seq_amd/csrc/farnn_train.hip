@@ -1,5 +1,5 @@
 // libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
-// i-FST (farnn_onehot_train_*) and the onehot FST (farnn_fst4_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
+// i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*) and the onehot independent=1 model (farnn_ind1_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
 // loss) compile once, beside the tagging path.  Each step is a sequence of named stages (the static functions below, in the
 // order they run); what both steps share on the host side is in train_host.hip.h.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "train_max.hip.h"
 #include "onehot_train_max.hip.h"
 #include "fst4_train.hip.h"
+#include "ind1_train.hip.h"
 #include "optim.hip.h"
 
 using namespace farnn;
@@ -843,6 +844,181 @@ extern "C" int farnn_fst4_train_step(farnn_fst4_train_ctx *c, const farnn_fst4_t
     if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
         (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
         (rc = t.dM_words()) || (rc = t.scores<2>()) || (rc = t.wildcard())) return rc;
+    FARNN_HIP_TRY(hipGetLastError());
+    c->prof.end(t.s);
+    return FARNN_OK;
+}
+
+// ---- training step of the onehot independent=1 model (FARNN_S_O_I; ind1_train.hip.h) ----------------------
+struct farnn_ind1_train_ctx {
+    farnn_ind1_train_dims d;
+    int device = 0;
+    DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, Mc / McT / dMc, the partials
+    DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
+    StepProfile prof;
+    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
+};
+
+extern "C" int farnn_ind1_train_create(const farnn_ind1_train_dims *d, int device, farnn_ind1_train_ctx **out) {
+    if (!d || !out) return fail(FARNN_EINVAL, "ind1_train_create: null argument%s%s");
+    *out = nullptr;
+    if (d->V <= 0 || d->S <= 0 || d->C <= 0) return fail(FARNN_EINVAL, "ind1_train_create: bad dimensions%s%s");
+    if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "ind1_train_create: more than 128 states%s%s");
+    // fst4_loss_kernel keeps two score vectors per wavefront in LDS (fst4_loss_lds_bytes): C <= 2400
+    if (fst4_loss_lds_bytes(d->C) > 150 * 1024) return fail(FARNN_ERANGE, "ind1_train_create: too many score columns%s%s");
+    int rc;
+    if ((rc = select_device(device))) return rc;
+    farnn_ind1_train_ctx *c = new farnn_ind1_train_ctx();
+    c->d = *d; c->device = device;
+    if (!c->err.create()) { farnn_ind1_train_destroy(c); return fail(FARNN_ENOMEM, "ind1_train_create: out of memory%s%s"); }
+    *out = c;
+    return FARNN_OK;
+}
+
+extern "C" void farnn_ind1_train_destroy(farnn_ind1_train_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    delete c;
+}
+
+extern "C" int farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *c, int32_t enable) {
+    if (!c) return fail(FARNN_EINVAL, "ind1_train_set_profiling: null context%s%s");
+    c->prof.enabled = enable;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_ind1_train_time(farnn_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
+    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "ind1_train_time: null argument%s%s");
+    return c->prof.time(c->device, total_ms, steps);
+}
+
+// One step: the plan (ind1_plan: sizes from the dimensions alone) and what the stages hand on
+struct Ind1Step {
+    int B, L, ngrp, cpg;          // label groups per word of the score kernel's MODE 0 and 1, label columns per group
+    size_t S, K, V, N1, N0;
+    unsigned lgrid;               // workgroups of the loss kernel
+    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_ind1_ws / carve_ind1_ints
+    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
+    farnn_ind1_train_ctx *c; const farnn_ind1_train_weights *w; const farnn_ind1_train_outputs *o; hipStream_t s;
+    OhTrainParams q;
+    Ind1TrainParams f;
+    float *SC, *DS, *M, *MT, *dM, *Osum, *ones, *loss_part, *partial, *part;
+    Buckets bk;
+    int carve(const int64_t *x, const int64_t *lengths);
+    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words();
+    template <int MODE> int scores();
+};
+
+static size_t carve_ind1_ws(float *base, Ind1Step &t) {
+    Carver<float> a(base);
+    const size_t nS = t.N1 * t.S, SS = t.S * t.S;
+    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
+    t.SC = a.take(t.N0 * t.K); t.DS = a.take(t.N0 * t.K);
+    t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS);
+    t.Osum = a.take((SS + 3) & ~(size_t)3);
+    t.ones = a.take((t.S + 3) & ~(size_t)3);
+    t.loss_part = a.take((size_t)t.lgrid * 8);
+    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dMc: partial tiles of the words with several runs
+    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and label group
+    return a.off;
+}
+static size_t carve_ind1_ints(int *base, Ind1Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
+
+// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
+static int ind1_plan(const farnn_ind1_train_ctx *c, int B, int L, Ind1Step &t) {
+    // positions are 32-bit flat indices b L + i in the bucketing, dMc and score kernels
+    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "ind1_train_step: B (L+1) must stay below 2^30%s%s");
+    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
+    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
+    // a word's label columns are split over enough workgroups to fill the chip when the batch has few distinct words
+    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.K, (size_t)F4_MAX_GROUPS});
+    t.cpg = (int)((t.K + want - 1) / want); t.ngrp = (int)((t.K + t.cpg - 1) / t.cpg);
+    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
+    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
+    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
+    t.lds_tok = (size_t)(L + 1) * sizeof(int);
+    t.lds_sc = ind1_train_lds_floats(SP, CPR, GW) * sizeof(float);
+    t.lds_loss = fst4_loss_lds_bytes(t.K);
+    t.need = carve_ind1_ws(nullptr, t); t.ineed = carve_ind1_ints(nullptr, t);
+    int rc;
+    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
+    return lds_fits(t.lds_loss);
+}
+// Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
+int Ind1Step::carve(const int64_t *x, const int64_t *lengths) {
+    int rc;
+    if ((rc = c->ws.ensure(need, "ind1_train_step: out of device memory for the workspace%s%s")) ||
+        (rc = c->iws.ensure(ineed, "ind1_train_step: out of device memory for the index workspace%s%s"))) return rc;
+    [[maybe_unused]] const size_t carved = carve_ind1_ws(c->ws.p, *this), icarved = carve_ind1_ints(c->iws.p, *this);
+    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
+    // the chains always use relu (model_onehot.py:266, :278); the output mask is premixed into Mc: a mask of ones
+    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
+    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = FARNN_NL_RELU;
+    f.T = w->T; f.W = w->W; f.O = w->O; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
+    f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
+    f.SC = SC; f.DS = DS; f.part = part; f.dMc = dM; f.Osum = Osum; f.dT = o->dT;
+    f.L = L; f.S = (int)S; f.C = (int)K; f.cpg = cpg; f.ngrp = ngrp; f.mask = c->d.mask_by_output != 0;
+    return FARNN_OK;
+}
+// Stages 4 and 5: the positions bucketed by word; with the mask Osum = output_tensor.sum(0); Mc[w] = (T[w] + W) (* Osum) and its
+// transpose for the words of the batch only (the bucket counts say which: the blocks of the other words are never read)
+int Ind1Step::prepare() {
+    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
+    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    const unsigned nt = (unsigned)((S + 31) / 32);
+    if (f.mask) fst4_premix_kernel<<<dim3(1, nt * nt), 256, 0, s>>>(w->O, nullptr, nullptr, Osum, nullptr, (int)S, (int)K);
+    ind1_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(w->T, w->W, f.mask ? Osum : nullptr, bk.wcount, M, MT, (int)S);
+    return FARNN_OK;
+}
+// Stages 7, 9 and 12: the score kernel in bucket order (MODE 0: the scores, 1: the partials of d alpha / d beta, 2: dT, all the
+// labels of a word in one workgroup); register rows per thread by S
+template <int MODE>
+int Ind1Step::scores() {
+    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
+    auto go = [&](auto RPT) {
+        return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, MODE == 2 ? 1 : ngrp), I1_THREADS, lds_sc, s, f);
+    };
+    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
+                                                                                                             : go(int_c<16>());
+}
+// Stage 8: priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront partials
+int Ind1Step::loss(const int64_t *labels, int64_t valid_tokens) {
+    if (int rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
+                        (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens)) return rc;
+    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    return FARNN_OK;
+}
+// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the label groups' partials added in group order
+int Ind1Step::adjoints() {
+    if (int rc = scores<1>()) return rc;
+    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
+    return FARNN_OK;
+}
+// Stage 11: dMc[w] of the chains, the i-FST step's per-word reduction
+int Ind1Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
+
+extern "C" int farnn_ind1_train_step(farnn_ind1_train_ctx *c, const farnn_ind1_train_weights *w, const int64_t *x,
+                                     const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                     int64_t valid_tokens, const farnn_ind1_train_outputs *o, void *stream) {
+    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "ind1_train_step: null argument%s%s");
+    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "ind1_train_step: null weight%s%s");
+    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "ind1_train_step: null output%s%s");
+    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "ind1_train_step: B, L and valid_tokens must be positive%s%s");
+    Ind1Step t = {};
+    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
+    int rc, bad = 0;
+    if ((rc = ind1_plan(c, B, L, t))) return rc;
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->err.take(t.s, &bad))) return rc;
+    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "ind1_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
+                                                 : "ind1_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
+    if ((rc = t.carve(x, lengths))) return rc;
+    StepProfile::Guard timing = c->prof.begin(t.s);
+    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
+        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
+        (rc = t.dM_words()) || (rc = t.scores<2>())) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     c->prof.end(t.s);
     return FARNN_OK;

@@ -418,6 +418,115 @@ class FARNN_S_O_I(_OnehotBase):
             mask_by_output=(a.independent == 2), threshold=a.threshold, o_idx=self.o_idx,
             device=self.device_index)
 
+    def _dense(self):
+        """language_tensor / wildcard_mat / output_tensor of an edge-built model, on demand (enable_training, state_dict):
+        what the edge-built handle scatters.  A class edge with no member in the vocabulary (word -2) keeps its label in
+        output_tensor and writes nothing into language_tensor."""
+        word, frm, to, label = self.edges
+        T = np.zeros((self.V, self.S, self.S), np.float32)
+        W = np.zeros((self.S, self.S), np.float32)
+        O = np.zeros((self.C, self.S, self.S), np.float32)
+        lang = word >= 0
+        T[word[lang], frm[lang], to[lang]] = 1
+        wild = word == -1
+        W[frm[wild], to[wild]] = 1
+        has = label >= 0
+        O[label[has], frm[has], to[has]] = 1
+        return T, W, O
+
+    # ---- training step (reference :229-306 with train=True + train_onehot.py:156-206; DESIGN.md, row f8) ----
+    @staticmethod
+    def _ind1_train_enabled():
+        """RE2NN_ONEHOT_IND1_TRAIN=1: this model's training step (opt-in for its first release, as RE2NN_ONEHOT_FST_TRAIN)"""
+        return os.environ.get('RE2NN_ONEHOT_IND1_TRAIN', '') == '1'
+
+    def _check_trainable(self):
+        """The cases the HIP training step does not cover, refused before any device work."""
+        if not self._ind1_train_enabled():            # before self.args is touched: the refusal needs the type only
+            from ..train_onehot import no_training_step
+            raise no_training_step(self)              # today's refusal, word for word
+        a = self.args
+        if a.train_mode != 'sum':
+            raise NotImplementedError('training the onehot independent=1 model covers the sum semiring only, --train_mode {} '
+                                      'was asked for (DESIGN.md, row f8)'.format(a.train_mode))
+        if a.local_loss_func != 'CE1':
+            raise NotImplementedError('training the onehot independent=1 model covers the CE1 loss only (main.py:127)')
+        from ..dist import world
+        if world()[1] > 1:
+            raise NotImplementedError('multi-GPU data-parallel training of the onehot independent=1 model is not built; '
+                                      'train on one GPU (DESIGN.md, row f8)')
+
+    def enable_training(self):
+        """Device-resident tensors (language_tensor the only one with requires_grad, as in the reference :209-223) and the
+        library context.  An edge-built model gets its dense tensors here (_dense())."""
+        self._check_trainable()
+        if getattr(self, '_tp', None) is not None:
+            return self
+        if not torch.cuda.is_available():
+            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
+        dev = self._dev()
+        sd = self.state_dict()
+        self._tp = {}
+        for k in ('language_tensor', 'wildcard_mat', 'output_tensor', 'h0', 'hT'):
+            t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).clone()
+            self._tp[k] = t.requires_grad_(k == 'language_tensor')
+        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
+            if self.args.use_priority else None
+        V = self._tp['language_tensor'].shape[0]
+        self._tc = _lib.Ind1TrainContext(V, self.S, self.C, mask_by_output=(self.args.independent == 2),
+                                         threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index)
+        self._dirty = False
+        return self
+
+    def parameters(self):
+        tp = getattr(self, '_tp', None)
+        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+
+    def named_parameters(self):
+        tp = getattr(self, '_tp', None)
+        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
+
+    def sync_from_training(self):
+        """Copy the trained language_tensor back into the host attributes the tagging handle is built from.  An
+        edge-built model becomes a dense one (its edges no longer describe the weights)."""
+        tp = getattr(self, '_tp', None)
+        if tp is None or not self._dirty:
+            return
+        if getattr(self, 'edges', None) is not None:
+            self.language_tensor, self.wildcard_mat, self.output_tensor = self._dense()
+            self.output_wildcard_mat = None
+            self.edges = None
+        self.language_tensor = tp['language_tensor'].detach().cpu().numpy()
+        self._dirty = False
+        self.invalidate()
+
+    def eval(self):
+        self.sync_from_training()
+        return super().eval()
+
+    def forward_local(self, input, label, lengths, train=True, re_tags=None):
+        if not train:
+            self.sync_from_training()
+            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
+        from .train_step import onehot_ind1_train_step
+        self.enable_training()
+        tp = self._tp
+        on_host = lengths.device.type == 'cpu'
+        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
+        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
+        x = input[:, :Lmax]
+        lab = label[:, :Lmax]
+        loss, tags = onehot_ind1_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_tensor'],
+                                            tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
+        self._dirty = True
+        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
+        true = self._flatten(label, lengths).to(input.device)
+        return loss, pred, true
+
     def state_dict(self):
+        self.sync_from_training()
+        if getattr(self, 'edges', None) is not None:
+            T, W, O = self._dense()
+            return {'h0': self.h0, 'hT': self.hT, 'language_tensor': T, 'wildcard_mat': W, 'output_tensor': O}
         return {'h0': self.h0, 'hT': self.hT, 'language_tensor': self.language_tensor,
                 'wildcard_mat': self.wildcard_mat, 'output_tensor': self.output_tensor}

@@ -1,5 +1,5 @@
 """The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step,
-farnn_onehot_ifst_train_step and farnn_fst4_train_step (include/farnn.h).
+farnn_onehot_ifst_train_step, farnn_fst4_train_step and farnn_ind1_train_step (include/farnn.h).
 
 What the reference does in FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
 (model_decompose_single.py:207-304, train_decompose.py:186-190) is split like this: the word table
@@ -18,6 +18,9 @@ language_tensor: one library call computes the loss, the tags and d loss / d lan
 
 The onehot FST (FARNN_S_O, model_onehot.py:66-146) trains language_tensor [V,C,S,S] and, with
 --train_wildcard, wildcard_tensor [C,S,S]: again one library call.
+
+The onehot independent=1 model (FARNN_S_O_I, model_onehot.py:184-306) trains language_tensor [V,S,S]
+only: one library call.
 """
 import torch
 
@@ -160,3 +163,33 @@ def onehot_fst4_train_step(tc, T4, W4, h0, hT, P, x, lengths, labels, valid_toke
     """Returns (loss scalar tensor with grad towards T4 and, if it requires grad, W4; tags int32 [B,L] with -1 at pads).
     h0, hT and P are read but receive no gradient (model_onehot.py:32-33)."""
     return _OnehotFst4TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, h0, hT, T4, W4)
+
+
+class _OnehotInd1TrainStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T, ntok, x, lengths, labels)
+        B, L = x.shape
+        ws = {n: _f32(t) for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
+        Pc = _f32(P)
+        dT = torch.empty_like(ws['T'])
+        weights = {n: t.data_ptr() for n, t in ws.items()}
+        weights['P'] = None if Pc is None else Pc.data_ptr()
+        outputs = {'loss': loss.data_ptr(), 'dT': dT.data_ptr(), 'tags': tags.data_ptr()}
+        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
+                torch.cuda.current_stream(dev).cuda_stream)
+        ctx.save_for_backward(dT)
+        ctx.mark_non_differentiable(tags)
+        return loss.reshape(()), tags
+
+    @staticmethod
+    def backward(ctx, gloss, _gtags):
+        dT, = ctx.saved_tensors
+        return (None,) * 10 + (dT * gloss,)
+
+
+def onehot_ind1_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens=None):
+    """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W [S,S], O [C,S,S], h0, hT and
+    P are read but receive no gradient (the reference's requires_grad=False, model_onehot.py:209-223).  Whether the chains
+    run on (T + W) * O.sum(0) (args.independent == 2) is the context's mask_by_output."""
+    return _OnehotInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)

@@ -1,8 +1,9 @@
 """``--method onehot`` driver (reference src_seq/train_onehot.py:20-154: data, automaton ->
 tensors -> model, INIT evaluation on train/dev/test, `.res` record).  The epoch loop of the
 reference (:156-206, backward pass + Adam) runs for the i-FST (``--independent 2``, sum semiring,
-no CRF extension) on the HIP training step and, with RE2NN_ONEHOT_FST_TRAIN=1, for the FST
-(``--independent 0``, row f7); for the other onehot models a positive epoch count is refused before any device work."""
+no CRF extension) on the HIP training step and, opt-in, for the FST (``--independent 0``,
+RE2NN_ONEHOT_FST_TRAIN=1, row f7) and the independent=1 model (``--independent 1``, RE2NN_ONEHOT_IND1_TRAIN=1, row f8);
+otherwise a positive epoch count is refused before any device work."""
 from .create_logic_mat_bias import create_mat_priority_MITR
 from .data import SlotBatchDataset, iter_batches, load_slot_dataset
 from .RE import build_onehot_model
@@ -54,7 +55,8 @@ def init_evaluation(model, splits, args, s2i, i2s, logger, model_dir='../model_s
 
 
 def no_training_step(model):
-    """The refusal of a model without a training step (also the onehot FST's without its opt-in: model_onehot.FARNN_S_O)."""
+    """The refusal of a model without a training step (also the onehot FST's and the independent=1 model's without their
+    opt-ins: model_onehot.FARNN_S_O, FARNN_S_O_I)."""
     return NotImplementedError(
         'training epochs are implemented for the i-FST models only (--independent 2: --method decompose, DESIGN.md '
         'row f3, and --method onehot, row f5); {} has no training step, run it with --epoch 0'.format(type(model).__name__))
@@ -64,9 +66,9 @@ def check_trainable(model):
     """Refuses a model the HIP training step does not cover (raises NotImplementedError; no device work)."""
     if not hasattr(model, 'enable_training'):
         raise no_training_step(model)
-    from .farnn.model_onehot import FARNN_S_O, FARNN_S_O_I_S
-    if isinstance(model, (FARNN_S_O, FARNN_S_O_I_S)):
-        model._check_trainable()                  # max semiring, CRF extension, several GPUs; the FST without its opt-in
+    from .farnn.model_onehot import FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S
+    if isinstance(model, (FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S)):
+        model._check_trainable()                  # max semiring, CRF extension, several GPUs; a model without its opt-in
 
 
 def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
