@@ -35,7 +35,7 @@
 
 namespace farnn {
 
-// What a compute wavefront carries from its priming (before the workgroup's set-up barrier) into the step loop
+// What a compute wavefront carries from its priming into the step loop
 // H16: the ring holds the block's 16-bit image (layout.hip.h, half_image_kernel): TWO 16-byte chunks per lane and step, each the
 // f16 values of two of the lane's four f32 chunks -- half the load instructions and half the bytes of a step
 template <int D, int LPR, bool H16 = false>
@@ -86,10 +86,13 @@ __device__ __forceinline__ void dest_lane(const int lane, int &rj, int &rs, bool
                          : "v"(ring_.voff[0]), "v"(ring_.voff[1]), "v"(ring_.voff[2]), "v"(ring_.voff[3]), "s"(bp_)); \
     } while (0)
 
-// PRIMING, before the workgroup's set-up barrier (round 5, the review's "hide the set-up under the first block loads"): the block
-// offsets of the first 64 steps straight from the token ids in global memory (the set-up writes them to LDS for the later windows
-// and for nobody's first loads), and the first D steps' pieces requested -- an L2 / Infinity-Cache round trip at the launch's start,
-// when all 512 workgroups ask at once, that used to begin only behind the barrier.
+// PRIMING: the block offsets of the first 64 steps straight from the token ids in global memory (the set-up writes them to LDS for
+// the later windows and for nobody's first loads -- for a sequence of at most 64 steps not at all), and the first D steps' pieces
+// requested -- an L2 / Infinity-Cache round trip at the launch's start, when all 512 workgroups ask at once.
+// Where it runs: in the launch that scores beside the recurrence, before the set-up (round 5, "hide the set-up under the first
+// block loads"; that set-up's __syncthreads() then waits for the pieces).  In the recurrence-only launch (chain_regs_body, HEAD) the
+// set-up has no part left that depends on the sequence -- it is stored while wavefront 0 selects -- so the priming runs BEHIND the
+// one LDS-only barrier, as the first thing that knows (b, len): nothing in front of step 0 drains vmcnt with the ring in flight.
 template <int D, int LPR, bool H16>
 __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int dir, const int w, const int lane, const int nsteps,
                                                 const int len, const int b, DestRing<D, LPR, H16> &ring) {

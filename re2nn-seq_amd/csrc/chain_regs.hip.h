@@ -50,6 +50,9 @@
 #ifndef FARNN_ABLATE
 #define FARNN_ABLATE 0       /* timing-only ablation builds set bits; the shipped library is built with 0 */
 #endif
+#ifndef FARNN_CHAIN_HEAD
+#define FARNN_CHAIN_HEAD 1   /* 0: a variant build for A/B runs -- every form keeps the head with the selection in front of the set-up */
+#endif
 
 namespace farnn {
 
@@ -109,9 +112,15 @@ constexpr int WG_STAMP_MAX = 4096;
 __device__ long long g_wg_stamps[16 * WG_STAMP_MAX];    // FARNN_DBG & 2048 (chain_regs_kernel): {seq, len, start, end, cycles, xcc, se, cu,
                                                         //  setup, chain, scorer done - chain end, meeting - chain end, tiles + arrival} per workgroup
 #define FARNN_RG_STAMP(i) do { if (probe && lane == 0) stamps[i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+// ... and of the recurrence-only launch's head and tail (FARNN_DBG & 2048; slots 8 .. 13 of the workgroup's sixteen): entry, selection
+// done, set-up barrier passed, first step about to start (ring primed), chain end, writer drained -- each straight to the buffer
+// from the wavefront that passes the point (no barrier to collect them)
+#define FARNN_HD_STAMP(i) do { if (!SCORE && quiet && lane == 0 && item < WG_STAMP_MAX) g_wg_stamps[16 * (long long)item + 8 + (i)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define FARNN_RG_STAMP(i) do { } while (0)
+#define FARNN_HD_STAMP(i) do { } while (0)
 #endif
+constexpr int RGM_SEL = 30;      // misc[30], misc[31]: {sequence, length} from the selecting wavefront (beside.hip.h's RGM_* end at 22)
 
 // The kernel's body as a function of (LDS base, thread index 0..511, item = 2 * launch slot + direction): chain_regs_kernel runs
 // it on one workgroup per item; chain_viterbi_kernel (chain_viterbi.hip) runs the two directions of a sequence as the two
@@ -143,50 +152,109 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
     float *ab = smem + lds.ab, *scl = smem + lds.scl, *obuf = smem + lds.obuf;
     int *misc = reinterpret_cast<int *>(smem + lds.misc);
 
-    int b = p.order ? p.order[slot] : slot;
-    // (a compute unit holds two workgroups of the narrow form: slots i and i + B/2 pair a long with a short sequence; it holds ONE
-    //  of the wide form, and workgroups start in slot order as compute units fall free: longest first)
-    int len_sel = -1;
-    if (p.sort) b = select_by_length_rank(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, reinterpret_cast<int *>(hist), tid, nthreads, &len_sel);
-    if (b_out) *b_out = b;
-    const int len = len_sel >= 0 ? len_sel : clamp_len(p.len[b], p.L);      // (the selection hands the length back: no len[b] load behind it)
-    const int nsteps = p.full ? p.L : len;
+    // HEAD (the destination split's recurrence-only launch, f16 and f32): the selection runs BESIDE the set-up, and ONE LDS-only
+    // barrier stands in front of step 0.  The other forms keep the head below.
+    constexpr bool HEAD = DEST && !SCORE && (FARNN_CHAIN_HEAD != 0);
+    int b, len;
     const float *hinit = dir == 0 ? p.h0 : p.hT;
 #if defined(FARNN_PROBES)
     __shared__ long long stamps[8];
     const bool quiet = (p.dbg & 2048) != 0;                               // 2048: every workgroup stamps, nobody prints (g_wg_stamps)
+    if (w == 0) { if (lane == 0) stamps[0] = (long long)__builtin_amdgcn_s_memtime(); FARNN_HD_STAMP(0); }
+#endif
+    DestRing<RD_D, RD_LPR, H16> dring;
+    if constexpr (HEAD) {
+        if (w == 0) {
+            // wavefront 0: the sequence and its length (launch_order.hip.h), in registers; two words of `misc` hand them on
+            int bb = p.order ? p.order[slot] : slot, ll = -1;
+            if (p.sort) bb = select_by_length_rank_one_wave(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, lane, &ll);
+            if (ll < 0) ll = clamp_len(p.len[bb], p.L);
+            if (lane == 0) { misc[RGM_SEL] = bb; misc[RGM_SEL + 1] = ll; }
+            FARNN_HD_STAMP(1);
+        } else {
+            // wavefronts 1 .. 7 meanwhile: everything that depends on neither.  Every word has ONE store, from one wavefront.
+            // Of `hist` only what is read before it is written: row 0, and the pad columns S .. SP - 1 of rows 1 .. L (the compute
+            // lanes write every column below S of a row they finish; the writer copies whole SP-wide rows, and the stash's readers
+            // take the pads as exact zeros).  At most three words a row, at S not a multiple of four: nothing wider than a dword fits.
+            const int t = tid - 64;
+            constexpr int nt = nthreads - 64;
+            for (int j = t; j < SP; j += nt) {
+                ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
+                hist[j] = (j < S) ? hinit[j] : 0.0f;
+            }
+            const int npad = SP - S;
+            for (int j = t; j < p.L * npad; j += nt) {
+                const int r = j / npad;
+                hist[(r + 1) * SP + S + (j - r * npad)] = 0.0f;
+            }
+            if (t < RGM_SEL) misc[t] = t == RGM_ACQ ? -1 : 0;
+            if (t < 2) part[t * PSTR + PSTR - 1] = 0.0f;                        // the reduction's identity (masked reads)
+            if (t < 2 * 4 * RG_NWC) {                                           // the step flags: 1 = "row 0 is there", buffer 0 only
+                const int fb = t / (4 * RG_NWC), fk = t % (4 * RG_NWC);
+                part[fb * PSTR + NP * PS + fk] = (fb == 0 && (fk & 3) == 0) ? __int_as_float(1) : 0.0f;
+            }
+            // exchange row 0 = the initial state (scaled by o for the backward chain, model_onehot.py:393), zeros behind S and in row 1
+            for (int j = t; j < 2 * RD_XS; j += nt)
+                smem[lds.xd + j] = j < S ? hinit[j] * ((dir == 1 && p.o) ? p.o[j] : 1.0f) : 0.0f;
+        }
+        wg_barrier_lds();                                // the ONE barrier in front of step 0: LDS traffic only, nothing of the ring is in flight yet
+        b = __builtin_amdgcn_readfirstlane(misc[RGM_SEL]);
+        len = __builtin_amdgcn_readfirstlane(misc[RGM_SEL + 1]);
+        if (b_out) *b_out = b;
+        // the block offsets in LDS feed the address windows BEHIND the first (chain_dest.hip.h, FARNN_RD_WINDOW): a sequence of at most
+        // 64 steps never reads them.  A longer one fills them as before, in front of a barrier of its own, before anything is primed.
+        if ((p.full ? p.L : len) > 64) {
+            const int ns = p.full ? p.L : len;
+            for (int k = tid; k < ns; k += nthreads) {
+                const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
+                tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
+            }
+            wg_barrier_lds();
+        }
+    } else {
+        b = p.order ? p.order[slot] : slot;
+        // (a compute unit holds two workgroups of the narrow form: slots i and i + B/2 pair a long with a short sequence; it holds ONE
+        //  of the wide form, and workgroups start in slot order as compute units fall free: longest first)
+        int len_sel = -1;
+        if (p.sort) b = select_by_length_rank(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, reinterpret_cast<int *>(hist), tid, nthreads, &len_sel);
+        if (b_out) *b_out = b;
+        len = len_sel >= 0 ? len_sel : clamp_len(p.len[b], p.L);      // (the selection hands the length back: no len[b] load behind it)
+        if (w == 0) FARNN_HD_STAMP(1);
+    }
+    const int nsteps = p.full ? p.L : len;
+#if defined(FARNN_PROBES)
     const bool probe = ((p.dbg & 32768) && nsteps == p.L && p.L >= 32) || quiet;   // 32768: the full-length workgroups print their timeline
                                                                                    // (off by default: the A/B build is also what the A/B forms are timed with)
-    if (w == 0) FARNN_RG_STAMP(0);
 #endif
 
     // (destination split: the compute wavefronts request their first blocks BEFORE the set-up -- chain_dest.hip.h, regs_dest_prime)
     // (not in the instantiation that carries the matrix-core tile code: with the ring live across the set-up it spilled 20 VGPRs)
-    constexpr bool PRIME_EARLY = DEST && (!SCORE || LMO);
-    DestRing<RD_D, RD_LPR, H16> dring;
+    constexpr bool PRIME_EARLY = DEST && (!SCORE || LMO) && !HEAD;     // (HEAD primes behind its one barrier, below)
     if constexpr (PRIME_EARLY)
         if (w < RG_NWC && nsteps > 0) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
-    // ---- set-up ----------------------------------------------------------------------------------------------------------
-    for (int k = tid; k < nsteps; k += nthreads) {
-        const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
-        tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
+    if constexpr (!HEAD) {
+        // ---- set-up ----------------------------------------------------------------------------------------------------------
+        for (int k = tid; k < nsteps; k += nthreads) {
+            const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
+            tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
+        }
+        for (int j = tid; j < SP; j += nthreads) ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
+        for (int j = tid; j < (nsteps + 1) * SP; j += nthreads) hist[j] = (j < S) ? hinit[j] : 0.0f;     // row 0; pad columns zero
+        if (tid < 32) misc[tid] = tid == RGM_ACQ ? -1 : 0;
+        if (tid < 2) part[tid * PSTR + PSTR - 1] = MAXSR ? -INFINITY : 0.0f;     // the reduction's identity (masked reads)
+        if (tid < 2 * 4 * RG_NWC) {                     // the step flags (DEST, chain_dest.hip.h: a flag of 1 = "row 0 is there", buffer 0 only)
+            const int fb = tid / (4 * RG_NWC), fk = tid % (4 * RG_NWC);
+            part[fb * PSTR + NP * PS + fk] = (DEST && fb == 0 && (fk & 3) == 0) ? __int_as_float(1) : 0.0f;
+        }
+        if constexpr (DEST) {
+            // exchange row 0 = the initial state (scaled by o for the backward chain, model_onehot.py:393), zeros behind S and in row 1
+            for (int j = tid; j < 2 * RD_XS; j += nthreads)
+                smem[lds.xd + j] = j < S ? hinit[j] * ((dir == 1 && p.o) ? p.o[j] : 1.0f) : 0.0f;
+        }
+        if (WIDE && tid < RG_NWC * RGW_XCH) smem[lds.xch + tid] = 0.0f;          // exchange slots without a row stay exact zeros
+        __syncthreads();
     }
-    for (int j = tid; j < SP; j += nthreads) ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
-    for (int j = tid; j < (nsteps + 1) * SP; j += nthreads) hist[j] = (j < S) ? hinit[j] : 0.0f;     // row 0; pad columns zero
-    if (tid < 32) misc[tid] = tid == RGM_ACQ ? -1 : 0;
-    if (tid < 2) part[tid * PSTR + PSTR - 1] = MAXSR ? -INFINITY : 0.0f;     // the reduction's identity (masked reads)
-    if (tid < 2 * 4 * RG_NWC) {                     // the step flags (DEST, chain_dest.hip.h: a flag of 1 = "row 0 is there", buffer 0 only)
-        const int fb = tid / (4 * RG_NWC), fk = tid % (4 * RG_NWC);
-        part[fb * PSTR + NP * PS + fk] = (DEST && fb == 0 && (fk & 3) == 0) ? __int_as_float(1) : 0.0f;
-    }
-    if constexpr (DEST) {
-        // exchange row 0 = the initial state (scaled by o for the backward chain, model_onehot.py:393), zeros behind S and in row 1
-        for (int j = tid; j < 2 * RD_XS; j += nthreads)
-            smem[lds.xd + j] = j < S ? hinit[j] * ((dir == 1 && p.o) ? p.o[j] : 1.0f) : 0.0f;
-    }
-    if (WIDE && tid < RG_NWC * RGW_XCH) smem[lds.xch + tid] = 0.0f;          // exchange slots without a row stay exact zeros
-    __syncthreads();
-    if (w == 0) FARNN_RG_STAMP(1);
+    if (w == 0) { FARNN_RG_STAMP(1); FARNN_HD_STAMP(2); }
 #if FARNN_ABLATE & 256                               /* 256 = set-up only */
     return;
 #endif
@@ -231,9 +299,10 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
                 const bool probe_ = false;
 #endif
                 if constexpr (!PRIME_EARLY) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
+                if (w == 0) FARNN_HD_STAMP(3);
                 regs_compute_dest<NLX, RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, smem + lds.xd, probe_, b, dring);
                 __builtin_amdgcn_s_setprio(0);
-                if (w == 0) FARNN_RG_STAMP(2);
+                if (w == 0) { FARNN_RG_STAMP(2); FARNN_HD_STAMP(4); }
 #if defined(FARNN_PROBES)
                 if (!SCORE && probe && !quiet && w == 0 && lane == 0)
                     printf("seq %d dir %d (destination split): setup %lld, chain %lld (%lld per step)\n", b, dir, stamps[1] - stamps[0], stamps[2] - stamps[1],
@@ -544,6 +613,9 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+#if defined(FARNN_PROBES)
+        if (!SCORE && quiet) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); FARNN_HD_STAMP(5); }     // the last rows have left
+#endif
     } else if (SCORE) {
         // =================================================================================================================
         // scorer wavefront: tiles of this workgroup's half, while the chain runs

@@ -901,4 +901,12 @@ extern "C" int farnn_debug_ct_stamps(long long *out, int n_workgroups) {
     if (hipDeviceSynchronize() != hipSuccess) return FARNN_EIO;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(farnn::g_ct_stamps), sizeof(long long) * 16 * (size_t)n_workgroups) == hipSuccess ? FARNN_OK : FARNN_EIO;
 }
+// ... the state stash of the handle's last call, as it lies in the workspace: `n` floats each of A (forward) and Bk (backward),
+// [B][L + 1][SP] of that call (tests/test_gpu_chain_head.py reads the pad columns S .. SP - 1 back)
+extern "C" int farnn_debug_stash(farnn_model *m, float *A_out, float *Bk_out, long long n) {
+    if (!m || !A_out || !Bk_out || n < 0 || !m->ws.A || !m->ws.Bk) return FARNN_EINVAL;
+    if (hipDeviceSynchronize() != hipSuccess) return FARNN_EIO;
+    if (hipMemcpy(A_out, m->ws.A, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return FARNN_EIO;
+    return hipMemcpy(Bk_out, m->ws.Bk, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess ? FARNN_OK : FARNN_EIO;
+}
 #endif

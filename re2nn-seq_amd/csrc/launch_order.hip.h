@@ -58,6 +58,15 @@ __device__ __forceinline__ int select_by_length_rank_wave(const int64_t *len, in
     return res;
 }
 
+// The selection as ONE wavefront runs it, whatever the batch size (B <= 1024): every lane of the calling wavefront gets the sequence
+// and, through len_out, its clamped length.  No LDS and no barrier in here: chain_regs_body's recurrence-only destination-split
+// launch calls it on wavefront 0 WHILE the other wavefronts store the set-up, and hands the pair on through two words of LDS.
+__device__ __forceinline__ int select_by_length_rank_one_wave(const int64_t *len, int B, int L, int rank, int lane, int *len_out) {
+    if (B <= 256) return select_by_length_rank_wave<4>(len, B, L, rank, lane, len_out);
+    if (B <= 512) return select_by_length_rank_wave<8>(len, B, L, rank, lane, len_out);
+    return select_by_length_rank_wave<16>(len, B, L, rank, lane, len_out);          // B <= 1024
+}
+
 // len_out (optional): the selected sequence's clamped length comes back with it -- the class the search found -- so the caller
 // need not load len[b] behind the selection (a dependent global round trip at the launch's start, when every workgroup loads).
 // LDS_ONLY: the two workgroup barriers order LDS traffic only (wg_barrier_lds) -- a __syncthreads() also drains the vector-memory
@@ -68,10 +77,8 @@ __device__ __forceinline__ int select_by_length_rank(const int64_t *len, int B, 
                                                      int tid, int /*nthreads*/, int *len_out = nullptr) {
     if ((tid >> 6) == 0) {
         const int lane = tid & 63;
-        int res, cls = 0;
-        if (B <= 256) res = select_by_length_rank_wave<4>(len, B, L, rank, lane, &cls);
-        else if (B <= 512) res = select_by_length_rank_wave<8>(len, B, L, rank, lane, &cls);
-        else res = select_by_length_rank_wave<16>(len, B, L, rank, lane, &cls);       // B <= 1024
+        int cls = 0;
+        const int res = select_by_length_rank_one_wave(len, B, L, rank, lane, &cls);
         if (lane == 0) { scratch[0] = res; scratch[1] = cls; }
     }
     if constexpr (LDS_ONLY) wg_barrier_lds(); else __syncthreads();
