@@ -554,6 +554,62 @@ int  farnn_ind1_train_step(farnn_ind1_train_ctx *ctx, const farnn_ind1_train_wei
 int  farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_ind1_train_time(farnn_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);
 
+/* ---- training step of the decomposed independent=1 model (FARNN_S_D_W_I, --method decompose --independent 1) ---
+ * Replaces FARNN_S_D_W_I.forward_local(train=True) + loss.backward() (model_decompose_independent.py:219-300,
+ * train_decompose.py:161-221) for farnn = 0, the sum semiring and the CE1 loss, no CRF.  With v = Vgen[w]
+ * (model_decompose.py:222-241): N[w] = sum_r v_r S1[:,r] S2[:,r]^T + wildcard_mat (:171-173);
+ * Osum = sum_r (sum_c C_output[c,r]) S1_output[:,r] S2_output[:,r]^T (:210-214; wildcard_output is not read under CE1);
+ * Mc[w] = N[w] * Osum (:174); both chains run on Mc with update_nonlinear (:176-188, :239-252);
+ * br_i[r] = sum_{ij} alpha_i[i] beta_{i+1}[j] N[x_i][i,j] S1_output[i,r] S2_output[j,r] with alpha_i the state BEFORE token i and
+ * N, not Mc; score_i = br_i C_output^T [. P] (:199-208, :260-278); the loss is the cross-entropy, mean over the valid
+ * tokens (:295); the tags are local_decode's (:298).  Every gradient output is written in full; dVgen's rows of words absent
+ * from the batch are zero.
+ * Limits: S <= 128 (the chains' kernels, as farnn_onehot_train_create), C <= 2400 (the loss kernel keeps two score vectors per
+ * wavefront within 150 KiB of LDS), R S S and R_O S S below 2^31 (farnn_decomp_ind1_train_create returns FARNN_ERANGE outside,
+ * naming the quantity), B (L + 1) < 2^30 (the step returns FARNN_ERANGE before enqueuing anything and leaves the outputs
+ * untouched).  All pointers are DEVICE pointers; tensors are row-major and unpadded. */
+typedef struct farnn_decomp_ind1_train_ctx farnn_decomp_ind1_train_ctx;
+
+typedef struct {
+    int32_t V, S, R, RO, C;     /* vocabulary rows of Vgen, states, rank of S1/S2 (:40), rank of the output factors and score
+                                   columns (C_output is [C][RO], :39)                                  */
+    int32_t nl;                 /* args.update_nonlinear: FARNN_NL_NONE / RELU / TANH / RELUTANH (:181-188) */
+    float   threshold;          /* decode clamp of column C-1 (model_decompose.py local_decode)     */
+    int32_t o_idx;              /* label written for column C-1                                     */
+} farnn_decomp_ind1_train_dims;
+
+typedef struct {
+    const float *Vgen;          /* [V][R] get_generalized_v_embed_vec of every word (model_decompose.py:222-241) */
+    const float *S1, *S2;       /* [S][R] (:70-71)                  */
+    const float *W;             /* [S][S] wildcard_mat (:91)        */
+    const float *C;             /* [C][RO] C_output (:82)           */
+    const float *S1o, *S2o;     /* [S][RO] S1_output, S2_output (:85-89) */
+    const float *h0, *hT;       /* [S] (:52-55)                     */
+    const float *P;             /* [C][C] priority matrix or NULL (args.use_priority = 0, :277) */
+} farnn_decomp_ind1_train_weights;
+
+typedef struct {
+    float *loss;                /* [1]                                                                 */
+    float *dVgen;               /* [V][R] (rows of words absent from the batch are written as zero)    */
+    float *dS1, *dS2;           /* [S][R]                                                              */
+    float *dW;                  /* [S][S] or NULL (train_wildcard_wildcard = 0, :93)                   */
+    float *dC;                  /* [C][RO] or NULL (train_wildcard = 0, :83)                           */
+    float *dS1o, *dS2o;         /* [S][RO] or NULL (train_wildcard = 0, :86-89)                        */
+    float *dh0, *dhT;           /* [S] or NULL (train_h0 / train_hT = 0, :53-55)                       */
+    int32_t *tags;              /* [B][L] decoded labels of this forward pass, -1 at pad positions     */
+} farnn_decomp_ind1_train_outputs;
+
+int  farnn_decomp_ind1_train_create(const farnn_decomp_ind1_train_dims *dims, int device, farnn_decomp_ind1_train_ctx **out);
+void farnn_decomp_ind1_train_destroy(farnn_decomp_ind1_train_ctx *ctx);
+/* One step on the given stream: writes all outputs (no float atomics: bit-identical across runs).  x, lengths, labels,
+ * valid_tokens and the handling of bad labels / words: as farnn_onehot_ifst_train_step. */
+int  farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_decomp_ind1_train_weights *w, const int64_t *x,
+                                  const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                  int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *out, void *stream);
+/* as farnn_train_set_profiling / farnn_train_time */
+int  farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *ctx, int32_t enable);
+int  farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);
+
 /* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
  * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,
  * no weight decay, no amsgrad:

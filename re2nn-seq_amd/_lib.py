@@ -156,6 +156,19 @@ class Ind1TrainOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('loss', 'dT', 'tags')]
 
 
+class Decomp1TrainDims(C.Structure):
+    _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('R', C.c_int32), ('RO', C.c_int32), ('C', C.c_int32), ('nl', C.c_int32),
+                ('threshold', C.c_float), ('o_idx', C.c_int32)]
+
+
+class Decomp1TrainWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('Vgen', 'S1', 'S2', 'W', 'C', 'S1o', 'S2o', 'h0', 'hT', 'P')]
+
+
+class Decomp1TrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('loss', 'dVgen', 'dS1', 'dS2', 'dW', 'dC', 'dS1o', 'dS2o', 'dh0', 'dhT', 'tags')]
+
+
 class OptimDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
@@ -193,6 +206,13 @@ SIGNATURES = {
                                         C.POINTER(Ind1TrainOutputs), C.c_void_p]),
     'farnn_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_decomp_ind1_train_create': (C.c_int, [C.POINTER(Decomp1TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_decomp_ind1_train_destroy': (None, [C.c_void_p]),
+    'farnn_decomp_ind1_train_step': (C.c_int, [C.c_void_p, C.POINTER(Decomp1TrainWeights), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                               C.POINTER(Decomp1TrainOutputs), C.c_void_p]),
+    'farnn_decomp_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -666,6 +686,18 @@ class Ind1TrainContext(_TrainContextBase):
         self._open(Ind1TrainDims(int(V), int(S), int(n_cols), int(bool(mask_by_output)), float(threshold), int(o_idx)),
                    device)
         self.dims = (int(V), int(S), int(n_cols))
+
+
+class Decomp1TrainContext(_TrainContextBase):
+    """Owns one farnn_decomp_ind1_train_ctx* (training step of the decomposed independent=1 model, include/farnn.h)."""
+    _create, _destroy = 'farnn_decomp_ind1_train_create', 'farnn_decomp_ind1_train_destroy'
+    _step = 'farnn_decomp_ind1_train_step'
+    _set_profiling, _time = 'farnn_decomp_ind1_train_set_profiling', 'farnn_decomp_ind1_train_time'
+    _weights, _outputs = Decomp1TrainWeights, Decomp1TrainOutputs
+
+    def __init__(self, V, S, R, RO, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
+        self._open(Decomp1TrainDims(int(V), int(S), int(R), int(RO), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
+        self.dims = (int(V), int(S), int(R), int(RO), int(n_cols))
 
 
 class Optim:

@@ -1,5 +1,5 @@
 // libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
-// i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*) and the onehot independent=1 model (farnn_ind1_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
+// i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*), the onehot independent=1 model (farnn_ind1_train_*) and the decomposed independent=1 model (farnn_decomp_ind1_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
 // loss) compile once, beside the tagging path.  Each step is a sequence of named stages (the static functions below, in the
 // order they run); what both steps share on the host side is in train_host.hip.h.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "onehot_train_max.hip.h"
 #include "fst4_train.hip.h"
 #include "ind1_train.hip.h"
+#include "decomp1_train.hip.h"
 #include "optim.hip.h"
 
 using namespace farnn;
@@ -1019,6 +1020,241 @@ extern "C" int farnn_ind1_train_step(farnn_ind1_train_ctx *c, const farnn_ind1_t
     if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
         (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
         (rc = t.dM_words()) || (rc = t.scores<2>())) return rc;
+    FARNN_HIP_TRY(hipGetLastError());
+    c->prof.end(t.s);
+    return FARNN_OK;
+}
+
+// ---- training step of the decomposed independent=1 model (FARNN_S_D_W_I; decomp1_train.hip.h) --------------
+struct farnn_decomp_ind1_train_ctx {
+    farnn_decomp_ind1_train_dims d;
+    int device = 0;
+    DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, br / scores, N / Mc / McT / dMc / dN, the factor
+                                  // products Kfac / Ofac / E, the partials
+    DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
+    StepProfile prof;
+    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
+};
+
+extern "C" int farnn_decomp_ind1_train_create(const farnn_decomp_ind1_train_dims *d, int device, farnn_decomp_ind1_train_ctx **out) {
+    if (!d || !out) return fail(FARNN_EINVAL, "decomp_ind1_train_create: null argument%s%s");
+    *out = nullptr;
+    if (d->V <= 0 || d->S <= 0 || d->R <= 0 || d->RO <= 0 || d->C <= 0) return fail(FARNN_EINVAL, "decomp_ind1_train_create: bad dimensions%s%s");
+    if (d->nl < FARNN_NL_NONE || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "decomp_ind1_train_create: bad nonlinearity%s%s");
+    if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "decomp_ind1_train_create: more than 128 states%s%s");
+    // fst4_loss_kernel keeps two score vectors per wavefront in LDS (fst4_loss_lds_bytes): C <= 2400
+    if (fst4_loss_lds_bytes(d->C) > 150 * 1024) return fail(FARNN_ERANGE, "decomp_ind1_train_create: too many score columns%s%s");
+    // element offsets into Kfac [R][S][S] and Ofac [R_O][S][S] are computed in 32 bits by the kernels that fill them
+    if ((unsigned long long)d->R * d->S * d->S >= (1ull << 31))
+        return fail(FARNN_ERANGE, "decomp_ind1_train_create: rank R too large (R S S must stay below 2^31)%s%s");
+    if ((unsigned long long)d->RO * d->S * d->S >= (1ull << 31))
+        return fail(FARNN_ERANGE, "decomp_ind1_train_create: output rank R_O too large (R_O S S must stay below 2^31)%s%s");
+    int rc;
+    if ((rc = select_device(device))) return rc;
+    farnn_decomp_ind1_train_ctx *c = new farnn_decomp_ind1_train_ctx();
+    c->d = *d; c->device = device;
+    if (!c->err.create()) { farnn_decomp_ind1_train_destroy(c); return fail(FARNN_ENOMEM, "decomp_ind1_train_create: out of memory%s%s"); }
+    *out = c;
+    return FARNN_OK;
+}
+
+extern "C" void farnn_decomp_ind1_train_destroy(farnn_decomp_ind1_train_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    delete c;
+}
+
+extern "C" int farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *c, int32_t enable) {
+    if (!c) return fail(FARNN_EINVAL, "decomp_ind1_train_set_profiling: null context%s%s");
+    c->prof.enabled = enable;
+    return FARNN_OK;
+}
+
+extern "C" int farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
+    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "decomp_ind1_train_time: null argument%s%s");
+    return c->prof.time(c->device, total_ms, steps);
+}
+
+// One step: the plan (decomp1_plan: sizes from the dimensions alone) and what the stages hand on
+struct Decomp1Step {
+    int B, L, ngrp, cpg;          // rank groups per word of the score kernel's MODE 0 and 1, output ranks per group
+    size_t S, K, V, R, RO, N1, N0;
+    unsigned lgrid;               // workgroups of the loss kernel
+    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_decomp1_ws / carve_decomp1_ints
+    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
+    farnn_decomp_ind1_train_ctx *c; const farnn_decomp_ind1_train_weights *w; const farnn_decomp_ind1_train_outputs *o; hipStream_t s;
+    OhTrainParams q;
+    Ind1TrainParams f;
+    D1BackParams bp;
+    float *BR, *DBR, *SC, *DS, *Nw, *M, *MT, *dM, *dN, *Kfac, *Ofac, *E, *Osum, *dOsum, *zero, *csum, *dcsum, *ones, *loss_part,
+          *partial, *part, *fpart, *HP;
+    Buckets bk;
+    int carve(const int64_t *x, const int64_t *lengths);
+    int gemm(const float *A, size_t am, size_t ak, const float *Bm, size_t bk_, size_t bn, float *Cm, size_t ldc, size_t M_, size_t N_,
+             size_t K_, const float *add = nullptr, const int *rows = nullptr);
+    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words(); int back(); int factors();
+    template <int MODE> int scores();
+};
+
+static size_t carve_decomp1_ws(float *base, Decomp1Step &t) {
+    Carver<float> a(base);
+    const size_t nS = t.N1 * t.S, SS = t.S * t.S, SS4 = (SS + 3) & ~(size_t)3, RO4 = (t.RO + 3) & ~(size_t)3;
+    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
+    t.BR = a.take(t.N0 * t.RO); t.DS = a.take(t.N0 * t.K);             // (neighbours: cleared by one memset)
+    t.DBR = a.take(t.N0 * t.RO); t.SC = a.take(t.N0 * t.K);
+    t.Nw = a.take(t.V * SS); t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS); t.dN = a.take(t.V * SS);
+    t.Kfac = a.take(t.R * SS); t.E = a.take(t.R * SS); t.Ofac = a.take(t.RO * SS);
+    t.Osum = a.take(SS4); t.dOsum = a.take(SS4); t.zero = a.take(SS4);
+    t.csum = a.take(RO4); t.dcsum = a.take(RO4);
+    t.ones = a.take((t.S + 3) & ~(size_t)3);
+    t.loss_part = a.take((size_t)t.lgrid * 8);
+    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dMc: partial tiles of the words with several runs
+    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and rank group
+    t.fpart = a.take(t.V * t.RO * 2 * t.S);                             // the words' shares of dS1_output / dS2_output
+    t.HP = a.take((size_t)t.B * 2 * t.S);                               // the sequences' shares of dh0 / dhT
+    return a.off;
+}
+static size_t carve_decomp1_ints(int *base, Decomp1Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
+
+// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
+static int decomp1_plan(const farnn_decomp_ind1_train_ctx *c, int B, int L, Decomp1Step &t) {
+    // positions are 32-bit flat indices b L + i in the bucketing, dMc and score kernels
+    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "decomp_ind1_train_step: B (L+1) must stay below 2^30%s%s");
+    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V; t.R = c->d.R; t.RO = c->d.RO;
+    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
+    // a word's output ranks are split over enough workgroups to fill the chip when the batch has few distinct words
+    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.RO, (size_t)F4_MAX_GROUPS});
+    t.cpg = (int)((t.RO + want - 1) / want); t.ngrp = (int)((t.RO + t.cpg - 1) / t.cpg);
+    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
+    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
+    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
+    t.lds_tok = (size_t)(L + 1) * sizeof(int);
+    t.lds_sc = ind1_train_lds_floats(SP, CPR, GW) * sizeof(float);
+    t.lds_loss = fst4_loss_lds_bytes(t.K);
+    t.need = carve_decomp1_ws(nullptr, t); t.ineed = carve_decomp1_ints(nullptr, t);
+    int rc;
+    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
+    return lds_fits(t.lds_loss);
+}
+// Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
+int Decomp1Step::carve(const int64_t *x, const int64_t *lengths) {
+    int rc;
+    if ((rc = c->ws.ensure(need, "decomp_ind1_train_step: out of device memory for the workspace%s%s")) ||
+        (rc = c->iws.ensure(ineed, "decomp_ind1_train_step: out of device memory for the index workspace%s%s"))) return rc;
+    [[maybe_unused]] const size_t carved = carve_decomp1_ws(c->ws.p, *this), icarved = carve_decomp1_ints(c->iws.p, *this);
+    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
+    // the chains use args.update_nonlinear (model_decompose_independent.py:181-188); the output mask is premixed into Mc: a mask of ones
+    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
+    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = c->d.nl;
+    // the score kernel in factor space: N (wildcard_mat already in it) in T's place beside a zero W, Ofac in O's, br in the scores'
+    f.T = Nw; f.W = zero; f.O = Ofac; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
+    f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
+    f.SC = BR; f.DS = DBR; f.part = part; f.dMc = dM; f.Osum = Osum; f.dT = dN;
+    f.L = L; f.S = (int)S; f.C = (int)RO; f.cpg = cpg; f.ngrp = ngrp; f.mask = 1;
+    bp.N = Nw; bp.Ofac = Ofac; bp.S1o = w->S1o; bp.S2o = w->S2o; bp.A = q.A; bp.Bk = q.Bk; bp.len = lengths;
+    bp.list = bk.list; bp.wstart = bk.wstart; bp.wcount = bk.wcount; bp.DBR = DBR; bp.dMc = dM; bp.Osum = Osum;
+    bp.dN = dN; bp.fpart = fpart; bp.L = L; bp.S = (int)S; bp.SP = f.SP; bp.RO = (int)RO; bp.CPR = f.CPR; bp.GW = f.GW;
+    return FARNN_OK;
+}
+// C[m][n] = sum_k A[m am + k ak] B[k bk + n bn] (+ add[n]); rows: the rows read as zero (decomp1_gemm_kernel)
+int Decomp1Step::gemm(const float *A, size_t am, size_t ak, const float *Bm, size_t bk_, size_t bn, float *Cm, size_t ldc, size_t M_,
+                      size_t N_, size_t K_, const float *add, const int *rows) {
+    D1Gemm g = {A, Bm, add, rows, Cm, (int)M_, (int)N_, (int)K_, am, ak, bk_, bn, ldc};
+    return launch(decomp1_gemm_kernel, dim3((unsigned)((M_ + D1_TM - 1) / D1_TM), (unsigned)((N_ + D1_TM - 1) / D1_TM)), 256, 0, s, g);
+}
+// Stages 4 and 5: the positions bucketed by word; the factor products Kfac and Ofac; Osum; N[w] = Vgen[w] Kfac + wildcard_mat
+// for the words of the batch (the bucket counts say which), Mc[w] = N[w] * Osum and its transpose.  br and d score are cleared:
+// their rows at pad positions enter the products over the positions (dC_output) as zeros
+int Decomp1Step::prepare() {
+    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    FARNN_HIP_TRY(hipMemsetAsync(BR, 0, N0 * (RO + K) * sizeof(float), s));
+    FARNN_HIP_TRY(hipMemsetAsync(zero, 0, S * S * sizeof(float), s));
+    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
+    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    const size_t SS = S * S;
+    decomp1_outer_kernel<<<(unsigned)((R * SS + 255) / 256), 256, 0, s>>>(w->S1, w->S2, Kfac, (int)S, (int)R);
+    decomp1_outer_kernel<<<(unsigned)((RO * SS + 255) / 256), 256, 0, s>>>(w->S1o, w->S2o, Ofac, (int)S, (int)RO);
+    decomp1_csum_kernel<<<(unsigned)((RO + 255) / 256), 256, 0, s>>>(w->C, csum, (int)K, (int)RO);
+    decomp1_osum_kernel<<<(unsigned)((SS + 255) / 256), 256, 0, s>>>(csum, Ofac, Osum, (int)SS, (int)RO);
+    if (int rc = gemm(w->Vgen, R, 1, Kfac, SS, 1, Nw, SS, V, SS, R, w->W, bk.wcount)) return rc;
+    const unsigned nt = (unsigned)((S + 31) / 32);
+    ind1_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(Nw, zero, Osum, bk.wcount, M, MT, (int)S);
+    return FARNN_OK;
+}
+// Stages 7 and 9: ind1_train_kernel in bucket order over the output ranks (MODE 0: br, 1: the partials of d alpha / d beta)
+template <int MODE>
+int Decomp1Step::scores() {
+    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
+    auto go = [&](auto RPT) { return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), I1_THREADS, lds_sc, s, f); };
+    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
+                                                                                                             : go(int_c<16>());
+}
+// Stage 8: score = br C_output^T (:206); priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront
+// partials; d br = d score C_output
+int Decomp1Step::loss(const int64_t *labels, int64_t valid_tokens) {
+    int rc;
+    if ((rc = gemm(BR, RO, 1, w->C, 1, RO, SC, K, N0, K, RO))) return rc;
+    if ((rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
+                     (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens))) return rc;
+    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    return gemm(DS, K, 1, w->C, RO, 1, DBR, RO, N0, RO, K);
+}
+// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the rank groups' partials added in group order
+int Decomp1Step::adjoints() {
+    if (int rc = scores<1>()) return rc;
+    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
+    return FARNN_OK;
+}
+// Stage 11: dMc[w] of the chains, the i-FST step's per-word reduction
+int Decomp1Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
+// Stage 12: dN[w] and the words' shares of dS1_output / dS2_output, one workgroup per word over all output ranks
+int Decomp1Step::back() {
+    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
+    auto go = [&](auto RPT) { return launch(decomp1_back_kernel<RPT()>, (unsigned)V, I1_THREADS, lds_sc, s, bp); };
+    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
+                                                                                                             : go(int_c<16>());
+}
+// Stage 13: the dense adjoints contracted onto the factors, every sum over the words in id order and over the sequences in order
+int Decomp1Step::factors() {
+    int rc;
+    const size_t SS = S * S;
+    decomp1_word_sum_kernel<<<(unsigned)((SS + 255) / 256), 256, 0, s>>>(dN, dM, Nw, bk.wcount, o->dW, dOsum, (int)V, SS);
+    decomp1_out_factors_kernel<<<(unsigned)RO, 128, 0, s>>>(fpart, bk.wcount, dOsum, w->S1o, w->S2o, csum, o->dS1o, o->dS2o, dcsum,
+                                                           (int)V, (int)S, (int)RO);
+    // dC_output[c,r] = sum_pos d score[pos,c] br[pos,r] (positions in order) + dcsum[r] (every row: csum = C_output.sum(0))
+    if (o->dC && (rc = gemm(DS, 1, K, BR, RO, 1, o->dC, RO, K, RO, N0, dcsum))) return rc;
+    if ((rc = gemm(dN, SS, 1, Kfac, 1, SS, o->dVgen, R, V, R, SS, nullptr, bk.wcount)) ||      // dv_r = sum_ij dN[w]_ij S1[i,r] S2[j,r]
+        (rc = gemm(w->Vgen, 1, R, dN, SS, 1, E, SS, R, SS, V))) return rc;                     // E[r] = sum_w v_r[w] dN[w]
+    decomp1_in_factors_kernel<<<(unsigned)R, 128, 0, s>>>(E, w->S1, w->S2, o->dS1, o->dS2, (int)S, (int)R);
+    if (o->dh0 || o->dhT) {
+        decomp1_init_adj_kernel<<<(unsigned)B, 128, 0, s>>>(q, HP);
+        decomp1_init_sum_kernel<<<1, 128, 0, s>>>(HP, o->dh0, o->dhT, B, (int)S);
+    }
+    return FARNN_OK;
+}
+
+extern "C" int farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *c, const farnn_decomp_ind1_train_weights *w, const int64_t *x,
+                                            const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                            int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *o, void *stream) {
+    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "decomp_ind1_train_step: null argument%s%s");
+    if (!w->Vgen || !w->S1 || !w->S2 || !w->W || !w->C || !w->S1o || !w->S2o || !w->h0 || !w->hT)
+        return fail(FARNN_EINVAL, "decomp_ind1_train_step: null weight%s%s");
+    if (!o->loss || !o->dVgen || !o->dS1 || !o->dS2 || !o->tags) return fail(FARNN_EINVAL, "decomp_ind1_train_step: null output%s%s");
+    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "decomp_ind1_train_step: B, L and valid_tokens must be positive%s%s");
+    Decomp1Step t = {};
+    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
+    int rc, bad = 0;
+    if ((rc = decomp1_plan(c, B, L, t))) return rc;
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->err.take(t.s, &bad))) return rc;
+    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "decomp_ind1_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
+                                                 : "decomp_ind1_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
+    if ((rc = t.carve(x, lengths))) return rc;
+    StepProfile::Guard timing = c->prof.begin(t.s);
+    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
+        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
+        (rc = t.dM_words()) || (rc = t.back()) || (rc = t.factors())) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     c->prof.end(t.s);
     return FARNN_OK;

@@ -2,7 +2,10 @@
 (src_seq/farnn/model_decompose_independent.py:11-300): a rank-R language tensor plus a separate
 rank-R_O output tensor (C_output, S1_output, S2_output).  Same constructor arguments and state-dict
 keys as the reference; inference runs in the HIP library (farnn_decomp_ind1_create).
+Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -98,3 +101,85 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             o_idx=self.o_idx, use_crf=self.use_crf,
             crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(),
             device=self.device_index)
+
+    # ---- training step (reference :148-300 with train=True + train_decompose.py:161-221) ----
+    # which tensors get a gradient: the reference's requires_grad flags (:52-55, :70-97).  wildcard_output is not read under
+    # CE1 (:213-216): it has no gradient, is not a parameter here and stays as it is in the state dict.
+    _TRAIN_FLAGS = {'S1': None, 'S2': None, 'embed_r_generalized': None, 'V_embed': 'train_V_embed',
+                    'C_output': 'train_wildcard', 'S1_output': 'train_wildcard', 'S2_output': 'train_wildcard',
+                    'wildcard_mat': 'train_wildcard_wildcard', 'h0': 'train_h0', 'hT': 'train_hT',
+                    'beta_vec': 'train_beta', 'embedding.weight': 'train_word_embed'}
+
+    @staticmethod
+    def _decomp_ind1_train_enabled():
+        """RE2NN_DECOMP_IND1_TRAIN=1: this model's training step (opt-in for its first release, as RE2NN_ONEHOT_IND1_TRAIN)"""
+        return os.environ.get('RE2NN_DECOMP_IND1_TRAIN', '') == '1'
+
+    def _check_trainable(self, re_tags=None):
+        """The cases the HIP training step does not cover, refused before any device work."""
+        if not self._decomp_ind1_train_enabled():     # before self.args is touched: the refusal needs the type only
+            from ..train_onehot import no_training_step
+            raise no_training_step(self)
+        a = self.args
+        why = None
+        if a.farnn != 0:
+            why = 'the gated recurrences (--farnn {})'.format(a.farnn)
+        elif a.train_mode != 'sum':
+            why = 'the max semiring (--train_mode {})'.format(a.train_mode)
+        elif a.use_crf:
+            why = 'the CRF (--use_crf 1)'
+        elif a.local_loss_func != 'CE1':
+            why = 'a loss other than CE1 (--local_loss_func {})'.format(a.local_loss_func)
+        elif re_tags is not None or getattr(a, 'marryup_type', 'none') not in ('none', None):
+            why = 'the KD / PR teacher terms (--marryup_type {})'.format(getattr(a, 'marryup_type', 'none'))
+        else:
+            from ..dist import world
+            if world()[1] > 1:
+                why = 'multi-GPU data-parallel training'
+        if why is not None:
+            raise NotImplementedError('training the decomposed independent=1 model covers farnn 0, the sum semiring and the CE1 '
+                                      'loss on one GPU; {} is not built (DESIGN.md, row f9)'.format(why))
+
+    def enable_training(self):
+        """Device-resident leaf tensors for the optimizer (returned by parameters()) and the library context."""
+        self._check_trainable()
+        if getattr(self, '_tp', None) is not None:
+            return self
+        if not torch.cuda.is_available():
+            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
+        dev = self._dev()
+        src = dict(self.state_dict())
+        self._tp = {}
+        for k, flag in self._TRAIN_FLAGS.items():
+            t = src[k].detach().to(dev).float().clone()
+            t.requires_grad_(True if flag is None else bool(getattr(self.args, flag, 0)))
+            self._tp[k] = t
+        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
+            if self.args.use_priority else None
+        S, R = self._tp['S1'].shape
+        C, RO = self._tp['C_output'].shape
+        self._tc = _lib.Decomp1TrainContext(self._tp['V_embed'].shape[0], S, R, RO, C, nl=self.args.update_nonlinear,
+                                            threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index)
+        self._dirty = False
+        return self
+
+    def forward_local(self, input, label, lengths, train=True, re_tags=None):
+        if not train:
+            self.sync_from_training()
+            return NativeTagger.forward_local(self, input, label, lengths, train=False, re_tags=re_tags)
+        from .train_step import decomp_ind1_train_step
+        self._check_trainable(re_tags)
+        self.enable_training()
+        tp = self._tp
+        on_host = lengths.device.type == 'cpu'
+        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
+        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
+        x = input[:, :Lmax]
+        lab = label[:, :Lmax]
+        loss, tags = decomp_ind1_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
+                                            tp['C_output'], tp['S1_output'], tp['S2_output'], tp['h0'], tp['hT'], self._tpP,
+                                            x, lengths, lab, valid_tokens=ntok)
+        self._dirty = True
+        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
+        true = self._flatten(label, lengths).to(input.device)
+        return loss, pred, true

@@ -1,5 +1,5 @@
 """The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step,
-farnn_onehot_ifst_train_step, farnn_fst4_train_step and farnn_ind1_train_step (include/farnn.h).
+farnn_onehot_ifst_train_step, farnn_fst4_train_step, farnn_ind1_train_step and farnn_decomp_ind1_train_step (include/farnn.h).
 
 What the reference does in FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
 (model_decompose_single.py:207-304, train_decompose.py:186-190) is split like this: the word table
@@ -21,6 +21,10 @@ The onehot FST (FARNN_S_O, model_onehot.py:66-146) trains languag
 
 The onehot independent=1 model (FARNN_S_O_I, model_onehot.py:184-306) trains language_tensor [V,S,S]
 only: one library call.
+
+The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.py:148-300): the word table as
+for f3 through torch's autograd, and one library call (farnn_decomp_ind1_train_step) for the loss, the tags and the gradients of
+Vgen, S1, S2, wildcard_mat, C_output, S1_output, S2_output, h0 and hT.
 """
 import torch
 
@@ -193,3 +197,42 @@ def onehot_ind1_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tok
     P are read but receive no gradient (the reference's requires_grad=False, model_onehot.py:209-223).  Whether the chains
     run on (T + W) * O.sum(0) (args.independent == 2) is the context's mask_by_output."""
     return _OnehotInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
+
+
+_D1_NAMES = ('Vgen', 'S1', 'S2', 'W', 'C', 'S1o', 'S2o', 'h0', 'hT')
+_D1_OPTIONAL = ('W', 'C', 'S1o', 'S2o', 'h0', 'hT')       # gradients the library writes only when asked (include/farnn.h)
+
+
+class _DecompInd1TrainStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT):
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(S1, ntok, x, lengths, labels)
+        B, L = x.shape
+        ts = dict(zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT)))
+        ws = {n: _f32(t) for n, t in ts.items()}
+        Pc = _f32(P)
+        grads = {n: torch.empty_like(ws[n]) for n in _D1_NAMES if n not in _D1_OPTIONAL or ts[n].requires_grad}
+        weights = {n: t.data_ptr() for n, t in ws.items()}
+        weights['P'] = None if Pc is None else Pc.data_ptr()
+        outputs = {'d' + n: (grads[n].data_ptr() if n in grads else None) for n in _D1_NAMES}
+        outputs['loss'] = loss.data_ptr()
+        outputs['tags'] = tags.data_ptr()
+        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
+                torch.cuda.current_stream(dev).cuda_stream)
+        ctx.have = tuple(n in grads for n in _D1_NAMES)
+        ctx.save_for_backward(*[grads[n] for n in _D1_NAMES if n in grads])
+        ctx.mark_non_differentiable(tags)
+        return loss.reshape(()), tags
+
+    @staticmethod
+    def backward(ctx, gloss, _gtags):
+        saved = iter(ctx.saved_tensors)
+        return (None,) * 6 + tuple(next(saved) * gloss if h else None for h in ctx.have)
+
+
+def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, lengths, labels, valid_tokens=None):
+    """The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.py:219-300): returns
+    (loss scalar tensor with grad, tags int32 [B,L] with -1 at pads).  Vgen [V,R] (its gradient flows on through torch's
+    autograd to V_embed, embed_r_generalized, embedding.weight and beta_vec), S1 and S2 always get a gradient; wildcard_mat W,
+    C_output, S1_output, S2_output, h0 and hT get one when they require it and None otherwise.  P is read only."""
+    return _DecompInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT)

@@ -5,13 +5,14 @@ example configs use) or FARNN_S_D_W_I (``--independent 1``), INIT evaluation, `.
 reached from the CLI: main.py:127 forces local_loss_func='CE1' and :69-70 asserts independent != 0
 under CE1.  The epoch loop (:155-220) runs on the HIP training step (csrc/train.hip.h through
 train_onehot.train_epochs) for the decomposed i-FST (``--independent 2``) with farnn 0/1/2, with or without the CRF,
-CE + CRF NLL losses; the KD / PR teacher terms and the other ``--independent`` settings are evaluated with --epoch 0."""
+CE + CRF NLL losses, and, opt-in (RE2NN_DECOMP_IND1_TRAIN=1, csrc/decomp1_train.hip.h), for ``--independent 1``
+with farnn 0 and the CE1 loss; the KD / PR teacher terms and ``--independent 0`` are evaluated with --epoch 0."""
 from .farnn.model_decompose import FARNN_S_D_W
 from .farnn.model_decompose_independent import FARNN_S_D_W_I
 from .farnn.model_decompose_single import FARNN_S_D_W_I_S
 from .init_params import (get_init_params_seq, get_init_params_seq_independent,
                           get_init_params_seq_independent_single)
-from .train_onehot import init_evaluation, prepare_slot_data
+from .train_onehot import check_trainable, init_evaluation, prepare_slot_data
 from .utils import Logger, set_seed
 
 
@@ -41,6 +42,8 @@ def train_slot_decompose(args, data_dir='../data/', model_dir='../model_seq/'):
                               wildcard_output=wildcard_output, final_vector=final_vector,
                               start_vector=start_vector, pretrained_word_embed=pretrain_embed_extend,
                               priority_mat=priority_mat, args=args, o_idx=s2i['o'])
+        if args.epoch > 0:
+            check_trainable(model)                 # before the INIT evaluations touch the device
         return init_evaluation(model, splits, args, s2i, i2s, logger, model_dir)
     t2i_nopad = t2i                                # init_params appends the pad row itself
     (V_embed_extend, S1, S2, pretrain_embed_extend, wildcard_mat, wildcard_output_vector,

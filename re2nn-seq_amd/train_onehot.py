@@ -55,8 +55,8 @@ def init_evaluation(model, splits, args, s2i, i2s, logger, model_dir='../model_s
 
 
 def no_training_step(model):
-    """The refusal of a model without a training step (also the onehot FST's and the independent=1 model's without their
-    opt-ins: model_onehot.FARNN_S_O, FARNN_S_O_I)."""
+    """The refusal of a model without a training step (also the onehot FST's and the independent=1 models' without their
+    opt-ins: model_onehot.FARNN_S_O, FARNN_S_O_I, model_decompose_independent.FARNN_S_D_W_I)."""
     return NotImplementedError(
         'training epochs are implemented for the i-FST models only (--independent 2: --method decompose, DESIGN.md '
         'row f3, and --method onehot, row f5); {} has no training step, run it with --epoch 0'.format(type(model).__name__))
@@ -67,7 +67,8 @@ def check_trainable(model):
     if not hasattr(model, 'enable_training'):
         raise no_training_step(model)
     from .farnn.model_onehot import FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S
-    if isinstance(model, (FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S)):
+    from .farnn.model_decompose_independent import FARNN_S_D_W_I
+    if isinstance(model, (FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S, FARNN_S_D_W_I)):
         model._check_trainable()                  # max semiring, CRF extension, several GPUs; a model without its opt-in
 
 

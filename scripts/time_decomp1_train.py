@@ -1,0 +1,101 @@
+"""Timing of the decomposed independent=1 training step (farnn_decomp_ind1_train_step) at the shape of
+bench.py's `decomp1` workload: V = 11 000, S = 104, C = 73, rank 50, output rank 70, tanh, B = 256, L = 64 with ragged
+lengths, rotating through four batches of the same lengths.  Prints one JSON line:
+
+  lib_us_per_step     HIP-event time of the library step (farnn_decomp_ind1_train_time): median of the per-step times, with
+  lib_us_min / _max   their spread
+  stage_us            (--stages 1) torch.profiler's device time per kernel name over the timed steps, divided by the steps,
+                      largest first, and `dominant` the first of them; a run of its own, after the event-timed steps
+
+    python scripts/time_decomp1_train.py [--steps 10] [--warmup 2] [--stages 1]
+
+The line carries no rate: none was measured.  Each GPU step of a job script runs it under its own time limit
+(timeout -k 10 ...)."""
+import argparse
+import json
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--stages', type=int, default=1)
+    a = ap.parse_args()
+    import torch
+    from re2nn_seq_amd import _lib, synth
+    from re2nn_seq_amd.farnn.train_step import decomp_ind1_train_step
+    V, S, C, R, RO, B, L = 11000, 104, 73, 50, 70, 256, 64
+    rng = np.random.RandomState(1234)
+    p = synth.random_decomposed_params(V, S, C, R, 100, rng, contractive=True)
+    f = lambda *shape, sc=0.2: (rng.randn(*shape) * sc).astype(np.float32)      # noqa: E731
+    x0, lengths = synth.random_batch(V, B, L, rng)
+    xs = [x0]
+    for k in range(1, 4):                         # same lengths, tokens drawn afresh (bench.py batch_variants)
+        r = np.random.RandomState(4321 + 7919 * k)
+        xk, _ = synth.random_batch(V, B, L, r, min_len=L, full_length_rows=B)
+        xk[np.arange(L)[None, :] >= lengths[:, None]] = V - 1
+        xs.append(xk)
+    labels = [rng.randint(0, C, size=(B, L)).astype(np.int64) for _ in xs]
+    ntok = int(lengths.sum())
+    dev = torch.device('cuda', 0)
+    d = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev).requires_grad_(True)      # noqa: E731
+    ws = [d(p['V_embed']), d(p['S1']), d(p['S2']), d(p['wildcard_mat']), d(f(C, RO, sc=0.5)), d(f(S, RO)), d(f(S, RO)),
+          d(p['start_vector']), d(p['final_vector'])]
+    xd = [torch.from_numpy(v).to(dev) for v in xs]
+    ld = torch.from_numpy(lengths).to(dev)
+    labd = [torch.from_numpy(v).to(dev) for v in labels]
+    tc = _lib.Decomp1TrainContext(V, S, R, RO, C, nl='tanh', device=0)
+
+    def one(i):
+        for t in ws:
+            t.grad = None
+        loss, _ = decomp_ind1_train_step(tc, *ws, None, xd[i % 4], ld, labd[i % 4], valid_tokens=ntok)
+        loss.backward()
+        return loss
+
+    for i in range(a.warmup):
+        one(i)
+    torch.cuda.synchronize()
+    tc.time()
+    tc.set_profiling(1)
+    per = []
+    for i in range(a.steps):
+        loss = one(i)
+        ms, n = tc.time()
+        per.append(1e3 * ms / max(n, 1))
+    tc.set_profiling(0)
+    words = [int(len(np.unique(v[np.arange(L)[None, :] < lengths[:, None]]))) for v in xs]
+    # the stamp of what was measured: sha256 over the library's sources (csrc/*.hip, csrc/*.h, include/farnn.h), names in order
+    h = hashlib.sha256()
+    csrc = os.path.join(ROOT, 're2nn-seq_amd', 'csrc')
+    for path in sorted(os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith(('.hip', '.h'))) + \
+            [os.path.join(ROOT, 'include', 'farnn.h')]:
+        with open(path, 'rb') as fh:
+            h.update(os.path.basename(path).encode() + b'\0' + fh.read())
+    tree = h.hexdigest()[:16]
+    out = {'shape': {'V': V, 'S': S, 'C': C, 'R': R, 'RO': RO, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok,
+           'steps': a.steps, 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
+           'lib_us_max': float(max(per)), 'distinct_words': words, 'loss': float(loss.detach()), 'tree': tree}
+    if a.stages:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for i in range(a.steps):
+                one(i)
+            torch.cuda.synchronize()
+        rows = sorted(((getattr(e, 'device_time_total', 0) or getattr(e, 'cuda_time_total', 0)) / a.steps, e.key)
+                      for e in prof.key_averages())[::-1][:8]
+        out['stage_us'] = [[k.split('(')[0][-60:], round(t, 1)] for t, k in rows if t > 0]
+        out['dominant'] = out['stage_us'][0][0] if out['stage_us'] else None
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == '__main__':
+    main()
