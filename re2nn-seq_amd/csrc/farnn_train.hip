@@ -1,7 +1,10 @@
-// libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
-// i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*), the onehot independent=1 model (farnn_ind1_train_*) and the decomposed independent=1 model (farnn_decomp_ind1_train_*), and the optimizer step that follows either (farnn_optim_*, at the end).  Their own translation unit: the kernels of train.hip.h (shared by both: the scores and the
-// loss) compile once, beside the tagging path.  Each step is a sequence of named stages (the static functions below, in the
-// order they run); what both steps share on the host side is in train_host.hip.h.
+// libfarnn_hip.so -- the five training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
+// i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*), the onehot independent=1 model (farnn_ind1_train_*) and the
+// decomposed independent=1 model (farnn_decomp_ind1_train_*), and the optimizer step that follows any of them (farnn_optim_*, at
+// the end).  Their own translation unit: the training kernels (train.hip.h: the scores and the loss, shared by the first two
+// steps; the headers below) compile once, beside the tagging path.  Each step is a struct whose member functions are its named
+// stages, in the order they run; every entry point goes through run_train_step and every context is a TrainCtxBase
+// (train_host.hip.h), and the last three steps are a BucketedStep each (train_bucketed.hip.h).
 #include <hip/hip_runtime.h>
 #include <assert.h>
 #include <math.h>
@@ -11,6 +14,7 @@
 #include "common.hip.h"
 #include "host_util.hip.h"
 #include "train_host.hip.h"
+#include "train_bucketed.hip.h"
 #include "train_max.hip.h"
 #include "onehot_train_max.hip.h"
 #include "fst4_train.hip.h"
@@ -21,10 +25,9 @@
 using namespace farnn;
 
 // ---- training step (decomposed i-FST) ------------------------------------------
-struct farnn_train_ctx {
+struct farnn_train_ctx : TrainCtxBase {     // (err: the kernels set bit 0 on a bad label)
     Tunables tun;                 // the FARNN_* switches as they stood when the context was created (host_util.hip.h)
     farnn_train_dims d;
-    int device = 0;
     int n_cu = 256;               // compute units of the device
     int semiring = FARNN_SEMIRING_SUM;  // farnn_train_set_semiring
     DevBuf<float> fixed;          // create's block: the transposes and column sums below
@@ -36,8 +39,6 @@ struct farnn_train_ctx {
     DevBuf<float> ones;           // 1.0f each: bias gradients as a product with a column of ones
     DevBuf<float> mws;            // max semiring only (train_max.hip.h): M, MT, dM, IN, GM; allocated on first use
     DevBuf<int> miws;             // max semiring only: IDX, the bucketing of the positions, the word slots
-    StepProfile prof;
-    ErrWord err;                  // the kernels set bit 0 on a bad label
 };
 
 extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out) {
@@ -51,32 +52,24 @@ extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_t
         return fail(FARNN_ERANGE, "train_create: CRF needs 4..190 score columns%s%s");
     if (d->farnn < 0 || d->farnn > 2) return fail(FARNN_EINVAL, "train_create: farnn must be 0, 1 or 2%s%s");
     int rc;
-    if ((rc = select_device(device))) return rc;
-    farnn_train_ctx *c = new farnn_train_ctx();
-    c->d = *d; c->device = device; c->n_cu = device_cus(device);
+    if ((rc = train_ctx_create("train", d, device, out))) return rc;
+    farnn_train_ctx *c = *out;
+    c->n_cu = device_cus(device);
     const size_t S = d->S, R = d->R, V = d->V;
     const char *oom = "train_create: out of device memory%s%s";
     if ((rc = c->fixed.ensure(2 * S * R + S * S + 2 * S + (d->farnn ? 2 * S * S + 2 * S * R : 0), oom)) ||
-        (d->farnn && ((rc = c->VgenT.ensure(V * R, oom)) || (rc = c->GV.ensure(6 * V * S, oom))))) { delete c; return rc; }
+        (d->farnn && ((rc = c->VgenT.ensure(V * R, oom)) || (rc = c->GV.ensure(6 * V * S, oom))))) {
+        train_ctx_destroy(c);
+        *out = nullptr;
+        return rc;
+    }
     c->S1T = c->fixed.p; c->S2T = c->S1T + S * R; c->WT = c->S2T + S * R; c->Osum = c->WT + S * S; c->dOsum = c->Osum + S;
     if (d->farnn) { c->Wss1T = c->dOsum + S; c->Wss2T = c->Wss1T + S * S; c->Wrs1T = c->Wss2T + S * S; c->Wrs2T = c->Wrs1T + S * R; }
-    if (!c->err.create()) { farnn_train_destroy(c); return fail(FARNN_ENOMEM, "train_create: out of memory%s%s"); }
-    *out = c;
     return FARNN_OK;
 }
-
-extern "C" void farnn_train_destroy(farnn_train_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    delete c;                     // the buffers, the events and the error word free themselves
-}
-
-extern "C" int farnn_train_set_profiling(farnn_train_ctx *c, int32_t enable) {
-    if (!c) return fail(FARNN_EINVAL, "train_set_profiling: null context%s%s");
-    c->prof.enabled = enable;
-    return FARNN_OK;
-}
+extern "C" void farnn_train_destroy(farnn_train_ctx *c) { train_ctx_destroy(c); }
+extern "C" int farnn_train_set_profiling(farnn_train_ctx *c, int32_t enable) { return train_ctx_set_profiling("train", c, enable); }
+extern "C" int farnn_train_time(farnn_train_ctx *c, double *total_ms, int64_t *steps) { return train_ctx_time("train", c, total_ms, steps); }
 
 extern "C" int farnn_train_set_semiring(farnn_train_ctx *c, int32_t semiring) {
     if (!c) return fail(FARNN_EINVAL, "train_set_semiring: null context%s%s");
@@ -86,11 +79,6 @@ extern "C" int farnn_train_set_semiring(farnn_train_ctx *c, int32_t semiring) {
         return fail(FARNN_ERANGE, "train_set_semiring: the max-semiring step holds at most 192 states%s%s");
     c->semiring = semiring;
     return FARNN_OK;
-}
-
-extern "C" int farnn_train_time(farnn_train_ctx *c, double *total_ms, int64_t *steps) {
-    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "train_time: null argument%s%s");
-    return c->prof.time(c->device, total_ms, steps);
 }
 
 static void atb_add(AtbJobs &jobs, const float *A, const float *Bm, float *out, long long N, int M, int J) {
@@ -176,8 +164,7 @@ static size_t carve_max_ints(int *base, MaxWs &m, const TrainPlan &pl) {
     return a.off;
 }
 // Stage 1: the arguments
-static int train_validate(const farnn_train_ctx *c, const farnn_train_weights *w, const farnn_train_outputs *o, int B, int L,
-                          int64_t valid_tokens) {
+static int train_validate(const farnn_train_ctx *c, const farnn_train_weights *w, const farnn_train_outputs *o) {
     if (!w->Vgen || !w->S1 || !w->S2 || !w->W || !w->C || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "train_step: null weight%s%s");
     if (!o->loss || !o->dVgen || !o->dS1 || !o->dS2 || !o->dW || !o->dC || !o->dh0 || !o->dhT || !o->tags)
         return fail(FARNN_EINVAL, "train_step: null output%s%s");
@@ -186,7 +173,6 @@ static int train_validate(const farnn_train_ctx *c, const farnn_train_weights *w
         return fail(FARNN_EINVAL, "train_step: update-gate weights / gradients missing%s%s");
     if (c->d.farnn == 2 && (!w->Wss2 || !w->Wrs2 || !w->bs2 || !o->dWss2 || !o->dWrs2 || !o->dbs2))
         return fail(FARNN_EINVAL, "train_step: reset-gate weights / gradients missing%s%s");
-    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "train_step: B, L and valid_tokens must be positive%s%s");
     return FARNN_OK;
 }
 // Stage 2: host arithmetic only, no HIP call -- the workspace sizes, the kernel forms and the LDS bytes of every launch, from the
@@ -256,13 +242,21 @@ static int train_plan(const farnn_train_ctx *c, int B, int L, TrainPlan &pl) {
 }
 // One step: its plan and what its stages hand on.  The stages are the member functions, below in the order they run.
 struct TrainStep : TrainPlan {
+    static constexpr const char *name = "train", *label_range = "K";
     farnn_train_ctx *c; const farnn_train_weights *w; const farnn_train_outputs *o; hipStream_t s;
     TrainParams p; MaxWs m; PrepJobs prep; AtbJobs gate_jobs, grad_jobs;
     float *dGVT;                        // dGV^T ([S][V]) as the A operand of dVgen += dGV Wrs^T
+    int validate() { return train_validate(c, w, o); }
+    int plan(int B_, int L_) { return train_plan(c, B_, L_, *this); }
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int prep_jobs(); int product_jobs();
     int prepare(); int forward(); int max_forward(); int loss(); int backward(); int max_weight_gradients(); int gradients();
     int max_backward() { return launch(tmax_backward_kernel, dim3(B, 2), TM_THREADS, lds_tok, s, p, m.mp); }
+    int stages() {
+        int rc;
+        if ((rc = prepare()) || (rc = mx ? max_forward() : forward()) || (rc = loss())) return rc;
+        return (rc = mx ? max_backward() : backward()) ? rc : gradients();
+    }
 };
 
 // Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters and the job lists.  Nothing is enqueued yet.
@@ -395,8 +389,8 @@ int TrainStep::forward() {
 }
 // Stage 5, max semiring: the positions bucketed by word (onehot_train.hip.h), the distinct words' slots, their blocks, both chains
 int TrainStep::max_forward() {
-    FARNN_HIP_TRY(hipMemsetAsync(m.bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
-    if (int rc = launch_bucketing(p.x, p.len, B, L, (int)V, m.bk, nullptr, s)) return rc;
+    int rc;
+    if ((rc = clear_bucket_counts(m.bk, V, N0, s)) || (rc = launch_bucketing(p.x, p.len, B, L, (int)V, m.bk, nullptr, s))) return rc;
     tmax_slots_kernel<<<1, 1024, 0, s>>>(m.bk.wcount, (int)V, m.wslot, m.wlist, m.nwords);
     const unsigned nt = (unsigned)((S + 31) / 32);
     tmax_premix_kernel<<<dim3((unsigned)nwmax, nt * nt), 256, 0, s>>>(w->Vgen, w->S1, w->S2, w->W, m.wlist, m.nwords, m.M, m.MT, (int)S, (int)R);
@@ -443,35 +437,18 @@ int TrainStep::gradients() {
 extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_train_weights *w, const int64_t *x,
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_train_outputs *o, void *stream) {
-    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "train_step: null argument%s%s");
-    TunScope tun_scope(&c->tun);
-    TrainStep t = {};
-    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
-    int rc, bad = 0;
-    if ((rc = train_validate(c, w, o, B, L, valid_tokens)) || (rc = train_plan(c, B, L, t))) return rc;
-    FARNN_HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->err.take(t.s, &bad))) return rc;
-    if (bad) return fail(FARNN_EINVAL, "train_step: an earlier step saw a label outside 0..K-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
-    if ((rc = t.carve(x, lengths, labels, valid_tokens))) return rc;
-    StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = t.mx ? t.max_forward() : t.forward()) || (rc = t.loss()) ||
-        (rc = t.mx ? t.max_backward() : t.backward()) || (rc = t.gradients())) return rc;
-    FARNN_HIP_TRY(hipGetLastError());
-    c->prof.end(t.s);
-    return FARNN_OK;
+    TunScope tun_scope(c ? &c->tun : nullptr);     // (a null context: run_train_step refuses it)
+    return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- training step of the onehot i-FST (FARNN_S_O_I_S; onehot_train.hip.h) -------------------------------
-struct farnn_onehot_train_ctx {
+struct farnn_onehot_train_ctx : TrainCtxBase {
     farnn_onehot_train_dims d;
-    int device = 0;
     int n_cu = 256;
     int semiring = FARNN_SEMIRING_SUM;  // farnn_onehot_train_set_semiring
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, MT, o, loss partials, dT partial tiles; the max
                                   // semiring's index and winning-entry stashes behind them (grown by the first max step)
     DevBuf<int> iws;              // per-batch int workspace: bucket counts / offsets, per-word tables, the sorted positions
-    StepProfile prof;
-    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
 };
 
 extern "C" int farnn_onehot_train_create(const farnn_onehot_train_dims *d, int device, farnn_onehot_train_ctx **out) {
@@ -482,26 +459,16 @@ extern "C" int farnn_onehot_train_create(const farnn_onehot_train_dims *d, int d
     if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "onehot_train_create: more than 128 states%s%s");
     // the loss kernel keeps output_mat or reads it through L2; its per-wavefront vectors must fit
     if (train_loss_lds(d->S, d->C).vec > 150 * 1024) return fail(FARNN_ERANGE, "onehot_train_create: too many score columns%s%s");
-    int rc;
-    if ((rc = select_device(device))) return rc;
-    farnn_onehot_train_ctx *c = new farnn_onehot_train_ctx();
-    c->d = *d; c->device = device; c->n_cu = device_cus(device);
-    if (!c->err.create()) { farnn_onehot_train_destroy(c); return fail(FARNN_ENOMEM, "onehot_train_create: out of memory%s%s"); }
-    *out = c;
+    if (int rc = train_ctx_create("onehot_train", d, device, out)) return rc;
+    (*out)->n_cu = device_cus(device);
     return FARNN_OK;
 }
-
-extern "C" void farnn_onehot_train_destroy(farnn_onehot_train_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    delete c;
-}
-
+extern "C" void farnn_onehot_train_destroy(farnn_onehot_train_ctx *c) { train_ctx_destroy(c); }
 extern "C" int farnn_onehot_train_set_profiling(farnn_onehot_train_ctx *c, int32_t enable) {
-    if (!c) return fail(FARNN_EINVAL, "onehot_train_set_profiling: null context%s%s");
-    c->prof.enabled = enable;
-    return FARNN_OK;
+    return train_ctx_set_profiling("onehot_train", c, enable);
+}
+extern "C" int farnn_onehot_train_time(farnn_onehot_train_ctx *c, double *total_ms, int64_t *steps) {
+    return train_ctx_time("onehot_train", c, total_ms, steps);
 }
 
 extern "C" int farnn_onehot_train_set_semiring(farnn_onehot_train_ctx *c, int32_t semiring) {
@@ -511,82 +478,89 @@ extern "C" int farnn_onehot_train_set_semiring(farnn_onehot_train_ctx *c, int32_
     c->semiring = semiring;
     return FARNN_OK;
 }
-
-extern "C" int farnn_onehot_train_time(farnn_onehot_train_ctx *c, double *total_ms, int64_t *steps) {
-    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "onehot_train_time: null argument%s%s");
-    return c->prof.time(c->device, total_ms, steps);
-}
-// One step: the plan (onehot_plan: sizes from the dimensions alone) and what the stages hand on
+// One step: the plan (sizes from the dimensions alone) and what the stages hand on
 struct OhStep {
+    static constexpr const char *name = "onehot_train", *label_range = "C";
     bool mx;                      // the max semiring (onehot_train_max.hip.h): its own chain, BPTT and dT stages
     int B, L;
     size_t S, K, V, N1, N0;
     unsigned lgrid;               // workgroups of the loss kernel
-    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_onehot_ws / carve_onehot_ints
+    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_ws / carve_bucket_ints
     size_t lds_tok, lds_mdt;      // LDS bytes of the chain kernels and of the max semiring's dT kernel
     farnn_onehot_train_ctx *c; const farnn_onehot_train_weights *w; const farnn_onehot_train_outputs *o; hipStream_t s;
     OhTrainParams q;
     OhMaxParams mq;
+    TrainParams p;                // of the loss kernel
     float *DS, *AB, *M, *MT, *osum, *loss_part, *partial;
     Buckets bk;
-    int carve(const int64_t *x, const int64_t *lengths);
-    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int dT();
-    template <bool BPTT> int chains();
-    int max_chains(); int max_dT();
+    size_t carve_ws(float *base);
+    int validate(); int plan(int B, int L);
+    int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
+    int prepare(); int loss(); int max_chains(); int max_dT(); int stages();
+    template <bool BPTT> int chains() { return launch_onehot_chains<BPTT>(q, lds_tok, s); }
     int max_bptt() { return launch(onehot_max_bptt_kernel, dim3(B, 2), OT_THREADS, 0, s, q, mq); }
+    int dT() { return launch_onehot_dT(q, bk, o->dT, partial, s); }
 };
 
-static size_t carve_onehot_ws(float *base, OhStep &t) {
+size_t OhStep::carve_ws(float *base) {
     Carver<float> a(base);
-    const size_t nS = t.N1 * t.S, SS = t.S * t.S;
-    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
-    t.DS = a.take(t.N0 * t.K); t.AB = a.take(t.N0 * t.S);
-    t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS);
-    t.osum = a.take((t.S + 3) & ~(size_t)3);
-    t.loss_part = a.take((size_t)t.lgrid * 8);
-    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // partial tiles of the words with several runs
-    if (t.mx) {
+    const size_t nS = N1 * S, SS = S * S;
+    q.A = a.take(nS); q.Bk = a.take(nS); q.GA = a.take(nS); q.GB = a.take(nS); q.UF = a.take(nS); q.DQ = a.take(nS);
+    DS = a.take(N0 * K); AB = a.take(N0 * S);
+    M = a.take(V * SS); MT = a.take(V * SS);
+    osum = a.take((S + 3) & ~(size_t)3);
+    loss_part = a.take((size_t)lgrid * 8);
+    partial = a.take((2 * ((N0 + OT_G - 1) / OT_G) + 1) * SS);      // partial tiles of the words with several runs
+    if (mx) {
         // the max semiring, behind everything the sum step lays out: the winning entries, and the indices as bytes.  The
         // per-step dM entries take the rows the sum step's BPTT writes (UF, DQ), which the max step does not use.
-        t.mq.WINf = a.take(nS); t.mq.WINb = a.take(nS);
-        t.mq.IDXf = (uint8_t *)a.take((nS + 3) / 4); t.mq.IDXb = (uint8_t *)a.take((nS + 3) / 4);
-        t.mq.GMf = t.q.UF; t.mq.GMb = t.q.DQ;
+        mq.WINf = a.take(nS); mq.WINb = a.take(nS);
+        mq.IDXf = (uint8_t *)a.take((nS + 3) / 4); mq.IDXb = (uint8_t *)a.take((nS + 3) / 4);
+        mq.GMf = q.UF; mq.GMb = q.DQ;
     }
     return a.off;
 }
-static size_t carve_onehot_ints(int *base, OhStep &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
-
-// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
-static int onehot_plan(const farnn_onehot_train_ctx *c, int B, int L, OhStep &t) {
+// Stage 1: the arguments
+int OhStep::validate() {
+    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "onehot_train_step: null weight%s%s");
+    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "onehot_train_step: null output%s%s");
+    return FARNN_OK;
+}
+// Stage 2: host arithmetic only; every size the step refuses is refused here, before anything is enqueued
+int OhStep::plan(int B_, int L_) {
     // positions are 32-bit flat indices b L + i in the bucketing and dT kernels
-    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "onehot_train_step: B (L+1) must stay below 2^30%s%s");
-    t.mx = c->semiring == FARNN_SEMIRING_MAX;
-    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
-    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
+    if ((unsigned long long)B_ * (L_ + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "onehot_train_step: B (L+1) must stay below 2^30%s%s");
+    mx = c->semiring == FARNN_SEMIRING_MAX;
+    B = B_; L = L_; S = c->d.S; K = c->d.C; V = c->d.V;
+    N1 = (size_t)B * (L + 1); N0 = (size_t)B * L;
     // the loss kernel's persistent workgroups: three per compute unit (48 KiB of LDS each at ATIS size; one per unit left
     // the position loop latency-bound: 127 us)
-    t.lgrid = (unsigned)std::min<size_t>(3 * (size_t)c->n_cu, (t.N0 + 7) / 8);
-    t.lds_tok = (size_t)(L + 1) * sizeof(int); t.lds_mdt = onehot_max_dT_lds_bytes(t.S);
-    t.need = carve_onehot_ws(nullptr, t); t.ineed = carve_onehot_ints(nullptr, t);
-    if (int rc = lds_fits(t.lds_tok)) return rc;
-    return t.mx ? lds_fits(t.lds_mdt) : FARNN_OK;
+    lgrid = (unsigned)std::min<size_t>(3 * (size_t)c->n_cu, (N0 + 7) / 8);
+    lds_tok = (size_t)(L + 1) * sizeof(int); lds_mdt = onehot_max_dT_lds_bytes(S);
+    need = carve_ws(nullptr); ineed = carve_bucket_ints(nullptr, bk, V, N0);
+    if (int rc = lds_fits(lds_tok)) return rc;
+    return mx ? lds_fits(lds_mdt) : FARNN_OK;
 }
-// Stage 3: grow the buffers, lay the workspaces out, fill the chain kernels' parameters
-int OhStep::carve(const int64_t *x, const int64_t *lengths) {
-    int rc;
-    if ((rc = c->ws.ensure(need, "onehot_train_step: out of device memory for the workspace%s%s")) ||
-        (rc = c->iws.ensure(ineed, "onehot_train_step: out of device memory for the index workspace%s%s"))) return rc;
-    [[maybe_unused]] const size_t carved = carve_onehot_ws(c->ws.p, *this), icarved = carve_onehot_ints(c->iws.p, *this);
+// Stage 3: grow the buffers, lay the workspaces out, fill the chain and the loss kernels' parameters (the loss kernel is the
+// decomposed step's, PHASE 0, with output_mat in C_output_mat's place and the loss as per-wavefront partials)
+int OhStep::carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens) {
+    if (int rc = grow_workspaces(name, c, need, ineed)) return rc;
+    [[maybe_unused]] const size_t carved = carve_ws(c->ws.p), icarved = carve_bucket_ints(c->iws.p, bk, V, N0);
     assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
     q.M = M; q.MT = MT; q.o = osum; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
     q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = c->d.nl;
+    p.C = w->O; p.P = w->P; p.len = q.len; p.labels = labels; p.err = c->err.dev;
+    p.A = q.A; p.Bk = q.Bk; p.GA = q.GA; p.GB = q.GB; p.DS = DS; p.AB = AB;
+    p.loss = o->loss; p.loss_part = loss_part; p.tags = o->tags;
+    p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
+    p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
     return FARNN_OK;
 }
 // Stages 4 and 5: o = output_mat.sum(0), M_w = T[w] + W and its transpose, the positions bucketed by word.  Every workspace
 // entry a kernel reads is written by an earlier kernel of this step (the chains write the stash rows 0..len, the loss kernel
 // the adjoint rows of every valid position): only the bucket counts are zeroed
 int OhStep::prepare() {
-    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    if (int rc = clear_bucket_counts(bk, V, N0, s)) return rc;
     PrepJobs pj = {};
     prep_add(pj, 2, w->O, osum, K, S);              // o = output_mat.sum(0)
     train_prep_kernel<<<(pj.total + 255) / 256, 256, 0, s>>>(pj);
@@ -594,46 +568,16 @@ int OhStep::prepare() {
     onehot_premix_kernel<<<(unsigned)V * nt * nt, 256, 0, s>>>(w->T, w->W, M, MT, (int)S);
     return launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s);
 }
-// Stages 6 and 8: both chains (BPTT = false: with the state stash; true: back-propagation through time), rows per share by S
-template <bool BPTT>
-static int launch_onehot_chains(const OhTrainParams &q, size_t lds_tok, hipStream_t s) {
-    auto go = [&](auto RS) { return launch(onehot_train_chain_kernel<RS(), BPTT>, dim3(q.B, 2), OT_THREADS, lds_tok, s, q); };
-    return q.S <= 64 ? go(int_c<8>()) : q.S <= 72 ? go(int_c<18>()) : q.S <= 96 ? go(int_c<24>()) : go(int_c<32>());
-}
-template <bool BPTT>
-int OhStep::chains() { return launch_onehot_chains<BPTT>(q, lds_tok, s); }
 // Stage 6, max semiring: both chains with the state, arg-max index and winning-entry stash (the sum kernel's register slots by S)
 int OhStep::max_chains() {
-    auto go = [&](auto RS) { return launch(onehot_max_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_tok, s, q, mq); };
-    return S <= 64 ? go(int_c<8>()) : S <= 72 ? go(int_c<18>()) : S <= 96 ? go(int_c<24>()) : go(int_c<32>());
+    return with_chain_slots(S, [&](auto RS) { return launch(onehot_max_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_tok, s, q, mq); });
 }
-// Stage 7: scores, cross-entropy, decode, d loss / d alpha, d loss / d beta: the decomposed step's kernel (PHASE 0) with
-// output_mat in C_output_mat's place, the loss as per-wavefront partials
-int OhStep::loss(const int64_t *labels, int64_t valid_tokens) {
-    TrainParams p = {};
-    p.C = w->O; p.P = w->P; p.len = q.len; p.labels = labels; p.err = c->err.dev;
-    p.A = q.A; p.Bk = q.Bk; p.GA = q.GA; p.GB = q.GB; p.DS = DS; p.AB = AB;
-    p.loss = o->loss; p.loss_part = loss_part; p.tags = o->tags;
-    p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
-    p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
+// Stage 7: scores, cross-entropy, decode, d loss / d alpha, d loss / d beta
+int OhStep::loss() {
     if (int rc = launch_train_loss<0>(p, lgrid, s)) return rc;
-    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    launch_loss_sum(loss_part, lgrid, o->loss, s);
     return FARNN_OK;
 }
-// Stage 9: d loss / d language_tensor, word by word from the sorted positions; tiles per workgroup by S
-static int launch_onehot_dT(const OhTrainParams &q, const Buckets &bk, float *dT, float *partial, hipStream_t s) {
-    const size_t V = q.V, S = q.S, N0 = (size_t)q.B * q.L;
-    const unsigned ngrid = (unsigned)(V + (N0 + OT_G - 1) / OT_G);   // bound on the runs: sum_w max(1, ceil(n_w / G))
-    auto go = [&](auto NT) {
-        return launch(onehot_dT_kernel<NT()>, ngrid, 256, 4 * (size_t)OT_G * S * sizeof(float), s, q, bk.list, bk.wstart, bk.wcount,
-                      bk.itoff, bk.psoff, dT, partial);
-    };
-    if (int rc = S <= 32 ? go(int_c<2>()) : S <= 64 ? go(int_c<4>()) : S <= 96 ? go(int_c<6>()) : go(int_c<8>())) return rc;
-    onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((S * S + 255) / 256)), 256, 0, s>>>(bk.itoff, bk.psoff, partial, dT, (int)S);
-    return FARNN_OK;
-}
-int OhStep::dT() { return launch_onehot_dT(q, bk, o->dT, partial, s); }
-
 // Stage 9, max semiring: the per-step dM entries added per word in bucket order, the sum step's runs and its reduction
 int OhStep::max_dT() {
     const unsigned ngrid = (unsigned)(V + (N0 + OT_G - 1) / OT_G);
@@ -642,39 +586,24 @@ int OhStep::max_dT() {
     onehot_dT_reduce_kernel<<<dim3((unsigned)V, (unsigned)((S * S + 255) / 256)), 256, 0, s>>>(bk.itoff, bk.psoff, partial, o->dT, (int)S);
     return FARNN_OK;
 }
+// Stages 4 to 9 (6 and 8: both chains, with the state stash, then back-propagation through time; 9: d loss / d language_tensor)
+int OhStep::stages() {
+    int rc;
+    if ((rc = prepare()) || (rc = mx ? max_chains() : chains<false>()) || (rc = loss())) return rc;
+    return (rc = mx ? max_bptt() : chains<true>()) ? rc : mx ? max_dT() : dT();
+}
 
 extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const farnn_onehot_train_weights *w, const int64_t *x,
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_onehot_train_outputs *o, void *stream) {
-    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "onehot_train_step: null argument%s%s");
-    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "onehot_train_step: null weight%s%s");
-    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "onehot_train_step: null output%s%s");
-    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "onehot_train_step: B, L and valid_tokens must be positive%s%s");
-    OhStep t = {};
-    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
-    int rc, bad = 0;
-    if ((rc = onehot_plan(c, B, L, t))) return rc;
-    FARNN_HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->err.take(t.s, &bad))) return rc;
-    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "onehot_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
-                                                 : "onehot_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
-    if ((rc = t.carve(x, lengths))) return rc;
-    StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = t.mx ? t.max_chains() : t.chains<false>()) || (rc = t.loss(labels, valid_tokens)) ||
-        (rc = t.mx ? t.max_bptt() : t.chains<true>()) || (rc = t.mx ? t.max_dT() : t.dT())) return rc;
-    FARNN_HIP_TRY(hipGetLastError());
-    c->prof.end(t.s);
-    return FARNN_OK;
+    return run_train_step<OhStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- training step of the onehot FST (FARNN_S_O; fst4_train.hip.h) ----------------------------------------
-struct farnn_fst4_train_ctx {
+struct farnn_fst4_train_ctx : TrainCtxBase {
     farnn_fst4_train_dims d;
-    int device = 0;
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, M / MT / dM, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
-    StepProfile prof;
-    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
 };
 
 extern "C" int farnn_fst4_train_create(const farnn_fst4_train_dims *d, int device, farnn_fst4_train_ctx **out) {
@@ -687,95 +616,55 @@ extern "C" int farnn_fst4_train_create(const farnn_fst4_train_dims *d, int devic
     // byte offsets into [V][C][S][S] stay inside 63 bits
     if ((unsigned long long)d->V * (unsigned long long)d->C > (1ull << 47))
         return fail(FARNN_ERANGE, "fst4_train_create: V C S S is not addressable%s%s");
-    int rc;
-    if ((rc = select_device(device))) return rc;
-    farnn_fst4_train_ctx *c = new farnn_fst4_train_ctx();
-    c->d = *d; c->device = device;
-    if (!c->err.create()) { farnn_fst4_train_destroy(c); return fail(FARNN_ENOMEM, "fst4_train_create: out of memory%s%s"); }
-    *out = c;
-    return FARNN_OK;
+    return train_ctx_create("fst4_train", d, device, out);
 }
-
-extern "C" void farnn_fst4_train_destroy(farnn_fst4_train_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    delete c;
-}
-
+extern "C" void farnn_fst4_train_destroy(farnn_fst4_train_ctx *c) { train_ctx_destroy(c); }
 extern "C" int farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *c, int32_t enable) {
-    if (!c) return fail(FARNN_EINVAL, "fst4_train_set_profiling: null context%s%s");
-    c->prof.enabled = enable;
-    return FARNN_OK;
+    return train_ctx_set_profiling("fst4_train", c, enable);
 }
-
 extern "C" int farnn_fst4_train_time(farnn_fst4_train_ctx *c, double *total_ms, int64_t *steps) {
-    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "fst4_train_time: null argument%s%s");
-    return c->prof.time(c->device, total_ms, steps);
+    return train_ctx_time("fst4_train", c, total_ms, steps);
 }
 
-// One step: the plan (fst4_plan: sizes from the dimensions alone) and what the stages hand on
-struct Fst4Step {
-    int B, L, ngrp, cpg;          // label groups per word of the score kernels, label columns per group
-    size_t S, K, V, N1, N0;
-    unsigned lgrid;               // workgroups of the loss kernel
-    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_fst4_ws / carve_fst4_ints
-    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
-    farnn_fst4_train_ctx *c; const farnn_fst4_train_weights *w; const farnn_fst4_train_outputs *o; hipStream_t s;
-    OhTrainParams q;
-    Fst4TrainParams f;
-    float *SC, *DS, *M, *MT, *dM, *Wsum, *ones, *loss_part, *partial, *part;
-    Buckets bk;
-    int carve(const int64_t *x, const int64_t *lengths);
-    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words(); int wildcard();
+// One step (BucketedStep, train_bucketed.hip.h); the groups of its score kernels divide the label columns
+struct Fst4Step : BucketedStep<farnn_fst4_train_ctx, farnn_fst4_train_weights, farnn_fst4_train_outputs, Fst4TrainParams> {
+    static constexpr const char *name = "fst4_train", *label_range = "C";
+    float *Wsum;
+    size_t carve_ws(float *base);
+    int validate(); int plan(int B, int L);
+    int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
+    int prepare(); int wildcard(); int stages();
     template <int MODE> int scores();
 };
 
-static size_t carve_fst4_ws(float *base, Fst4Step &t) {
+size_t Fst4Step::carve_ws(float *base) {
     Carver<float> a(base);
-    const size_t nS = t.N1 * t.S, SS = t.S * t.S;
-    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
-    t.SC = a.take(t.N0 * t.K); t.DS = a.take(t.N0 * t.K);
-    t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS);
-    t.Wsum = a.take((SS + 3) & ~(size_t)3);
-    t.ones = a.take((t.S + 3) & ~(size_t)3);
-    t.loss_part = a.take((size_t)t.lgrid * 8);
-    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dM: partial tiles of the words with several runs
-    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and label group
+    const size_t SS = S * S;
+    carve_head(a);
+    SC = a.take(N0 * K); DS = a.take(N0 * K);
+    M = a.take(V * SS); MT = a.take(V * SS); dM = a.take(V * SS);
+    Wsum = a.take((SS + 3) & ~(size_t)3);
+    carve_tail(a);
     return a.off;
 }
-static size_t carve_fst4_ints(int *base, Fst4Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
-
-// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
-static int fst4_plan(const farnn_fst4_train_ctx *c, int B, int L, Fst4Step &t) {
-    // positions are 32-bit flat indices b L + i in the bucketing, dM and score kernels
-    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "fst4_train_step: B (L+1) must stay below 2^30%s%s");
-    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
-    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
-    // a word's label columns are split over enough workgroups to fill the chip when the batch has few distinct words
-    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.K, (size_t)F4_MAX_GROUPS});
-    t.cpg = (int)((t.K + want - 1) / want); t.ngrp = (int)((t.K + t.cpg - 1) / t.cpg);
-    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
-    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
-    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
-    t.lds_tok = (size_t)(L + 1) * sizeof(int);
-    t.lds_sc = fst4_train_lds_floats(SP, CPR, GW) * sizeof(float);
-    t.lds_loss = fst4_loss_lds_bytes(t.K);
-    t.need = carve_fst4_ws(nullptr, t); t.ineed = carve_fst4_ints(nullptr, t);
-    int rc;
-    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
-    return lds_fits(t.lds_loss);
+// Stage 1: the arguments
+int Fst4Step::validate() {
+    if (!w->T4 || !w->W4 || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "fst4_train_step: null weight%s%s");
+    if (!o->loss || !o->dT4 || !o->tags) return fail(FARNN_EINVAL, "fst4_train_step: null output%s%s");
+    return FARNN_OK;
+}
+int Fst4Step::plan(int B_, int L_) {
+    if (int rc = plan_bucketed(name, B_, L_, c->d.C, fst4_train_lds_floats)) return rc;
+    need = carve_ws(nullptr);
+    return FARNN_OK;
 }
 // Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
-int Fst4Step::carve(const int64_t *x, const int64_t *lengths) {
-    int rc;
-    if ((rc = c->ws.ensure(need, "fst4_train_step: out of device memory for the workspace%s%s")) ||
-        (rc = c->iws.ensure(ineed, "fst4_train_step: out of device memory for the index workspace%s%s"))) return rc;
-    [[maybe_unused]] const size_t carved = carve_fst4_ws(c->ws.p, *this), icarved = carve_fst4_ints(c->iws.p, *this);
-    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
-    // the chains always use relu and have no output mask (model_onehot.py:93-94, :100-101): a mask of ones
-    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
-    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = FARNN_NL_RELU;
+int Fst4Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *labels_, int64_t valid_tokens) {
+    if (int rc = grow_workspaces(name, c, need, ineed)) return rc;
+    [[maybe_unused]] const size_t carved = carve_ws(c->ws.p);
+    assert(carved == need);     // the sizing pass and the carving pass agree
+    // the chains always use relu and have no output mask (model_onehot.py:93-94, :100-101)
+    carve_bucketed(x, lengths, labels_, valid_tokens, FARNN_NL_RELU);
     f.T4 = w->T4; f.W4 = w->W4; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
     f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
     f.SC = SC; f.DS = DS; f.part = part; f.dM = dM; f.dT4 = o->dT4;
@@ -785,9 +674,8 @@ int Fst4Step::carve(const int64_t *x, const int64_t *lengths) {
 // Stages 4 and 5: the positions bucketed by word; W4.sum(0); M[w] = T4[w].sum(0) + W4.sum(0) and its transpose for the words of
 // the batch only (the bucket counts say which: the blocks of the other words are never read)
 int Fst4Step::prepare() {
-    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
-    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
-    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    int rc;
+    if ((rc = clear_bucket_counts(bk, V, N0, s)) || (rc = bucket_and_fill())) return rc;
     const unsigned nt = (unsigned)((S + 31) / 32);
     fst4_premix_kernel<<<dim3(1, nt * nt), 256, 0, s>>>(w->W4, nullptr, nullptr, Wsum, nullptr, (int)S, (int)K);
     fst4_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(w->T4, Wsum, bk.wcount, M, MT, (int)S, (int)K);
@@ -797,26 +685,10 @@ int Fst4Step::prepare() {
 // register rows per thread by S
 template <int MODE>
 int Fst4Step::scores() {
-    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
-    auto go = [&](auto RPT) { return launch(fst4_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), F4_THREADS, lds_sc, s, f); };
-    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
-                                                                                                             : go(int_c<16>());
+    return with_rows_per_thread(S, f.GW, [&](auto RPT) {
+        return launch(fst4_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), F4_THREADS, lds_sc, s, f);
+    });
 }
-// Stage 8: priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront partials
-int Fst4Step::loss(const int64_t *labels, int64_t valid_tokens) {
-    if (int rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
-                        (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens)) return rc;
-    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
-    return FARNN_OK;
-}
-// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the label groups' partials added in group order
-int Fst4Step::adjoints() {
-    if (int rc = scores<1>()) return rc;
-    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
-    return FARNN_OK;
-}
-// Stage 11: dM[w] of the chains, the i-FST step's per-word reduction
-int Fst4Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
 // Stage 13 (asked for): d loss / d wildcard_tensor
 int Fst4Step::wildcard() {
     if (!o->dW4) return FARNN_OK;
@@ -824,40 +696,25 @@ int Fst4Step::wildcard() {
     fst4_dW_kernel<<<(unsigned)((CSS + 255) / 256), 256, 0, s>>>(o->dT4, bk.wcount, o->dW4, (int)V, CSS);
     return FARNN_OK;
 }
+// Stages 4 to 13 (6 and 10: both chains, with the state stash, then back-propagation through time)
+int Fst4Step::stages() {
+    int rc;
+    if ((rc = prepare()) || (rc = chains<false>()) || (rc = scores<0>()) || (rc = loss_on_scores()) ||
+        (rc = adjoints([&] { return scores<1>(); })) || (rc = chains<true>()) || (rc = dM_words()) || (rc = scores<2>())) return rc;
+    return wildcard();
+}
 
 extern "C" int farnn_fst4_train_step(farnn_fst4_train_ctx *c, const farnn_fst4_train_weights *w, const int64_t *x,
                                      const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                      int64_t valid_tokens, const farnn_fst4_train_outputs *o, void *stream) {
-    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "fst4_train_step: null argument%s%s");
-    if (!w->T4 || !w->W4 || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "fst4_train_step: null weight%s%s");
-    if (!o->loss || !o->dT4 || !o->tags) return fail(FARNN_EINVAL, "fst4_train_step: null output%s%s");
-    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "fst4_train_step: B, L and valid_tokens must be positive%s%s");
-    Fst4Step t = {};
-    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
-    int rc, bad = 0;
-    if ((rc = fst4_plan(c, B, L, t))) return rc;
-    FARNN_HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->err.take(t.s, &bad))) return rc;
-    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "fst4_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
-                                                 : "fst4_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
-    if ((rc = t.carve(x, lengths))) return rc;
-    StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
-        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
-        (rc = t.dM_words()) || (rc = t.scores<2>()) || (rc = t.wildcard())) return rc;
-    FARNN_HIP_TRY(hipGetLastError());
-    c->prof.end(t.s);
-    return FARNN_OK;
+    return run_train_step<Fst4Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- training step of the onehot independent=1 model (FARNN_S_O_I; ind1_train.hip.h) ----------------------
-struct farnn_ind1_train_ctx {
+struct farnn_ind1_train_ctx : TrainCtxBase {
     farnn_ind1_train_dims d;
-    int device = 0;
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, Mc / McT / dMc, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
-    StepProfile prof;
-    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
 };
 
 extern "C" int farnn_ind1_train_create(const farnn_ind1_train_dims *d, int device, farnn_ind1_train_ctx **out) {
@@ -867,95 +724,55 @@ extern "C" int farnn_ind1_train_create(const farnn_ind1_train_dims *d, int devic
     if (d->S > OT_MAX_S) return fail(FARNN_ERANGE, "ind1_train_create: more than 128 states%s%s");
     // fst4_loss_kernel keeps two score vectors per wavefront in LDS (fst4_loss_lds_bytes): C <= 2400
     if (fst4_loss_lds_bytes(d->C) > 150 * 1024) return fail(FARNN_ERANGE, "ind1_train_create: too many score columns%s%s");
-    int rc;
-    if ((rc = select_device(device))) return rc;
-    farnn_ind1_train_ctx *c = new farnn_ind1_train_ctx();
-    c->d = *d; c->device = device;
-    if (!c->err.create()) { farnn_ind1_train_destroy(c); return fail(FARNN_ENOMEM, "ind1_train_create: out of memory%s%s"); }
-    *out = c;
-    return FARNN_OK;
+    return train_ctx_create("ind1_train", d, device, out);
 }
-
-extern "C" void farnn_ind1_train_destroy(farnn_ind1_train_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    delete c;
-}
-
+extern "C" void farnn_ind1_train_destroy(farnn_ind1_train_ctx *c) { train_ctx_destroy(c); }
 extern "C" int farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *c, int32_t enable) {
-    if (!c) return fail(FARNN_EINVAL, "ind1_train_set_profiling: null context%s%s");
-    c->prof.enabled = enable;
-    return FARNN_OK;
+    return train_ctx_set_profiling("ind1_train", c, enable);
 }
-
 extern "C" int farnn_ind1_train_time(farnn_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
-    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "ind1_train_time: null argument%s%s");
-    return c->prof.time(c->device, total_ms, steps);
+    return train_ctx_time("ind1_train", c, total_ms, steps);
 }
 
-// One step: the plan (ind1_plan: sizes from the dimensions alone) and what the stages hand on
-struct Ind1Step {
-    int B, L, ngrp, cpg;          // label groups per word of the score kernel's MODE 0 and 1, label columns per group
-    size_t S, K, V, N1, N0;
-    unsigned lgrid;               // workgroups of the loss kernel
-    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_ind1_ws / carve_ind1_ints
-    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
-    farnn_ind1_train_ctx *c; const farnn_ind1_train_weights *w; const farnn_ind1_train_outputs *o; hipStream_t s;
-    OhTrainParams q;
-    Ind1TrainParams f;
-    float *SC, *DS, *M, *MT, *dM, *Osum, *ones, *loss_part, *partial, *part;
-    Buckets bk;
-    int carve(const int64_t *x, const int64_t *lengths);
-    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words();
+// One step (BucketedStep); the groups of its score kernel's MODE 0 and 1 divide the label columns
+struct Ind1Step : BucketedStep<farnn_ind1_train_ctx, farnn_ind1_train_weights, farnn_ind1_train_outputs, Ind1TrainParams> {
+    static constexpr const char *name = "ind1_train", *label_range = "C";
+    float *Osum;
+    size_t carve_ws(float *base);
+    int validate(); int plan(int B, int L);
+    int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
+    int prepare(); int stages();
     template <int MODE> int scores();
 };
 
-static size_t carve_ind1_ws(float *base, Ind1Step &t) {
+size_t Ind1Step::carve_ws(float *base) {
     Carver<float> a(base);
-    const size_t nS = t.N1 * t.S, SS = t.S * t.S;
-    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
-    t.SC = a.take(t.N0 * t.K); t.DS = a.take(t.N0 * t.K);
-    t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS);
-    t.Osum = a.take((SS + 3) & ~(size_t)3);
-    t.ones = a.take((t.S + 3) & ~(size_t)3);
-    t.loss_part = a.take((size_t)t.lgrid * 8);
-    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dMc: partial tiles of the words with several runs
-    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and label group
+    const size_t SS = S * S;
+    carve_head(a);
+    SC = a.take(N0 * K); DS = a.take(N0 * K);
+    M = a.take(V * SS); MT = a.take(V * SS); dM = a.take(V * SS);
+    Osum = a.take((SS + 3) & ~(size_t)3);
+    carve_tail(a);
     return a.off;
 }
-static size_t carve_ind1_ints(int *base, Ind1Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
-
-// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
-static int ind1_plan(const farnn_ind1_train_ctx *c, int B, int L, Ind1Step &t) {
-    // positions are 32-bit flat indices b L + i in the bucketing, dMc and score kernels
-    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "ind1_train_step: B (L+1) must stay below 2^30%s%s");
-    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V;
-    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
-    // a word's label columns are split over enough workgroups to fill the chip when the batch has few distinct words
-    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.K, (size_t)F4_MAX_GROUPS});
-    t.cpg = (int)((t.K + want - 1) / want); t.ngrp = (int)((t.K + t.cpg - 1) / t.cpg);
-    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
-    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
-    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
-    t.lds_tok = (size_t)(L + 1) * sizeof(int);
-    t.lds_sc = ind1_train_lds_floats(SP, CPR, GW) * sizeof(float);
-    t.lds_loss = fst4_loss_lds_bytes(t.K);
-    t.need = carve_ind1_ws(nullptr, t); t.ineed = carve_ind1_ints(nullptr, t);
-    int rc;
-    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
-    return lds_fits(t.lds_loss);
+// Stage 1: the arguments
+int Ind1Step::validate() {
+    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "ind1_train_step: null weight%s%s");
+    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "ind1_train_step: null output%s%s");
+    return FARNN_OK;
+}
+int Ind1Step::plan(int B_, int L_) {
+    if (int rc = plan_bucketed(name, B_, L_, c->d.C, ind1_train_lds_floats)) return rc;
+    need = carve_ws(nullptr);
+    return FARNN_OK;
 }
 // Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
-int Ind1Step::carve(const int64_t *x, const int64_t *lengths) {
-    int rc;
-    if ((rc = c->ws.ensure(need, "ind1_train_step: out of device memory for the workspace%s%s")) ||
-        (rc = c->iws.ensure(ineed, "ind1_train_step: out of device memory for the index workspace%s%s"))) return rc;
-    [[maybe_unused]] const size_t carved = carve_ind1_ws(c->ws.p, *this), icarved = carve_ind1_ints(c->iws.p, *this);
-    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
-    // the chains always use relu (model_onehot.py:266, :278); the output mask is premixed into Mc: a mask of ones
-    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
-    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = FARNN_NL_RELU;
+int Ind1Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *labels_, int64_t valid_tokens) {
+    if (int rc = grow_workspaces(name, c, need, ineed)) return rc;
+    [[maybe_unused]] const size_t carved = carve_ws(c->ws.p);
+    assert(carved == need);     // the sizing pass and the carving pass agree
+    // the chains always use relu (model_onehot.py:266, :278); the output mask is premixed into Mc
+    carve_bucketed(x, lengths, labels_, valid_tokens, FARNN_NL_RELU);
     f.T = w->T; f.W = w->W; f.O = w->O; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
     f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
     f.SC = SC; f.DS = DS; f.part = part; f.dMc = dM; f.Osum = Osum; f.dT = o->dT;
@@ -965,9 +782,8 @@ int Ind1Step::carve(const int64_t *x, const int64_t *lengths) {
 // Stages 4 and 5: the positions bucketed by word; with the mask Osum = output_tensor.sum(0); Mc[w] = (T[w] + W) (* Osum) and its
 // transpose for the words of the batch only (the bucket counts say which: the blocks of the other words are never read)
 int Ind1Step::prepare() {
-    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
-    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
-    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    int rc;
+    if ((rc = clear_bucket_counts(bk, V, N0, s)) || (rc = bucket_and_fill())) return rc;
     const unsigned nt = (unsigned)((S + 31) / 32);
     if (f.mask) fst4_premix_kernel<<<dim3(1, nt * nt), 256, 0, s>>>(w->O, nullptr, nullptr, Osum, nullptr, (int)S, (int)K);
     ind1_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(w->T, w->W, f.mask ? Osum : nullptr, bk.wcount, M, MT, (int)S);
@@ -977,63 +793,30 @@ int Ind1Step::prepare() {
 // labels of a word in one workgroup); register rows per thread by S
 template <int MODE>
 int Ind1Step::scores() {
-    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
-    auto go = [&](auto RPT) {
+    return with_rows_per_thread(S, f.GW, [&](auto RPT) {
         return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, MODE == 2 ? 1 : ngrp), I1_THREADS, lds_sc, s, f);
-    };
-    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
-                                                                                                             : go(int_c<16>());
+    });
 }
-// Stage 8: priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront partials
-int Ind1Step::loss(const int64_t *labels, int64_t valid_tokens) {
-    if (int rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
-                        (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens)) return rc;
-    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
-    return FARNN_OK;
+// Stages 4 to 12 (6 and 10: both chains, with the state stash, then back-propagation through time)
+int Ind1Step::stages() {
+    int rc;
+    if ((rc = prepare()) || (rc = chains<false>()) || (rc = scores<0>()) || (rc = loss_on_scores()) ||
+        (rc = adjoints([&] { return scores<1>(); })) || (rc = chains<true>()) || (rc = dM_words())) return rc;
+    return scores<2>();
 }
-// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the label groups' partials added in group order
-int Ind1Step::adjoints() {
-    if (int rc = scores<1>()) return rc;
-    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
-    return FARNN_OK;
-}
-// Stage 11: dMc[w] of the chains, the i-FST step's per-word reduction
-int Ind1Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
 
 extern "C" int farnn_ind1_train_step(farnn_ind1_train_ctx *c, const farnn_ind1_train_weights *w, const int64_t *x,
                                      const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                      int64_t valid_tokens, const farnn_ind1_train_outputs *o, void *stream) {
-    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "ind1_train_step: null argument%s%s");
-    if (!w->T || !w->W || !w->O || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "ind1_train_step: null weight%s%s");
-    if (!o->loss || !o->dT || !o->tags) return fail(FARNN_EINVAL, "ind1_train_step: null output%s%s");
-    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "ind1_train_step: B, L and valid_tokens must be positive%s%s");
-    Ind1Step t = {};
-    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
-    int rc, bad = 0;
-    if ((rc = ind1_plan(c, B, L, t))) return rc;
-    FARNN_HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->err.take(t.s, &bad))) return rc;
-    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "ind1_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
-                                                 : "ind1_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
-    if ((rc = t.carve(x, lengths))) return rc;
-    StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
-        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
-        (rc = t.dM_words()) || (rc = t.scores<2>())) return rc;
-    FARNN_HIP_TRY(hipGetLastError());
-    c->prof.end(t.s);
-    return FARNN_OK;
+    return run_train_step<Ind1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- training step of the decomposed independent=1 model (FARNN_S_D_W_I; decomp1_train.hip.h) --------------
-struct farnn_decomp_ind1_train_ctx {
+struct farnn_decomp_ind1_train_ctx : TrainCtxBase {
     farnn_decomp_ind1_train_dims d;
-    int device = 0;
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, br / scores, N / Mc / McT / dMc / dN, the factor
                                   // products Kfac / Ofac / E, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
-    StepProfile prof;
-    ErrWord err;                  // bit 0 a bad label, bit 1 a word outside 0..V-1
 };
 
 extern "C" int farnn_decomp_ind1_train_create(const farnn_decomp_ind1_train_dims *d, int device, farnn_decomp_ind1_train_ctx **out) {
@@ -1049,104 +832,67 @@ extern "C" int farnn_decomp_ind1_train_create(const farnn_decomp_ind1_train_dims
         return fail(FARNN_ERANGE, "decomp_ind1_train_create: rank R too large (R S S must stay below 2^31)%s%s");
     if ((unsigned long long)d->RO * d->S * d->S >= (1ull << 31))
         return fail(FARNN_ERANGE, "decomp_ind1_train_create: output rank R_O too large (R_O S S must stay below 2^31)%s%s");
-    int rc;
-    if ((rc = select_device(device))) return rc;
-    farnn_decomp_ind1_train_ctx *c = new farnn_decomp_ind1_train_ctx();
-    c->d = *d; c->device = device;
-    if (!c->err.create()) { farnn_decomp_ind1_train_destroy(c); return fail(FARNN_ENOMEM, "decomp_ind1_train_create: out of memory%s%s"); }
-    *out = c;
-    return FARNN_OK;
+    return train_ctx_create("decomp_ind1_train", d, device, out);
 }
-
-extern "C" void farnn_decomp_ind1_train_destroy(farnn_decomp_ind1_train_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    delete c;
-}
-
+extern "C" void farnn_decomp_ind1_train_destroy(farnn_decomp_ind1_train_ctx *c) { train_ctx_destroy(c); }
 extern "C" int farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *c, int32_t enable) {
-    if (!c) return fail(FARNN_EINVAL, "decomp_ind1_train_set_profiling: null context%s%s");
-    c->prof.enabled = enable;
-    return FARNN_OK;
+    return train_ctx_set_profiling("decomp_ind1_train", c, enable);
 }
-
 extern "C" int farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
-    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "decomp_ind1_train_time: null argument%s%s");
-    return c->prof.time(c->device, total_ms, steps);
+    return train_ctx_time("decomp_ind1_train", c, total_ms, steps);
 }
 
-// One step: the plan (decomp1_plan: sizes from the dimensions alone) and what the stages hand on
-struct Decomp1Step {
-    int B, L, ngrp, cpg;          // rank groups per word of the score kernel's MODE 0 and 1, output ranks per group
-    size_t S, K, V, R, RO, N1, N0;
-    unsigned lgrid;               // workgroups of the loss kernel
-    size_t need, ineed;           // floats of ws, ints of iws: the totals of carve_decomp1_ws / carve_decomp1_ints
-    size_t lds_tok, lds_sc, lds_loss;   // LDS bytes of the chain, score and loss kernels
-    farnn_decomp_ind1_train_ctx *c; const farnn_decomp_ind1_train_weights *w; const farnn_decomp_ind1_train_outputs *o; hipStream_t s;
-    OhTrainParams q;
-    Ind1TrainParams f;
+// One step (BucketedStep); the groups of its score kernel's MODE 0 and 1 divide the output ranks
+struct Decomp1Step : BucketedStep<farnn_decomp_ind1_train_ctx, farnn_decomp_ind1_train_weights, farnn_decomp_ind1_train_outputs,
+                                  Ind1TrainParams> {
+    static constexpr const char *name = "decomp_ind1_train", *label_range = "C";
+    size_t R, RO;
     D1BackParams bp;
-    float *BR, *DBR, *SC, *DS, *Nw, *M, *MT, *dM, *dN, *Kfac, *Ofac, *E, *Osum, *dOsum, *zero, *csum, *dcsum, *ones, *loss_part,
-          *partial, *part, *fpart, *HP;
-    Buckets bk;
-    int carve(const int64_t *x, const int64_t *lengths);
+    float *BR, *DBR, *Nw, *dN, *Kfac, *Ofac, *E, *Osum, *dOsum, *zero, *csum, *dcsum, *fpart, *HP;
+    size_t carve_ws(float *base);
+    int validate(); int plan(int B, int L);
+    int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int gemm(const float *A, size_t am, size_t ak, const float *Bm, size_t bk_, size_t bn, float *Cm, size_t ldc, size_t M_, size_t N_,
              size_t K_, const float *add = nullptr, const int *rows = nullptr);
-    int prepare(); int loss(const int64_t *labels, int64_t valid_tokens); int adjoints(); int dM_words(); int back(); int factors();
+    int prepare(); int loss(); int back(); int factors(); int stages();
     template <int MODE> int scores();
 };
 
-static size_t carve_decomp1_ws(float *base, Decomp1Step &t) {
+size_t Decomp1Step::carve_ws(float *base) {
     Carver<float> a(base);
-    const size_t nS = t.N1 * t.S, SS = t.S * t.S, SS4 = (SS + 3) & ~(size_t)3, RO4 = (t.RO + 3) & ~(size_t)3;
-    t.q.A = a.take(nS); t.q.Bk = a.take(nS); t.q.GA = a.take(nS); t.q.GB = a.take(nS); t.q.UF = a.take(nS); t.q.DQ = a.take(nS);
-    t.BR = a.take(t.N0 * t.RO); t.DS = a.take(t.N0 * t.K);             // (neighbours: cleared by one memset)
-    t.DBR = a.take(t.N0 * t.RO); t.SC = a.take(t.N0 * t.K);
-    t.Nw = a.take(t.V * SS); t.M = a.take(t.V * SS); t.MT = a.take(t.V * SS); t.dM = a.take(t.V * SS); t.dN = a.take(t.V * SS);
-    t.Kfac = a.take(t.R * SS); t.E = a.take(t.R * SS); t.Ofac = a.take(t.RO * SS);
-    t.Osum = a.take(SS4); t.dOsum = a.take(SS4); t.zero = a.take(SS4);
-    t.csum = a.take(RO4); t.dcsum = a.take(RO4);
-    t.ones = a.take((t.S + 3) & ~(size_t)3);
-    t.loss_part = a.take((size_t)t.lgrid * 8);
-    t.partial = a.take((2 * ((t.N0 + OT_G - 1) / OT_G) + 1) * SS);      // dMc: partial tiles of the words with several runs
-    t.part = a.take(t.N0 * (size_t)t.ngrp * 2 * t.S);                   // d alpha / d beta per position and rank group
-    t.fpart = a.take(t.V * t.RO * 2 * t.S);                             // the words' shares of dS1_output / dS2_output
-    t.HP = a.take((size_t)t.B * 2 * t.S);                               // the sequences' shares of dh0 / dhT
+    const size_t SS = S * S, SS4 = (SS + 3) & ~(size_t)3, RO4 = (RO + 3) & ~(size_t)3;
+    carve_head(a);
+    BR = a.take(N0 * RO); DS = a.take(N0 * K);             // (neighbours: cleared by one memset)
+    DBR = a.take(N0 * RO); SC = a.take(N0 * K);
+    Nw = a.take(V * SS); M = a.take(V * SS); MT = a.take(V * SS); dM = a.take(V * SS); dN = a.take(V * SS);
+    Kfac = a.take(R * SS); E = a.take(R * SS); Ofac = a.take(RO * SS);
+    Osum = a.take(SS4); dOsum = a.take(SS4); zero = a.take(SS4);
+    csum = a.take(RO4); dcsum = a.take(RO4);
+    carve_tail(a);
+    fpart = a.take(V * RO * 2 * S);                             // the words' shares of dS1_output / dS2_output
+    HP = a.take((size_t)B * 2 * S);                               // the sequences' shares of dh0 / dhT
     return a.off;
 }
-static size_t carve_decomp1_ints(int *base, Decomp1Step &t) { Carver<int> a(base); carve_buckets(a, t.bk, t.V, t.N0); return a.off; }
-
-// Stage 2 (after the arguments): host arithmetic only; every size the step refuses is refused here, before anything is enqueued
-static int decomp1_plan(const farnn_decomp_ind1_train_ctx *c, int B, int L, Decomp1Step &t) {
-    // positions are 32-bit flat indices b L + i in the bucketing, dMc and score kernels
-    if ((unsigned long long)B * (L + 1) >= (1ull << 30)) return fail(FARNN_ERANGE, "decomp_ind1_train_step: B (L+1) must stay below 2^30%s%s");
-    t.B = B; t.L = L; t.S = c->d.S; t.K = c->d.C; t.V = c->d.V; t.R = c->d.R; t.RO = c->d.RO;
-    t.N1 = (size_t)B * (L + 1); t.N0 = (size_t)B * L;
-    // a word's output ranks are split over enough workgroups to fill the chip when the batch has few distinct words
-    const size_t words = std::min(t.V, t.N0), want = std::min<size_t>({(1024 + words - 1) / words, t.RO, (size_t)F4_MAX_GROUPS});
-    t.cpg = (int)((t.RO + want - 1) / want); t.ngrp = (int)((t.RO + t.cpg - 1) / t.cpg);
-    t.lgrid = (unsigned)std::min<size_t>(768, (t.N0 + 7) / 8);
-    const int SP = (int)((t.S + 3) & ~(size_t)3), CPR = SP / 4, GW = 64 / CPR;
-    t.f.SP = SP; t.f.CPR = CPR; t.f.GW = GW;
-    t.lds_tok = (size_t)(L + 1) * sizeof(int);
-    t.lds_sc = ind1_train_lds_floats(SP, CPR, GW) * sizeof(float);
-    t.lds_loss = fst4_loss_lds_bytes(t.K);
-    t.need = carve_decomp1_ws(nullptr, t); t.ineed = carve_decomp1_ints(nullptr, t);
-    int rc;
-    if ((rc = lds_fits(t.lds_tok)) || (rc = lds_fits(t.lds_sc))) return rc;
-    return lds_fits(t.lds_loss);
+// Stage 1: the arguments
+int Decomp1Step::validate() {
+    if (!w->Vgen || !w->S1 || !w->S2 || !w->W || !w->C || !w->S1o || !w->S2o || !w->h0 || !w->hT)
+        return fail(FARNN_EINVAL, "decomp_ind1_train_step: null weight%s%s");
+    if (!o->loss || !o->dVgen || !o->dS1 || !o->dS2 || !o->tags) return fail(FARNN_EINVAL, "decomp_ind1_train_step: null output%s%s");
+    return FARNN_OK;
+}
+int Decomp1Step::plan(int B_, int L_) {
+    R = c->d.R; RO = c->d.RO;
+    if (int rc = plan_bucketed(name, B_, L_, RO, ind1_train_lds_floats)) return rc;
+    need = carve_ws(nullptr);
+    return FARNN_OK;
 }
 // Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters
-int Decomp1Step::carve(const int64_t *x, const int64_t *lengths) {
-    int rc;
-    if ((rc = c->ws.ensure(need, "decomp_ind1_train_step: out of device memory for the workspace%s%s")) ||
-        (rc = c->iws.ensure(ineed, "decomp_ind1_train_step: out of device memory for the index workspace%s%s"))) return rc;
-    [[maybe_unused]] const size_t carved = carve_decomp1_ws(c->ws.p, *this), icarved = carve_decomp1_ints(c->iws.p, *this);
-    assert(carved == need && icarved == ineed);     // the sizing pass and the carving pass agree
-    // the chains use args.update_nonlinear (model_decompose_independent.py:181-188); the output mask is premixed into Mc: a mask of ones
-    q.M = M; q.MT = MT; q.o = ones; q.h0 = w->h0; q.hT = w->hT; q.x = x; q.len = lengths;
-    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.nl = c->d.nl;
+int Decomp1Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *labels_, int64_t valid_tokens) {
+    if (int rc = grow_workspaces(name, c, need, ineed)) return rc;
+    [[maybe_unused]] const size_t carved = carve_ws(c->ws.p);
+    assert(carved == need);     // the sizing pass and the carving pass agree
+    // the chains use args.update_nonlinear (model_decompose_independent.py:181-188); the output mask is premixed into Mc
+    carve_bucketed(x, lengths, labels_, valid_tokens, c->d.nl);
     // the score kernel in factor space: N (wildcard_mat already in it) in T's place beside a zero W, Ofac in O's, br in the scores'
     f.T = Nw; f.W = zero; f.O = Ofac; f.A = q.A; f.Bk = q.Bk; f.len = lengths;
     f.list = bk.list; f.wstart = bk.wstart; f.wcount = bk.wcount;
@@ -1167,17 +913,17 @@ int Decomp1Step::gemm(const float *A, size_t am, size_t ak, const float *Bm, siz
 // for the words of the batch (the bucket counts say which), Mc[w] = N[w] * Osum and its transpose.  br and d score are cleared:
 // their rows at pad positions enter the products over the positions (dC_output) as zeros
 int Decomp1Step::prepare() {
-    FARNN_HIP_TRY(hipMemsetAsync(bk.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    int rc;
+    if ((rc = clear_bucket_counts(bk, V, N0, s))) return rc;
     FARNN_HIP_TRY(hipMemsetAsync(BR, 0, N0 * (RO + K) * sizeof(float), s));
     FARNN_HIP_TRY(hipMemsetAsync(zero, 0, S * S * sizeof(float), s));
-    if (int rc = launch_bucketing(q.x, q.len, B, L, (int)V, bk, c->err.dev, s)) return rc;
-    fst4_fill_kernel<<<(unsigned)((S + 255) / 256), 256, 0, s>>>(ones, 1.0f, (int)S);
+    if ((rc = bucket_and_fill())) return rc;
     const size_t SS = S * S;
     decomp1_outer_kernel<<<(unsigned)((R * SS + 255) / 256), 256, 0, s>>>(w->S1, w->S2, Kfac, (int)S, (int)R);
     decomp1_outer_kernel<<<(unsigned)((RO * SS + 255) / 256), 256, 0, s>>>(w->S1o, w->S2o, Ofac, (int)S, (int)RO);
     decomp1_csum_kernel<<<(unsigned)((RO + 255) / 256), 256, 0, s>>>(w->C, csum, (int)K, (int)RO);
     decomp1_osum_kernel<<<(unsigned)((SS + 255) / 256), 256, 0, s>>>(csum, Ofac, Osum, (int)SS, (int)RO);
-    if (int rc = gemm(w->Vgen, R, 1, Kfac, SS, 1, Nw, SS, V, SS, R, w->W, bk.wcount)) return rc;
+    if ((rc = gemm(w->Vgen, R, 1, Kfac, SS, 1, Nw, SS, V, SS, R, w->W, bk.wcount))) return rc;
     const unsigned nt = (unsigned)((S + 31) / 32);
     ind1_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(Nw, zero, Osum, bk.wcount, M, MT, (int)S);
     return FARNN_OK;
@@ -1185,35 +931,19 @@ int Decomp1Step::prepare() {
 // Stages 7 and 9: ind1_train_kernel in bucket order over the output ranks (MODE 0: br, 1: the partials of d alpha / d beta)
 template <int MODE>
 int Decomp1Step::scores() {
-    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
-    auto go = [&](auto RPT) { return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), I1_THREADS, lds_sc, s, f); };
-    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
-                                                                                                             : go(int_c<16>());
+    return with_rows_per_thread(S, f.GW, [&](auto RPT) {
+        return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), I1_THREADS, lds_sc, s, f);
+    });
 }
-// Stage 8: score = br C_output^T (:206); priority layer, cross-entropy, decode, d loss / d scores; the loss as per-wavefront
-// partials; d br = d score C_output
-int Decomp1Step::loss(const int64_t *labels, int64_t valid_tokens) {
+// Stage 8: score = br C_output^T (:206); the loss on the scores; d br = d score C_output
+int Decomp1Step::loss() {
     int rc;
-    if ((rc = gemm(BR, RO, 1, w->C, 1, RO, SC, K, N0, K, RO))) return rc;
-    if ((rc = launch(fst4_loss_kernel, lgrid, 512, lds_loss, s, SC, w->P, q.len, labels, c->err.dev, DS, o->tags, loss_part, B, L,
-                     (int)K, c->d.o_idx, c->d.threshold, 1.0f / (float)valid_tokens))) return rc;
-    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, o->loss);
+    if ((rc = gemm(BR, RO, 1, w->C, 1, RO, SC, K, N0, K, RO)) || (rc = loss_on_scores())) return rc;
     return gemm(DS, K, 1, w->C, RO, 1, DBR, RO, N0, RO, K);
 }
-// Stage 9: d loss / d alpha_i and d loss / d beta_{i+1} of every position, the rank groups' partials added in group order
-int Decomp1Step::adjoints() {
-    if (int rc = scores<1>()) return rc;
-    fst4_adj_reduce_kernel<<<(unsigned)N0, 128, 0, s>>>(part, bk.list, bk.wstart, bk.wcount, q.len, q.GA, q.GB, (int)V, L, (int)S, ngrp);
-    return FARNN_OK;
-}
-// Stage 11: dMc[w] of the chains, the i-FST step's per-word reduction
-int Decomp1Step::dM_words() { return launch_onehot_dT(q, bk, dM, partial, s); }
 // Stage 12: dN[w] and the words' shares of dS1_output / dS2_output, one workgroup per word over all output ranks
 int Decomp1Step::back() {
-    const int rows = (int)((S + 4 * f.GW - 1) / (4 * f.GW));
-    auto go = [&](auto RPT) { return launch(decomp1_back_kernel<RPT()>, (unsigned)V, I1_THREADS, lds_sc, s, bp); };
-    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>())
-                                                                                                             : go(int_c<16>());
+    return with_rows_per_thread(S, f.GW, [&](auto RPT) { return launch(decomp1_back_kernel<RPT()>, (unsigned)V, I1_THREADS, lds_sc, s, bp); });
 }
 // Stage 13: the dense adjoints contracted onto the factors, every sum over the words in id order and over the sequences in order
 int Decomp1Step::factors() {
@@ -1233,31 +963,18 @@ int Decomp1Step::factors() {
     }
     return FARNN_OK;
 }
+// Stages 4 to 13 (6 and 10: both chains, with the state stash, then back-propagation through time)
+int Decomp1Step::stages() {
+    int rc;
+    if ((rc = prepare()) || (rc = chains<false>()) || (rc = scores<0>()) || (rc = loss()) ||
+        (rc = adjoints([&] { return scores<1>(); })) || (rc = chains<true>()) || (rc = dM_words()) || (rc = back())) return rc;
+    return factors();
+}
 
 extern "C" int farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *c, const farnn_decomp_ind1_train_weights *w, const int64_t *x,
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *o, void *stream) {
-    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "decomp_ind1_train_step: null argument%s%s");
-    if (!w->Vgen || !w->S1 || !w->S2 || !w->W || !w->C || !w->S1o || !w->S2o || !w->h0 || !w->hT)
-        return fail(FARNN_EINVAL, "decomp_ind1_train_step: null weight%s%s");
-    if (!o->loss || !o->dVgen || !o->dS1 || !o->dS2 || !o->tags) return fail(FARNN_EINVAL, "decomp_ind1_train_step: null output%s%s");
-    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "decomp_ind1_train_step: B, L and valid_tokens must be positive%s%s");
-    Decomp1Step t = {};
-    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
-    int rc, bad = 0;
-    if ((rc = decomp1_plan(c, B, L, t))) return rc;
-    FARNN_HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->err.take(t.s, &bad))) return rc;
-    if (bad) return fail(FARNN_EINVAL, (bad & 2) ? "decomp_ind1_train_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s%s"
-                                                 : "decomp_ind1_train_step: an earlier step saw a label outside 0..C-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0%s%s");
-    if ((rc = t.carve(x, lengths))) return rc;
-    StepProfile::Guard timing = c->prof.begin(t.s);
-    if ((rc = t.prepare()) || (rc = launch_onehot_chains<false>(t.q, t.lds_tok, t.s)) || (rc = t.scores<0>()) ||
-        (rc = t.loss(labels, valid_tokens)) || (rc = t.adjoints()) || (rc = launch_onehot_chains<true>(t.q, t.lds_tok, t.s)) ||
-        (rc = t.dM_words()) || (rc = t.back()) || (rc = t.factors())) return rc;
-    FARNN_HIP_TRY(hipGetLastError());
-    c->prof.end(t.s);
-    return FARNN_OK;
+    return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- the optimizer step (farnn_optim_*; optim.hip.h) -------------------------------------------------------------------

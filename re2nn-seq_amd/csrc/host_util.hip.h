@@ -140,16 +140,17 @@ inline int device_cus(int device) {      // compute units (256 if the device doe
 }
 
 // A device buffer that only grows.  A too-small one is freed after a device synchronize (an earlier step's kernels may still
-// use it).  `what` is the whole message of a failed allocation: it names the step and the buffer, and ends in "%s%s" (fail()).
+// use it).  `what` is the message of a failed allocation: it names the step and the buffer, and holds two "%s" (fail()); `a` fills
+// the first (a step's prefix, where the message is shared by several steps).
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
     ~DevBuf() { release(); }
-    int ensure(size_t need, const char *what) {
+    int ensure(size_t need, const char *what, const char *a = "") {
         if (need <= n) return FARNN_OK;
         if (p) { FARNN_HIP_TRY(hipDeviceSynchronize()); release(); }
-        if (hipMalloc((void **)&p, need * sizeof(T)) != hipSuccess) { p = nullptr; return fail(FARNN_ENOMEM, what); }
+        if (hipMalloc((void **)&p, need * sizeof(T)) != hipSuccess) { p = nullptr; return fail(FARNN_ENOMEM, what, a); }
         n = need;
         return FARNN_OK;
     }

@@ -1,7 +1,10 @@
-// Host-side pieces shared by the training steps (farnn_train.hip): the carver that sizes and lays out a workspace with one piece
-// of code, step profiling, the pinned error word, and the launches both steps make (DevBuf and launch: host_util.hip.h).
+// Host-side pieces shared by the five training steps (farnn_train.hip): the carver that sizes and lays out a workspace with one
+// piece of code, step profiling, the pinned error word, the handle every training context is and its life cycle, the driver
+// every step entry point goes through, and the launches several steps make (DevBuf and launch: host_util.hip.h).  What the
+// three steps over bucketed per-word blocks share beyond that is in train_bucketed.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <utility>
 #include <vector>
 #include "host_util.hip.h"
@@ -56,7 +59,7 @@ struct StepProfile {
         pending.clear();
         if (total_ms) { *total_ms = ms; *steps = n; ms = 0.0; n = 0; }
     }
-    int time(int device, double *total_ms, int64_t *steps) {      // farnn_train_time / farnn_onehot_train_time
+    int time(int device, double *total_ms, int64_t *steps) {      // train_ctx_time
         FARNN_HIP_TRY(hipSetDevice(device));
         FARNN_HIP_TRY(hipDeviceSynchronize());
         drain(total_ms, steps);
@@ -83,6 +86,73 @@ struct ErrWord {
     }
 };
 
+// ---- the handle of a training step (farnn_*train_ctx) and its life cycle --------------------------------------------------
+// `name` is the step's prefix in every message: "train", "onehot_train", "fst4_train", "ind1_train", "decomp_ind1_train".
+struct TrainCtxBase {
+    int device = 0;
+    StepProfile prof;
+    ErrWord err;                      // bit 0 a bad label, bit 1 a word outside 0..V-1 (the steps that bucket with it)
+};
+template <typename Ctx>
+inline void train_ctx_destroy(Ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    delete c;                         // the buffers, the events and the error word free themselves
+}
+// the tail of every create, after the step's own checks of the dimensions
+template <typename Ctx, typename Dims>
+inline int train_ctx_create(const char *name, const Dims *d, int device, Ctx **out) {
+    if (int rc = select_device(device)) return rc;
+    Ctx *c = new Ctx();
+    c->d = *d; c->device = device;
+    if (!c->err.create()) { train_ctx_destroy(c); return fail(FARNN_ENOMEM, "%s_create: out of memory%s", name); }
+    *out = c;
+    return FARNN_OK;
+}
+inline int train_ctx_set_profiling(const char *name, TrainCtxBase *c, int32_t enable) {
+    if (!c) return fail(FARNN_EINVAL, "%s_set_profiling: null context%s", name);
+    c->prof.enabled = enable;
+    return FARNN_OK;
+}
+inline int train_ctx_time(const char *name, TrainCtxBase *c, double *total_ms, int64_t *steps) {
+    if (!c || !total_ms || !steps) return fail(FARNN_EINVAL, "%s_time: null argument%s", name);
+    return c->prof.time(c->device, total_ms, steps);
+}
+
+// ---- one step, for every farnn_*_train_step ------------------------------------------------------------------------------
+// A Step names itself (Step::name) and its label range (Step::label_range: "K" or "C"), holds c / w / o / s, and supplies
+// validate() (its weights and outputs), plan(B, L) (host arithmetic only: every size the step refuses is refused there, before
+// anything is enqueued), carve(...) (grow the buffers, lay the workspaces out, fill the kernels' parameters) and stages() (the
+// launches, in order).  A step that returns before the end leaves no event pair behind (StepProfile::Guard).
+template <typename Step, typename Ctx, typename W, typename O>
+inline int run_train_step(Ctx *c, const W *w, const int64_t *x, const int64_t *lengths, const int64_t *labels, int B, int L,
+                          int64_t valid_tokens, const O *o, void *stream) {
+    if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "%s_step: null argument%s", Step::name);
+    Step t = {};
+    t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
+    int rc, bad = 0;
+    if ((rc = t.validate())) return rc;
+    if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "%s_step: B, L and valid_tokens must be positive%s", Step::name);
+    if ((rc = t.plan(B, L))) return rc;
+    FARNN_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->err.take(t.s, &bad))) return rc;
+    if (bad & 2) return fail(FARNN_EINVAL, "%s_step: an earlier step saw a word outside 0..V-1 at a valid position (torch raises on it); that step clamped it%s", Step::name);
+    if (bad) return fail(FARNN_EINVAL, "%s_step: an earlier step saw a label outside 0..%s-1 at a valid position (torch's CrossEntropyLoss raises on it); that step counted it as label 0", Step::name, Step::label_range);
+    if ((rc = t.carve(x, lengths, labels, valid_tokens))) return rc;
+    StepProfile::Guard timing = c->prof.begin(t.s);
+    if ((rc = t.stages())) return rc;
+    FARNN_HIP_TRY(hipGetLastError());
+    c->prof.end(t.s);
+    return FARNN_OK;
+}
+// the two workspaces of the steps that bucket the positions (ws: floats, iws: ints)
+template <typename Ctx>
+inline int grow_workspaces(const char *name, Ctx *c, size_t need, size_t ineed) {
+    if (int rc = c->ws.ensure(need, "%s_step: out of device memory for the workspace%s", name)) return rc;
+    return c->iws.ensure(ineed, "%s_step: out of device memory for the index workspace%s", name);
+}
+
 // ---- the positions of a batch bucketed by word (onehot_train.hip.h) ------------------------------------------------------
 struct Buckets {
     int *cnt, *wstart, *wcount, *itoff, *psoff, *list;   // [V][nch] counts per chunk, per-word tables, the sorted positions [B L]
@@ -92,6 +162,11 @@ inline void carve_buckets(Carver<int> &a, Buckets &b, size_t V, size_t N0) {
     b.cnt = a.take(V * (size_t)bucket_chunks(N0));
     b.wstart = a.take(V); b.wcount = a.take(V); b.itoff = a.take(V + 1); b.psoff = a.take(V + 1);
     b.list = a.take(N0);
+}
+inline size_t carve_bucket_ints(int *base, Buckets &b, size_t V, size_t N0) { Carver<int> a(base); carve_buckets(a, b, V, N0); return a.off; }
+inline int clear_bucket_counts(const Buckets &b, size_t V, size_t N0, hipStream_t s) {
+    FARNN_HIP_TRY(hipMemsetAsync(b.cnt, 0, V * (size_t)bucket_chunks(N0) * sizeof(int), s));
+    return FARNN_OK;
 }
 // count / scan (the counts in LDS when they fit) / fill; b.cnt is zero before.  err: the step's error word (bit 1: a word
 // outside 0..V-1) or null
@@ -121,6 +196,24 @@ inline int launch_train_loss(const TrainParams &p, unsigned grid, hipStream_t s)
     const LossLds l = train_loss_lds(p.S, p.K);
     return l.clds() ? launch(train_loss_kernel<true, PHASE>, grid, 512, l.bytes(), s, p)
                     : launch(train_loss_kernel<false, PHASE>, grid, 512, l.bytes(), s, p);
+}
+
+// the loss of a step whose loss kernel leaves per-wavefront partials (8 per workgroup), added in order
+inline void launch_loss_sum(const float *loss_part, unsigned lgrid, float *loss, hipStream_t s) {
+    onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)lgrid * 8, loss);
+}
+
+// ---- the kernel forms picked by S: go(int_c<N>()) with the one instantiation that holds the size ------------------------------
+// register slots per thread of the onehot chain kernels (sum and max semiring)
+template <typename F>
+inline int with_chain_slots(size_t S, F &&go) {
+    return S <= 64 ? go(int_c<8>()) : S <= 72 ? go(int_c<18>()) : S <= 96 ? go(int_c<24>()) : go(int_c<32>());
+}
+// register rows per thread of the score kernels in bucket order and of decomp1_back_kernel (GW: row groups per wavefront)
+template <typename F>
+inline int with_rows_per_thread(size_t S, int GW, F &&go) {
+    const int rows = (int)((S + 4 * GW - 1) / (4 * GW));
+    return rows <= 4 ? go(int_c<4>()) : rows <= 6 ? go(int_c<6>()) : rows <= 8 ? go(int_c<8>()) : rows <= 12 ? go(int_c<12>()) : go(int_c<16>());
 }
 
 }  // namespace farnn

@@ -107,7 +107,9 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
                                       *gates)
 
 
-class _OnehotIfstTrainStep(torch.autograd.Function):
+class _OnehotTTrainStep(torch.autograd.Function):
+    """The onehot i-FST and the onehot independent=1 step: the same weights T, W, O, h0, hT and the one gradient dT; which
+    library step runs is the context's (OnehotTrainContext or Ind1TrainContext)."""
     @staticmethod
     def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
         dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T, ntok, x, lengths, labels)
@@ -134,7 +136,7 @@ def onehot_ifst_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tok
     """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W, O, h0, hT and P are read
     but receive no gradient (the reference's requires_grad=False, model_onehot.py:326-337).  valid_tokens: the sum of
     the clamped lengths if the caller already has it."""
-    return _OnehotIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
+    return _OnehotTTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
 
 
 class _OnehotFst4TrainStep(torch.autograd.Function):
@@ -169,34 +171,11 @@ def onehot_fst4_train_step(tc, T4, W4, h0, hT, P, x, lengths, labels, valid_toke
     return _OnehotFst4TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, h0, hT, T4, W4)
 
 
-class _OnehotInd1TrainStep(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
-        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T, ntok, x, lengths, labels)
-        B, L = x.shape
-        ws = {n: _f32(t) for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
-        Pc = _f32(P)
-        dT = torch.empty_like(ws['T'])
-        weights = {n: t.data_ptr() for n, t in ws.items()}
-        weights['P'] = None if Pc is None else Pc.data_ptr()
-        outputs = {'loss': loss.data_ptr(), 'dT': dT.data_ptr(), 'tags': tags.data_ptr()}
-        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                torch.cuda.current_stream(dev).cuda_stream)
-        ctx.save_for_backward(dT)
-        ctx.mark_non_differentiable(tags)
-        return loss.reshape(()), tags
-
-    @staticmethod
-    def backward(ctx, gloss, _gtags):
-        dT, = ctx.saved_tensors
-        return (None,) * 10 + (dT * gloss,)
-
-
 def onehot_ind1_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens=None):
     """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W [S,S], O [C,S,S], h0, hT and
     P are read but receive no gradient (the reference's requires_grad=False, model_onehot.py:209-223).  Whether the chains
     run on (T + W) * O.sum(0) (args.independent == 2) is the context's mask_by_output."""
-    return _OnehotInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
+    return _OnehotTTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
 
 
 _D1_NAMES = ('Vgen', 'S1', 'S2', 'W', 'C', 'S1o', 'S2o', 'h0', 'hT')
