@@ -507,6 +507,16 @@ int  farnn_fst4_train_step(farnn_fst4_train_ctx *ctx, const farnn_fst4_train_wei
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *ctx, int32_t enable);
 int  farnn_fst4_train_time(farnn_fst4_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* The semiring of both chains (semiring_func, model_onehot.py:57, used at :93 and :100), with the arguments and error codes
+ * of farnn_onehot_train_set_semiring: FARNN_SEMIRING_SUM (the default) or FARNN_SEMIRING_MAX, where a chain step is
+ * max_j alpha[j] M_w[j,s] (forward) and max_j beta[j] M_w[s,j] (backward), torch.max's first maximal j taking the whole
+ * adjoint.  Only the two recurrences change: the score of a position, the priority layer, the loss, the decode and every
+ * limit are the same in both, and so is everything downstream of dM.  No float atomics.  The max step's extra workspace (an
+ * index byte and the winning entry per step and state) is allocated by its first step; a context switched back to
+ * FARNN_SEMIRING_SUM computes exactly what one that never left it does.  The Python mirror keeps this semiring opt-in for
+ * its first release: the three models below train with --train_mode max only when RE2NN_BUCKETED_MAX_TRAIN=1 is set beside
+ * the model's own switch (RE2NN_ONEHOT_FST_TRAIN, RE2NN_ONEHOT_IND1_TRAIN, RE2NN_DECOMP_IND1_TRAIN). */
+int  farnn_fst4_train_set_semiring(farnn_fst4_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the onehot independent=1 model (FARNN_S_O_I, --method onehot --independent 1) --------
  * Replaces FARNN_S_O_I.forward_local(train=True) + loss.backward() (model_onehot.py:184-306, train_onehot.py:156-206) for
@@ -553,6 +563,8 @@ int  farnn_ind1_train_step(farnn_ind1_train_ctx *ctx, const farnn_ind1_train_wei
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_ind1_train_time(farnn_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* As farnn_fst4_train_set_semiring (model_onehot.py:264, :276): the chains run max_j over Mc[w] = N[w] (* output_tensor.sum(0)). */
+int  farnn_ind1_train_set_semiring(farnn_ind1_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the decomposed independent=1 model (FARNN_S_D_W_I, --method decompose --independent 1) ---
  * Replaces FARNN_S_D_W_I.forward_local(train=True) + loss.backward() (model_decompose_independent.py:219-300,
@@ -609,6 +621,10 @@ int  farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* As farnn_fst4_train_set_semiring (model_decompose_independent.py:177-179): the chains run max_j over Mc[w] = N[w] * Osum with
+ * the model's update_nonlinear.  dh0 / dhT receive, beside the score adjoint of the first / last position, what the first chain
+ * step carries back -- in the max semiring to the winning index only. */
+int  farnn_decomp_ind1_train_set_semiring(farnn_decomp_ind1_train_ctx *ctx, int32_t semiring);
 
 /* ---- multi-tensor optimizer step: torch.optim.Adam / torch.optim.SGD (train_onehot.py:78-81 of this package) ----------
  * One launch updates every tensor of a training step (more than 32 tensors: one launch per 32).  Adam with torch's arithmetic,

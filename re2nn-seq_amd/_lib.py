@@ -199,6 +199,7 @@ SIGNATURES = {
                                         C.POINTER(Fst4TrainOutputs), C.c_void_p]),
     'farnn_fst4_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_fst4_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_fst4_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_ind1_train_create': (C.c_int, [C.POINTER(Ind1TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_ind1_train_destroy': (None, [C.c_void_p]),
     'farnn_ind1_train_step': (C.c_int, [C.c_void_p, C.POINTER(Ind1TrainWeights), C.c_void_p, C.c_void_p,
@@ -206,6 +207,7 @@ SIGNATURES = {
                                         C.POINTER(Ind1TrainOutputs), C.c_void_p]),
     'farnn_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_ind1_train_create': (C.c_int, [C.POINTER(Decomp1TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_decomp_ind1_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ind1_train_step': (C.c_int, [C.c_void_p, C.POINTER(Decomp1TrainWeights), C.c_void_p, C.c_void_p,
@@ -213,6 +215,7 @@ SIGNATURES = {
                                                C.POINTER(Decomp1TrainOutputs), C.c_void_p]),
     'farnn_decomp_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_decomp_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -593,12 +596,21 @@ class _TrainContextBase:
     """Owns one training context of the C-ABI (include/farnn.h).  A subclass names its five C symbols and its two struct types."""
     _create = _destroy = _step = _set_profiling = _time = None
     _weights = _outputs = None
+    _set_semiring = None
     _raw = None
 
-    def _open(self, dims, device):
+    def _open(self, dims, device, semiring='sum'):
+        if semiring not in SEMIRING:             # before the native context exists: a bad name leaves no handle behind
+            raise ValueError('semiring must be one of {}, not {!r}'.format(sorted(SEMIRING), semiring))
         out = C.c_void_p()
         check(getattr(load(), self._create)(C.byref(dims), int(device), C.byref(out)), self._create)
         self._raw = out
+        if semiring != 'sum':
+            self.set_semiring(semiring)
+
+    def set_semiring(self, semiring):
+        """'sum' or 'max' (the reference's --train_mode) for the following steps."""
+        check(getattr(load(), self._set_semiring)(self._raw, SEMIRING[semiring]), self._set_semiring)
 
     def close(self):
         if self._raw:
@@ -631,48 +643,37 @@ class TrainContext(_TrainContextBase):
     """Owns one farnn_train_ctx* (training step of the decomposed i-FST, include/farnn.h)."""
     _create, _destroy, _step = 'farnn_train_create', 'farnn_train_destroy', 'farnn_decomp_ifst_train_step'
     _set_profiling, _time = 'farnn_train_set_profiling', 'farnn_train_time'
+    _set_semiring = 'farnn_train_set_semiring'
     _weights, _outputs = TrainWeights, TrainOutputs
 
     def __init__(self, V, S, R, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0,
                  sigmoid_exponent=5.0, semiring='sum'):
         self._open(TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
-                             float(sigmoid_exponent), int(bool(use_crf))), device)
+                             float(sigmoid_exponent), int(bool(use_crf))), device, semiring)
         self.dims = (int(V), int(S), int(R), int(K))
-        if semiring != 'sum':
-            self.set_semiring(semiring)
-
-    def set_semiring(self, semiring):
-        """'sum' or 'max' (the reference's --train_mode) for the following steps."""
-        check(load().farnn_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_train_set_semiring')
 
 
 class OnehotTrainContext(_TrainContextBase):
     """Owns one farnn_onehot_train_ctx* (training step of the onehot i-FST, include/farnn.h)."""
     _create, _destroy, _step = 'farnn_onehot_train_create', 'farnn_onehot_train_destroy', 'farnn_onehot_ifst_train_step'
     _set_profiling, _time = 'farnn_onehot_train_set_profiling', 'farnn_onehot_train_time'
+    _set_semiring = 'farnn_onehot_train_set_semiring'
     _weights, _outputs = OnehotTrainWeights, OnehotTrainOutputs
 
     def __init__(self, V, S, n_cols, nl='none', threshold=0.5, o_idx=0, device=0, semiring='sum'):
-        if semiring not in SEMIRING:             # before the native context exists: a bad name leaves no handle behind
-            raise ValueError('semiring must be one of {}, not {!r}'.format(sorted(SEMIRING), semiring))
-        self._open(OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
+        self._open(OnehotTrainDims(int(V), int(S), int(n_cols), NL[nl], float(threshold), int(o_idx)), device, semiring)
         self.dims = (int(V), int(S), int(n_cols))
-        if semiring != 'sum':
-            self.set_semiring(semiring)
-
-    def set_semiring(self, semiring):
-        """'sum' or 'max' (the reference's --train_mode) for the following steps."""
-        check(load().farnn_onehot_train_set_semiring(self._raw, SEMIRING[semiring]), 'farnn_onehot_train_set_semiring')
 
 
 class Fst4TrainContext(_TrainContextBase):
     """Owns one farnn_fst4_train_ctx* (training step of the onehot FST, include/farnn.h)."""
     _create, _destroy, _step = 'farnn_fst4_train_create', 'farnn_fst4_train_destroy', 'farnn_fst4_train_step'
     _set_profiling, _time = 'farnn_fst4_train_set_profiling', 'farnn_fst4_train_time'
+    _set_semiring = 'farnn_fst4_train_set_semiring'
     _weights, _outputs = Fst4TrainWeights, Fst4TrainOutputs
 
-    def __init__(self, V, S, n_cols, threshold=0.5, o_idx=0, device=0):
-        self._open(Fst4TrainDims(int(V), int(S), int(n_cols), float(threshold), int(o_idx)), device)
+    def __init__(self, V, S, n_cols, threshold=0.5, o_idx=0, device=0, semiring='sum'):
+        self._open(Fst4TrainDims(int(V), int(S), int(n_cols), float(threshold), int(o_idx)), device, semiring)
         self.dims = (int(V), int(S), int(n_cols))
 
 
@@ -680,11 +681,12 @@ class Ind1TrainContext(_TrainContextBase):
     """Owns one farnn_ind1_train_ctx* (training step of the onehot independent=1 model, include/farnn.h)."""
     _create, _destroy, _step = 'farnn_ind1_train_create', 'farnn_ind1_train_destroy', 'farnn_ind1_train_step'
     _set_profiling, _time = 'farnn_ind1_train_set_profiling', 'farnn_ind1_train_time'
+    _set_semiring = 'farnn_ind1_train_set_semiring'
     _weights, _outputs = Ind1TrainWeights, Ind1TrainOutputs
 
-    def __init__(self, V, S, n_cols, mask_by_output=False, threshold=0.5, o_idx=0, device=0):
+    def __init__(self, V, S, n_cols, mask_by_output=False, threshold=0.5, o_idx=0, device=0, semiring='sum'):
         self._open(Ind1TrainDims(int(V), int(S), int(n_cols), int(bool(mask_by_output)), float(threshold), int(o_idx)),
-                   device)
+                   device, semiring)
         self.dims = (int(V), int(S), int(n_cols))
 
 
@@ -693,10 +695,12 @@ class Decomp1TrainContext(_TrainContextBase):
     _create, _destroy = 'farnn_decomp_ind1_train_create', 'farnn_decomp_ind1_train_destroy'
     _step = 'farnn_decomp_ind1_train_step'
     _set_profiling, _time = 'farnn_decomp_ind1_train_set_profiling', 'farnn_decomp_ind1_train_time'
+    _set_semiring = 'farnn_decomp_ind1_train_set_semiring'
     _weights, _outputs = Decomp1TrainWeights, Decomp1TrainOutputs
 
-    def __init__(self, V, S, R, RO, n_cols, nl='none', threshold=0.5, o_idx=0, device=0):
-        self._open(Decomp1TrainDims(int(V), int(S), int(R), int(RO), int(n_cols), NL[nl], float(threshold), int(o_idx)), device)
+    def __init__(self, V, S, R, RO, n_cols, nl='none', threshold=0.5, o_idx=0, device=0, semiring='sum'):
+        self._open(Decomp1TrainDims(int(V), int(S), int(R), int(RO), int(n_cols), NL[nl], float(threshold), int(o_idx)), device,
+                   semiring)
         self.dims = (int(V), int(S), int(R), int(RO), int(n_cols))
 
 

@@ -602,6 +602,7 @@ extern "C" int farnn_onehot_ifst_train_step(farnn_onehot_train_ctx *c, const far
 // ---- training step of the onehot FST (FARNN_S_O; fst4_train.hip.h) ----------------------------------------
 struct farnn_fst4_train_ctx : TrainCtxBase {
     farnn_fst4_train_dims d;
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_fst4_train_set_semiring
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, M / MT / dM, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
 };
@@ -625,6 +626,9 @@ extern "C" int farnn_fst4_train_set_profiling(farnn_fst4_train_ctx *c, int32_t e
 extern "C" int farnn_fst4_train_time(farnn_fst4_train_ctx *c, double *total_ms, int64_t *steps) {
     return train_ctx_time("fst4_train", c, total_ms, steps);
 }
+extern "C" int farnn_fst4_train_set_semiring(farnn_fst4_train_ctx *c, int32_t semiring) {
+    return bucketed_set_semiring("fst4_train", c, semiring);
+}
 
 // One step (BucketedStep, train_bucketed.hip.h); the groups of its score kernels divide the label columns
 struct Fst4Step : BucketedStep<farnn_fst4_train_ctx, farnn_fst4_train_weights, farnn_fst4_train_outputs, Fst4TrainParams> {
@@ -645,6 +649,7 @@ size_t Fst4Step::carve_ws(float *base) {
     M = a.take(V * SS); MT = a.take(V * SS); dM = a.take(V * SS);
     Wsum = a.take((SS + 3) & ~(size_t)3);
     carve_tail(a);
+    carve_max(a);
     return a.off;
 }
 // Stage 1: the arguments
@@ -713,6 +718,7 @@ extern "C" int farnn_fst4_train_step(farnn_fst4_train_ctx *c, const farnn_fst4_t
 // ---- training step of the onehot independent=1 model (FARNN_S_O_I; ind1_train.hip.h) ----------------------
 struct farnn_ind1_train_ctx : TrainCtxBase {
     farnn_ind1_train_dims d;
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_ind1_train_set_semiring
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, scores, Mc / McT / dMc, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
 };
@@ -732,6 +738,9 @@ extern "C" int farnn_ind1_train_set_profiling(farnn_ind1_train_ctx *c, int32_t e
 }
 extern "C" int farnn_ind1_train_time(farnn_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
     return train_ctx_time("ind1_train", c, total_ms, steps);
+}
+extern "C" int farnn_ind1_train_set_semiring(farnn_ind1_train_ctx *c, int32_t semiring) {
+    return bucketed_set_semiring("ind1_train", c, semiring);
 }
 
 // One step (BucketedStep); the groups of its score kernel's MODE 0 and 1 divide the label columns
@@ -753,6 +762,7 @@ size_t Ind1Step::carve_ws(float *base) {
     M = a.take(V * SS); MT = a.take(V * SS); dM = a.take(V * SS);
     Osum = a.take((SS + 3) & ~(size_t)3);
     carve_tail(a);
+    carve_max(a);
     return a.off;
 }
 // Stage 1: the arguments
@@ -814,6 +824,7 @@ extern "C" int farnn_ind1_train_step(farnn_ind1_train_ctx *c, const farnn_ind1_t
 // ---- training step of the decomposed independent=1 model (FARNN_S_D_W_I; decomp1_train.hip.h) --------------
 struct farnn_decomp_ind1_train_ctx : TrainCtxBase {
     farnn_decomp_ind1_train_dims d;
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_decomp_ind1_train_set_semiring
     DevBuf<float> ws;             // per-batch float workspace: stashes, adjoints, br / scores, N / Mc / McT / dMc / dN, the factor
                                   // products Kfac / Ofac / E, the partials
     DevBuf<int> iws;              // per-batch int workspace: the bucketing of the positions by word
@@ -840,6 +851,9 @@ extern "C" int farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx
 }
 extern "C" int farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *c, double *total_ms, int64_t *steps) {
     return train_ctx_time("decomp_ind1_train", c, total_ms, steps);
+}
+extern "C" int farnn_decomp_ind1_train_set_semiring(farnn_decomp_ind1_train_ctx *c, int32_t semiring) {
+    return bucketed_set_semiring("decomp_ind1_train", c, semiring);
 }
 
 // One step (BucketedStep); the groups of its score kernel's MODE 0 and 1 divide the output ranks
@@ -871,6 +885,7 @@ size_t Decomp1Step::carve_ws(float *base) {
     carve_tail(a);
     fpart = a.take(V * RO * 2 * S);                             // the words' shares of dS1_output / dS2_output
     HP = a.take((size_t)B * 2 * S);                               // the sequences' shares of dh0 / dhT
+    carve_max(a);
     return a.off;
 }
 // Stage 1: the arguments
@@ -901,6 +916,8 @@ int Decomp1Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *
     bp.N = Nw; bp.Ofac = Ofac; bp.S1o = w->S1o; bp.S2o = w->S2o; bp.A = q.A; bp.Bk = q.Bk; bp.len = lengths;
     bp.list = bk.list; bp.wstart = bk.wstart; bp.wcount = bk.wcount; bp.DBR = DBR; bp.dMc = dM; bp.Osum = Osum;
     bp.dN = dN; bp.fpart = fpart; bp.L = L; bp.S = (int)S; bp.SP = f.SP; bp.RO = (int)RO; bp.CPR = f.CPR; bp.GW = f.GW;
+    // max semiring: UF / DQ hold dM entries, not adjoint rows -- BPTT itself carries on into row 0 (onehot_max_bptt_carry_kernel)
+    if (mx && (o->dh0 || o->dhT)) carry0 = HP;
     return FARNN_OK;
 }
 // C[m][n] = sum_k A[m am + k ak] B[k bk + n bn] (+ add[n]); rows: the rows read as zero (decomp1_gemm_kernel)
@@ -958,7 +975,7 @@ int Decomp1Step::factors() {
         (rc = gemm(w->Vgen, 1, R, dN, SS, 1, E, SS, R, SS, V))) return rc;                     // E[r] = sum_w v_r[w] dN[w]
     decomp1_in_factors_kernel<<<(unsigned)R, 128, 0, s>>>(E, w->S1, w->S2, o->dS1, o->dS2, (int)S, (int)R);
     if (o->dh0 || o->dhT) {
-        decomp1_init_adj_kernel<<<(unsigned)B, 128, 0, s>>>(q, HP);
+        if (!mx) decomp1_init_adj_kernel<<<(unsigned)B, 128, 0, s>>>(q, HP);
         decomp1_init_sum_kernel<<<1, 128, 0, s>>>(HP, o->dh0, o->dhT, B, (int)S);
     }
     return FARNN_OK;

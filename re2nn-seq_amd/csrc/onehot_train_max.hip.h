@@ -137,8 +137,11 @@ onehot_max_chain_kernel(const OhTrainParams p, const OhMaxParams m) {
 
 // Back-propagation through time of both chains; grid (B, 2), the shares of the chain kernel.  Threads (0, j) own state j: the
 // adjoint, the step's dM entry, the stash rows of the next step fetched one step ahead.
-__global__ void __launch_bounds__(OT_THREADS)
-onehot_max_bptt_kernel(const OhTrainParams p, const OhMaxParams m) {
+// CARRY0 (the steps that train the chains' initial vectors): step 1 carries on into row 0 as every step does into the row
+// before it -- to the winning index only -- and HP[b][dir][j] = the adjoint of row 0 (GA / GB row 0: the score of the first /
+// last position) + that carry: d loss / d h0 (dir 0) and d loss / d hT (dir 1) from sequence b; zero for an empty sequence.
+template <bool CARRY0>
+__device__ __forceinline__ void onehot_max_bptt_body(const OhTrainParams &p, const OhMaxParams &m, float *__restrict__ HP) {
     __shared__ float uw[OT_MAX_S], os[OT_MAX_S];
     __shared__ int jj[OT_MAX_S];
     __shared__ float part[OT_THREADS / 64][OT_MAX_S];
@@ -176,7 +179,7 @@ onehot_max_bptt_kernel(const OhTrainParams p, const OhMaxParams m) {
             uw[j] = u * w; jj[j] = ix;
             GM[row] = u * cin;
         }
-        if (t == 1) break;
+        if (!CARRY0 && t == 1) break;
         wg_barrier_lds();
         // the carry into step t - 1: thread (ks, j) adds its share of the states whose index is j, ascending
         float a = 0.0f;
@@ -190,7 +193,13 @@ onehot_max_bptt_kernel(const OhTrainParams p, const OhMaxParams m) {
             g = gn; sv = sn; w = wn; ix = ixn;
         }
     }
+    if (CARRY0 && ep) HP[((size_t)b * 2 + dir) * S + j] = len > 0 ? gadj[row0 * S + j] + carry : 0.0f;
 }
+__global__ void __launch_bounds__(OT_THREADS)
+onehot_max_bptt_kernel(const OhTrainParams p, const OhMaxParams m) { onehot_max_bptt_body<false>(p, m, nullptr); }
+// the same with the row-0 carry: HP [B][2][S] (decomp1_init_sum_kernel adds the sequences in order)
+__global__ void __launch_bounds__(OT_THREADS)
+onehot_max_bptt_carry_kernel(const OhTrainParams p, const OhMaxParams m, float *__restrict__ HP) { onehot_max_bptt_body<true>(p, m, HP); }
 
 // dT: one workgroup per run of up to OT_G positions of one word, the runs of onehot_dT_kernel.  LDS: tile [S][S], then the
 // stash rows of the run's positions (forward step i + 1; backward step len - i, which exists for i >= 1: -1 otherwise).

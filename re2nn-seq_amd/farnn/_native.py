@@ -20,6 +20,13 @@ def default_device():
     return torch.cuda.current_device() if torch.cuda.is_available() else 0
 
 
+def bucketed_max_train_enabled():
+    """RE2NN_BUCKETED_MAX_TRAIN=1: --train_mode max for the three training steps over bucketed per-word blocks (the onehot FST,
+    the onehot and the decomposed independent=1 model), beside each model's own switch (opt-in for its
+    first release, as RE2NN_ONEHOT_MAX_TRAIN)"""
+    return os.environ.get('RE2NN_BUCKETED_MAX_TRAIN', '') == '1'
+
+
 class PendingLocal:
     """A forward_local() call whose device work has been enqueued; ``result()`` waits for it and returns the
     reference's triple (None, flat_pred, flat_true)."""

@@ -11,7 +11,7 @@ import torch
 
 from .. import _lib
 from .model_decompose_single import FARNN_S_D_W_I_S, crf_default_transitions, _GATE_KEYS
-from ._native import NativeTagger
+from ._native import NativeTagger, bucketed_max_train_enabled
 from .priority import expand_priority
 
 _PARAM_KEYS = ('S1', 'S2', 'V_embed', 'embed_r_generalized', 'C_output', 'S1_output', 'S2_output',
@@ -124,7 +124,7 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
         why = None
         if a.farnn != 0:
             why = 'the gated recurrences (--farnn {})'.format(a.farnn)
-        elif a.train_mode != 'sum':
+        elif a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             why = 'the max semiring (--train_mode {})'.format(a.train_mode)
         elif a.use_crf:
             why = 'the CRF (--use_crf 1)'
@@ -159,7 +159,8 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
         S, R = self._tp['S1'].shape
         C, RO = self._tp['C_output'].shape
         self._tc = _lib.Decomp1TrainContext(self._tp['V_embed'].shape[0], S, R, RO, C, nl=self.args.update_nonlinear,
-                                            threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index)
+                                            threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
+                                            semiring='max' if self.args.train_mode == 'max' else 'sum')
         self._dirty = False
         return self
 

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ._native import NativeTagger
+from ._native import NativeTagger, bucketed_max_train_enabled
 from .priority import expand_priority
 
 
@@ -280,7 +280,7 @@ class FARNN_S_O(_OnehotBase):
         if not self._fst_train_enabled():
             from ..train_onehot import no_training_step
             raise no_training_step(self)              # today's refusal, word for word
-        if a.train_mode != 'sum':
+        if a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             raise NotImplementedError('training the onehot FST covers the sum semiring only, --train_mode {} was asked for '
                                       '(DESIGN.md, row f7)'.format(a.train_mode))
         if a.local_loss_func != 'CE1':
@@ -312,7 +312,7 @@ class FARNN_S_O(_OnehotBase):
             if self.args.use_priority else None
         V = self._tp['language_tensor'].shape[0]
         self._tc = _lib.Fst4TrainContext(V, self.S, self.C, threshold=self.args.threshold, o_idx=self.o_idx,
-                                         device=self.device_index)
+                                         device=self.device_index, semiring='max' if self.args.train_mode == 'max' else 'sum')
         self._dirty = False
         return self
 
@@ -446,7 +446,7 @@ class FARNN_S_O_I(_OnehotBase):
             from ..train_onehot import no_training_step
             raise no_training_step(self)              # today's refusal, word for word
         a = self.args
-        if a.train_mode != 'sum':
+        if a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             raise NotImplementedError('training the onehot independent=1 model covers the sum semiring only, --train_mode {} '
                                       'was asked for (DESIGN.md, row f8)'.format(a.train_mode))
         if a.local_loss_func != 'CE1':
@@ -474,7 +474,8 @@ class FARNN_S_O_I(_OnehotBase):
             if self.args.use_priority else None
         V = self._tp['language_tensor'].shape[0]
         self._tc = _lib.Ind1TrainContext(V, self.S, self.C, mask_by_output=(self.args.independent == 2),
-                                         threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index)
+                                         threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
+                                         semiring='max' if self.args.train_mode == 'max' else 'sum')
         self._dirty = False
         return self
 

@@ -27,6 +27,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--train_mode', choices=('sum', 'max'), default='sum')       # the semiring of the chains
     ap.add_argument('--stages', type=int, default=1)
     a = ap.parse_args()
     import torch
@@ -52,7 +53,7 @@ def main():
     xd = [torch.from_numpy(v).to(dev) for v in xs]
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
-    tc = _lib.Decomp1TrainContext(V, S, R, RO, C, nl='tanh', device=0)
+    tc = _lib.Decomp1TrainContext(V, S, R, RO, C, nl='tanh', device=0, semiring=a.train_mode)
 
     def one(i):
         for t in ws:
@@ -81,7 +82,7 @@ def main():
         with open(path, 'rb') as fh:
             h.update(os.path.basename(path).encode() + b'\0' + fh.read())
     tree = h.hexdigest()[:16]
-    out = {'shape': {'V': V, 'S': S, 'C': C, 'R': R, 'RO': RO, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok,
+    out = {'shape': {'V': V, 'S': S, 'C': C, 'R': R, 'RO': RO, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok, 'train_mode': a.train_mode,
            'steps': a.steps, 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
            'lib_us_max': float(max(per)), 'distinct_words': words, 'loss': float(loss.detach()), 'tree': tree}
     if a.stages:

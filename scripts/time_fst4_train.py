@@ -55,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--train_mode', choices=('sum', 'max'), default='sum')       # the semiring of the chains
     ap.add_argument('--cpu-steps', type=int, default=0)
     ap.add_argument('--cpu-seqs', type=int, default=4)
     ap.add_argument('--wildcard', type=int, default=1)
@@ -85,7 +86,7 @@ def main():
     xd = [torch.from_numpy(v).to(dev) for v in xs]
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
-    tc = _lib.Fst4TrainContext(V, S, C, device=0)
+    tc = _lib.Fst4TrainContext(V, S, C, device=0, semiring=a.train_mode)
 
     def one(i):
         T4.grad = None
@@ -105,7 +106,7 @@ def main():
         ms, n = tc.time()
         per.append(1e3 * ms / max(n, 1))
     words = [int(len(np.unique(v[np.arange(L)[None, :] < lengths[:, None]]))) for v in xs]
-    out = {'shape': {'V': V, 'S': S, 'C': C, 'B': B, 'L': L}, 'valid_tokens': ntok, 'steps': a.steps, 'train_wildcard': a.wildcard,
+    out = {'shape': {'V': V, 'S': S, 'C': C, 'B': B, 'L': L}, 'valid_tokens': ntok, 'steps': a.steps, 'train_wildcard': a.wildcard, 'train_mode': a.train_mode,
            'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)), 'lib_us_max': float(max(per)),
            'distinct_words': words, 'block_gb': (float(np.mean(words)) + 1) * C * S * S * 4 / 1e9, 'loss': float(loss.detach())}
     if a.kernel_stats:

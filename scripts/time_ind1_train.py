@@ -29,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--train_mode', choices=('sum', 'max'), default='sum')       # the semiring of the chains
     ap.add_argument('--mask', type=int, default=0)
     ap.add_argument('--cpu-steps', type=int, default=0)
     ap.add_argument('--cpu-seqs', type=int, default=4)
@@ -57,7 +58,7 @@ def main():
     xd = [torch.from_numpy(v).to(dev) for v in xs]
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
-    tc = _lib.Ind1TrainContext(V, S, C, mask_by_output=bool(a.mask), device=0)
+    tc = _lib.Ind1TrainContext(V, S, C, mask_by_output=bool(a.mask), device=0, semiring=a.train_mode)
 
     def one(i):
         Td.grad = None
@@ -76,7 +77,7 @@ def main():
         ms, n = tc.time()
         per.append(1e3 * ms / max(n, 1))
     words = [int(len(np.unique(v[np.arange(L)[None, :] < lengths[:, None]]))) for v in xs]
-    out = {'shape': {'V': V, 'S': S, 'C': C, 'B': B, 'L': L}, 'valid_tokens': ntok, 'steps': a.steps, 'mask_by_output': a.mask,
+    out = {'shape': {'V': V, 'S': S, 'C': C, 'B': B, 'L': L}, 'valid_tokens': ntok, 'steps': a.steps, 'mask_by_output': a.mask, 'train_mode': a.train_mode,
            'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)), 'lib_us_max': float(max(per)),
            'distinct_words': words, 'o_mb': C * S * S * 4 / 1e6, 'loss': float(loss.detach())}
     if a.cpu_steps > 0:
