@@ -400,6 +400,36 @@ void farnn_train_destroy(farnn_train_ctx *ctx);
 int  farnn_decomp_ifst_train_step(farnn_train_ctx *ctx, const farnn_train_weights *w, const int64_t *x,
                                   const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                   int64_t valid_tokens, const farnn_train_outputs *out, void *stream);
+/* The same step with regular expressions as a teacher (--marryup_type kd | pr; model_decompose_single.py:291-300,
+ * baselines/KD.py:3-18), sum semiring, farnn = 0/1/2, with or without the CRF and the priority layer:
+ *   loss = pi * original + (1 - pi) * KL,   the original loss being the cross-entropy or the CRF sum of the plain step,
+ *   KD: KL = KLDivLoss()(log_softmax(scores / c1), softmax(re / c1)) c1^2                                  (KD.py:3-7)
+ *   PR: KL = KLDivLoss()(log_softmax(scores), softmax(softmax(scores) * exp(re - 1) * c1)), the teacher NOT detached:
+ *       the gradient flows through it as well                                                               (KD.py:10-18)
+ * KLDivLoss() is torch's default 'mean': the sum over all B L K elements over B L K, pad positions INCLUDED.  The scores of a
+ * pad position i >= len are C (f_{i+1} * b_{i+1}) of both chains continued through the raw tokens x[b][len..] (reverse() flips
+ * only the first len tokens, reverse(.., lengths + 1) only the first len + 1 rows of the backward stash; :222,:261), so both
+ * chains of every sequence, a sequence of length 0 included, and their back-propagation run L steps, x is read at every
+ * position (a word outside 0..V-1 is clamped) and the pad word's row of dVgen is not zero.  The cross-entropy / CRF term, the
+ * decode and the tags stay on the valid positions (tags are -1 at the pads).
+ * re_scores: float [B][L][K], the RE tagger's scores with the zero columns already appended (one without the CRF, three with
+ * it; :213-218) and cut to L.  pi is the weight of the original loss: c2_kdpr for KD, max(c2_kdpr, c3_pr ** t) for PR (:299),
+ * computed by the caller -- the library has no t.  The KL partials are added in a fixed order (no float atomic).
+ * FARNN_EINVAL: a null re_scores / teacher, a mode other than the two, c1 < 1 (main.py asserts c1_kdpr >= 1), pi outside
+ * [0, 1], a context set to FARNN_SEMIRING_MAX (its kernels walk the valid positions only).  Like every FARNN_ERANGE of the
+ * plain step, these are returned before anything is enqueued and leave the output buffers untouched.  A plain step before or
+ * after it on the same context is not affected: the teacher leaves no state behind. */
+#define FARNN_TEACHER_KD 1
+#define FARNN_TEACHER_PR 2
+typedef struct {
+    int32_t mode;               /* FARNN_TEACHER_KD or FARNN_TEACHER_PR                                          */
+    float   c1;                 /* KD: the temperature T; PR: the strength of the rule constraint (c1_kdpr)        */
+    float   pi;                 /* weight of the original loss; 1 - pi weighs the KL term                          */
+} farnn_teacher;
+int  farnn_decomp_ifst_teacher_train_step(farnn_train_ctx *ctx, const farnn_train_weights *w, const int64_t *x,
+                                          const int64_t *lengths, const int64_t *labels, const float *re_scores,
+                                          const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
+                                          const farnn_train_outputs *out, void *stream);
 /* accumulated HIP-event time of the step's launches since the last call (ms) and the number of steps timed;
  * profiling is enabled with farnn_train_set_profiling(ctx, 1) */
 int  farnn_train_set_profiling(farnn_train_ctx *ctx, int32_t enable);

@@ -118,6 +118,13 @@ class TrainOutputs(C.Structure):
                                           'dWss1', 'dWrs1', 'dbs1', 'dWss2', 'dWrs2', 'dbs2')]
 
 
+class Teacher(C.Structure):
+    _fields_ = [('mode', C.c_int32), ('c1', C.c_float), ('pi', C.c_float)]
+
+
+TEACHER = {'kd': 1, 'pr': 2}      # FARNN_TEACHER_KD, FARNN_TEACHER_PR
+
+
 class OnehotTrainDims(C.Structure):
     _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('C', C.c_int32), ('nl', C.c_int32), ('threshold', C.c_float),
                 ('o_idx', C.c_int32)]
@@ -221,6 +228,9 @@ SIGNATURES = {
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                                C.POINTER(TrainOutputs), C.c_void_p]),
+    'farnn_decomp_ifst_teacher_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(Teacher), C.c_int32, C.c_int32,
+                                                       C.c_int64, C.POINTER(TrainOutputs), C.c_void_p]),
     'farnn_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -651,6 +661,16 @@ class TrainContext(_TrainContextBase):
         self._open(TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
                              float(sigmoid_exponent), int(bool(use_crf))), device, semiring)
         self.dims = (int(V), int(S), int(R), int(K))
+
+    def teacher_step(self, weights, x_ptr, len_ptr, labels_ptr, re_ptr, mode, c1, pi, B, L, valid_tokens, outputs, stream=None):
+        """step() with the KD / PR teacher (farnn_decomp_ifst_teacher_train_step): re_ptr is the device pointer of the float
+        [B][L][K] teacher scores, mode 'kd' or 'pr' (or the raw FARNN_TEACHER_* value), pi the weight of the original loss."""
+        w = self._weights(**{k: (weights.get(k) or None) for k, _ in self._weights._fields_})
+        o = self._outputs(**{k: outputs.get(k) for k, _ in self._outputs._fields_})
+        t = Teacher(int(TEACHER.get(mode, mode)), float(c1), float(pi))
+        check(load().farnn_decomp_ifst_teacher_train_step(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, re_ptr, C.byref(t),
+                                                          int(B), int(L), int(valid_tokens), C.byref(o), stream),
+              'farnn_decomp_ifst_teacher_train_step')
 
 
 class OnehotTrainContext(_TrainContextBase):

@@ -14,6 +14,7 @@
 #include "common.hip.h"
 #include "host_util.hip.h"
 #include "train_host.hip.h"
+#include "train_teacher.hip.h"
 #include "train_bucketed.hip.h"
 #include "train_max.hip.h"
 #include "onehot_train_max.hip.h"
@@ -118,6 +119,7 @@ static void prep_add(PrepJobs &pj, int kind, const float *src, float *dst, size_
 // What a step needs, from the dimensions alone (train_plan)
 struct TrainPlan {
     bool crf, mx;
+    bool teacher;                       // a KD / PR step: both chains of every sequence run L steps, the loss walks every position
     int farnn, B, L;
     size_t S, R, K, V, N1, N0, nwmax;   // N1 = B (L+1) stash rows, N0 = B L positions, nwmax: bound on the batch's distinct words
     size_t need, mneed, mineed;         // floats of ws and of mws, ints of miws: the totals of the carve functions below
@@ -141,6 +143,7 @@ static size_t carve_train_ws(float *base, TrainParams &p, const TrainPlan &pl) {
     p.D1f = a.take(nR); p.D1b = a.take(nR); p.Tf = a.take(nR); p.Tb = a.take(nR);
     p.DS = a.take(pl.N0 * pl.K); p.AB = a.take(pl.N0 * pl.S);
     if (pl.crf) { p.SC = a.take(pl.N0 * pl.K); p.dtrans_part = a.take((size_t)pl.B * pl.K * pl.K); }
+    if (pl.teacher) p.loss_part = a.take((size_t)pl.lgrid * 8);      // one loss partial per wavefront of the teacher's loss kernel
     if (pl.farnn) {
         p.ZGf = a.take(nS); p.ZGb = a.take(nS); p.RGf = a.take(nS); p.RGb = a.take(nS); p.CDf = a.take(nS); p.CDb = a.take(nS);
         p.DAZf = a.take(nS); p.DAZb = a.take(nS); p.DARf = a.take(nS); p.DARb = a.take(nS); p.HBARf = a.take(nS);
@@ -178,7 +181,7 @@ static int train_validate(const farnn_train_ctx *c, const farnn_train_weights *w
 // Stage 2: host arithmetic only, no HIP call -- the workspace sizes, the kernel forms and the LDS bytes of every launch, from the
 // dimensions, the semiring, B, L, the device's CU count and the FARNN_TRAIN_* switches.  Every size the step refuses is refused
 // here, the launches above 160 KiB of LDS included: a refused step has enqueued nothing and has not touched the caller's outputs.
-static int train_plan(const farnn_train_ctx *c, int B, int L, TrainPlan &pl) {
+static int train_plan(const farnn_train_ctx *c, int B, int L, bool teacher, TrainPlan &pl) {
     const size_t S = c->d.S, R = c->d.R, K = c->d.K, V = c->d.V, SR = S > R ? S : R;
     const int farnn = c->d.farnn;
     const bool crf = c->d.use_crf != 0;
@@ -191,9 +194,10 @@ static int train_plan(const farnn_train_ctx *c, int B, int L, TrainPlan &pl) {
     // offsets against scalar base pointers (train.hip.h)
     if ((unsigned long long)B * (L + 1) * SR >= (1ull << 30) || (unsigned long long)V * SR >= (1ull << 30))
         return fail(FARNN_ERANGE, "train_step: B (L+1) max(S, R) and V max(S, R) must stay below 2^30 elements%s%s");
-    pl.crf = crf; pl.mx = c->semiring == FARNN_SEMIRING_MAX; pl.farnn = farnn; pl.B = B; pl.L = L;
+    pl.crf = crf; pl.mx = c->semiring == FARNN_SEMIRING_MAX; pl.teacher = teacher; pl.farnn = farnn; pl.B = B; pl.L = L;
     pl.S = S; pl.R = R; pl.K = K; pl.V = V;
     pl.N1 = (size_t)B * (L + 1); pl.N0 = (size_t)B * L; pl.nwmax = std::min(V, pl.N0);
+    pl.lgrid = (unsigned)std::min<size_t>(c->n_cu, (pl.N0 + 7) / 8);
     TrainParams p0; MaxWs m0;
     pl.need = carve_train_ws(nullptr, p0, pl); pl.mneed = carve_max_floats(nullptr, m0, pl); pl.mineed = carve_max_ints(nullptr, m0, pl);
 
@@ -234,9 +238,9 @@ static int train_plan(const farnn_train_ctx *c, int B, int L, TrainPlan &pl) {
     pl.lds_tok = (size_t)L * sizeof(int); pl.lds_m = ssb; pl.lds_w = tmax_wgrad_lds_bytes(S);
     pl.crf_big = train_crf_lds_bytes(K, L, false) > 160 * 1024;
     pl.lds_c = crf ? train_crf_lds_bytes(K, L, pl.crf_big) : 0;
-    pl.lgrid = (unsigned)std::min<size_t>(c->n_cu, (pl.N0 + 7) / 8);
     int rc;
     if ((rc = lds_fits(train_loss_lds(S, K).bytes())) || (rc = lds_fits(pl.lds_c))) return rc;
+    if (teacher && (rc = lds_fits(train_teacher_lds(S, K).bytes()))) return rc;
     if (pl.mx) return (rc = lds_fits(pl.lds_tok)) || (rc = lds_fits(pl.lds_m)) ? rc : lds_fits(pl.lds_w);
     return (rc = lds_fits(pl.lds_f)) ? rc : lds_fits(pl.lds_b);
 }
@@ -246,8 +250,13 @@ struct TrainStep : TrainPlan {
     farnn_train_ctx *c; const farnn_train_weights *w; const farnn_train_outputs *o; hipStream_t s;
     TrainParams p; MaxWs m; PrepJobs prep; AtbJobs gate_jobs, grad_jobs;
     float *dGVT;                        // dGV^T ([S][V]) as the A operand of dVgen += dGV Wrs^T
+    const float *re; const farnn_teacher *tch;      // the teacher's scores [B][L][K] and parameters; null: the plain step
     int validate() { return train_validate(c, w, o); }
-    int plan(int B_, int L_) { return train_plan(c, B_, L_, *this); }
+    int plan(int B_, int L_) {
+        if (int rc = teacher_check()) return rc;
+        return train_plan(c, B_, L_, tch != nullptr, *this);
+    }
+    int teacher_check() const; int teacher_loss();
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int prep_jobs(); int product_jobs();
     int prepare(); int forward(); int max_forward(); int loss(); int backward(); int max_weight_gradients(); int gradients();
@@ -288,6 +297,10 @@ int TrainStep::carve(const int64_t *x, const int64_t *lengths, const int64_t *la
     p.dVgen = o->dVgen; p.dOsum = c->dOsum; p.dh0 = o->dh0; p.dhT = o->dhT; p.loss = o->loss; p.tags = o->tags;
     p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.R = (int)R; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
     p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
+    if (teacher) {
+        p.full_chain = 1; p.re = re; p.t_mode = tch->mode; p.t_c1 = tch->c1; p.t_pi = tch->pi;
+        p.t_inv_n = (float)(1.0 / ((double)B * (double)L * (double)K));      // KLDivLoss(): the mean over ALL elements (KD.py:6,:17)
+    }
     if ((rc = prep_jobs()) || (rc = product_jobs())) return rc;
     // one buffer serves both reductions, one after the other on the stream
     if ((rc = c->part.ensure(std::max(atb_partial_floats(gate_jobs), atb_partial_floats(grad_jobs)),
@@ -399,6 +412,7 @@ int TrainStep::max_forward() {
 // Stage 6: the scores, the loss (cross-entropy or CRF), the decode, the adjoints of both chains' states
 int TrainStep::loss() {
     int rc;
+    if (teacher) return teacher_loss();
     if (!crf) return launch_train_loss<0>(p, lgrid, s);
     // emissions -> CRF forward-backward (loss, d loss / d emissions, transition counts, Viterbi tags) -> adjoints
     if ((rc = launch_train_loss<1>(p, lgrid, s))) return rc;
@@ -406,6 +420,35 @@ int TrainStep::loss() {
     if ((rc = crf_big ? launch(train_crf_kernel<true>, B, 256, lds_c, s, p) : launch(train_crf_kernel<false>, B, 256, lds_c, s, p))) return rc;
     crf_reduce_kernel<<<(unsigned)((K * K + 255) / 256), 256, 0, s>>>(p.dtrans_part, o->dtrans, B, (int)(K * K));
     return launch_train_loss<2>(p, lgrid, s);
+}
+// The teacher's refusals (stage 2: nothing is enqueued, the outputs stay untouched)
+int TrainStep::teacher_check() const {
+    if (!tch) return FARNN_OK;
+    if (!re) return fail(FARNN_EINVAL, "teacher_train_step: null teacher scores%s%s");
+    if (tch->mode != FARNN_TEACHER_KD && tch->mode != FARNN_TEACHER_PR)
+        return fail(FARNN_EINVAL, "teacher_train_step: mode must be FARNN_TEACHER_KD or FARNN_TEACHER_PR%s%s");
+    if (!(tch->c1 >= 1.0f) || !std::isfinite(tch->c1)) return fail(FARNN_EINVAL, "teacher_train_step: c1 must be at least 1 (main.py asserts it)%s%s");
+    if (!(tch->pi >= 0.0f && tch->pi <= 1.0f)) return fail(FARNN_EINVAL, "teacher_train_step: pi must lie in [0, 1]%s%s");
+    if (c->semiring == FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "teacher_train_step: the max semiring has no KD / PR teacher (its kernels walk the valid positions only)%s%s");
+    return FARNN_OK;
+}
+// Stage 6 with a teacher (train_teacher.hip.h): the same split around the CRF kernel, every position walked, then the loss
+// from the wavefronts' partials (and pi times the CRF's sum and transition gradient)
+int TrainStep::teacher_loss() {
+    int rc;
+    if (!crf) {
+        if ((rc = launch_teacher_loss<0>(p, lgrid, s))) return rc;
+    } else {
+        if ((rc = launch_teacher_loss<1>(p, lgrid, s))) return rc;
+        if ((rc = crf_big ? launch(train_crf_kernel<true>, B, 256, lds_c, s, p) : launch(train_crf_kernel<false>, B, 256, lds_c, s, p))) return rc;
+        crf_reduce_kernel<<<(unsigned)((K * K + 255) / 256), 256, 0, s>>>(p.dtrans_part, o->dtrans, B, (int)(K * K));
+        if ((rc = launch_teacher_loss<2>(p, lgrid, s))) return rc;
+    }
+    const int KK = crf ? (int)(K * K) : 0;
+    teacher_finish_kernel<<<(unsigned)std::max(1, (KK + 255) / 256), 256, 0, s>>>(p.loss_part, (int)lgrid * 8, o->loss, p.t_pi, crf ? 1 : 0,
+                                                                               crf ? o->dtrans : nullptr, KK);
+    return FARNN_OK;
 }
 // Stage 7: back-propagation through time (max semiring: max_backward)
 int TrainStep::backward() {
@@ -439,6 +482,16 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
                                             int64_t valid_tokens, const farnn_train_outputs *o, void *stream) {
     TunScope tun_scope(c ? &c->tun : nullptr);     // (a null context: run_train_step refuses it)
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
+}
+
+extern "C" int farnn_decomp_ifst_teacher_train_step(farnn_train_ctx *c, const farnn_train_weights *w, const int64_t *x,
+                                                    const int64_t *lengths, const int64_t *labels, const float *re_scores,
+                                                    const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
+                                                    const farnn_train_outputs *o, void *stream) {
+    TunScope tun_scope(c ? &c->tun : nullptr);
+    if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_train_step: null teacher argument%s%s");
+    return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
+                                     [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; });
 }
 
 // ---- training step of the onehot i-FST (FARNN_S_O_I_S; onehot_train.hip.h) -------------------------------

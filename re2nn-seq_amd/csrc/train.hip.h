@@ -56,6 +56,11 @@ struct TrainParams {
     float threshold, inv_tokens;
     float *loss_part;         // NULL: the loss is accumulated with atomics; else one partial per wavefront of train_loss_kernel
                               // ([gridDim.x * 8], summed in index order afterwards: the onehot step, onehot_train.hip.h)
+    // KD / PR teacher (train_teacher.hip.h; 0 / NULL in every other step)
+    int full_chain;           // 1: both chains of every sequence run L steps -- the teacher's KL reads the scores at the pad positions
+    const float *re;          // [B][L][K] the teacher's scores, zero columns already appended
+    int t_mode;               // FARNN_TEACHER_KD / FARNN_TEACHER_PR
+    float t_c1, t_pi, t_inv_n;   // temperature (KD) or rule strength (PR); weight of the original loss; 1 / (B L K)
 };
 
 __device__ __forceinline__ float nl_grad_from_output(float y, int nl) {
@@ -271,9 +276,12 @@ train_forward_kernel(const TrainParams p) {
         stage_matrix(wl + S * R + S * S, M3, R * S, tid, nt);
         M1 = wl; M2 = wl + S * R; M3 = wl + S * R + S * S;
     }
-    int len[NS], maxlen = 0;
+    // len: the steps of a sequence's chain -- its valid length, or L with a teacher (full_chain), whose chains go on through the
+    // pad tokens; vlen: the valid length, which only decides the order of the tokens below
+    int len[NS], vlen[NS], maxlen = 0;
     for (int q = 0; q < NS; q++) {
-        len[q] = b0 + q < p.B ? clamp_len(p.len[b0 + q], p.L) : 0;
+        vlen[q] = b0 + q < p.B ? clamp_len(p.len[b0 + q], p.L) : 0;
+        len[q] = (p.full_chain && b0 + q < p.B) ? p.L : vlen[q];
         maxlen = len[q] > maxlen ? len[q] : maxlen;
     }
     // the token of every step, in step order, so that no step waits for an index load
@@ -291,7 +299,8 @@ train_forward_kernel(const TrainParams p) {
     if (l_g2 && farnn == 2) stage_matrix(ssl + 2 * S * S, p.Wss2, S * S, tid, nt);
     for (int e = tid; e < NS * p.L; e += nt) {
         const int q = e / p.L, i = e - q * p.L;
-        toks[e] = i < len[q] ? clamp_tok(p.x[(long long)(b0 + q) * p.L + (dir == 0 ? i : len[q] - 1 - i)], p.V) : 0;
+        // the backward chain reads the valid tokens reversed and then, like the forward chain, the raw pad tokens (reverse(), utils.py:183-189)
+        toks[e] = i < len[q] ? clamp_tok(p.x[(long long)(b0 + q) * p.L + ((dir == 0 || i >= vlen[q]) ? i : vlen[q] - 1 - i)], p.V) : 0;
     }
     for (int e = tid; e < NS * SP + NS * RP; e += nt) f[e] = 0.0f;          // f | tv contiguous: pads stay zero
     if (farnn) for (int e = tid; e < NS * SP; e += nt) hv[e] = 0.0f;
@@ -839,9 +848,12 @@ train_backward_kernel(const TrainParams p) {
         stage_matrix(wl + 2 * S * R + S * S, Md, R * S, tid, nt);
         Ma = wl; Mb = wl + S * R; Mc = wl + 2 * S * R; Md = wl + 2 * S * R + S * S;
     }
-    int len[NS], maxlen = 0;
+    // len: the steps of a sequence's chain -- its valid length, or L with a teacher (full_chain), whose chains go on through the
+    // pad tokens; vlen: the valid length, which only decides the order of the tokens below
+    int len[NS], vlen[NS], maxlen = 0;
     for (int q = 0; q < NS; q++) {
-        len[q] = b0 + q < p.B ? clamp_len(p.len[b0 + q], p.L) : 0;
+        vlen[q] = b0 + q < p.B ? clamp_len(p.len[b0 + q], p.L) : 0;
+        len[q] = (p.full_chain && b0 + q < p.B) ? p.L : vlen[q];
         maxlen = len[q] > maxlen ? len[q] : maxlen;
     }
     int *toks = (int *)(pc + nw * NS * S);                     // [NS][L] tokens in step order
@@ -858,7 +870,8 @@ train_backward_kernel(const TrainParams p) {
     if (l_g2 && farnn == 2) stage_matrix(ssl + 2 * S * S, p.Wss2T, S * S, tid, nt);
     for (int e = tid; e < NS * p.L; e += nt) {
         const int q = e / p.L, i = e - q * p.L;
-        toks[e] = i < len[q] ? clamp_tok(p.x[(long long)(b0 + q) * p.L + (dir == 0 ? i : len[q] - 1 - i)], p.V) : 0;
+        // the backward chain reads the valid tokens reversed and then, like the forward chain, the raw pad tokens (reverse(), utils.py:183-189)
+        toks[e] = i < len[q] ? clamp_tok(p.x[(long long)(b0 + q) * p.L + ((dir == 0 || i >= vlen[q]) ? i : vlen[q] - 1 - i)], p.V) : 0;
     }
     for (int e = tid; e < 2 * NS * SP + NS * RP; e += nt) z[e] = 0.0f;          // z fp d1 contiguous: pads stay zero
     if (farnn) for (int e = tid; e < 2 * NS * SP; e += nt) dazv[e] = 0.0f;       // dazv | darv contiguous

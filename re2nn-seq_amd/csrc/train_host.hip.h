@@ -10,6 +10,7 @@
 #include "host_util.hip.h"
 #include "train.hip.h"
 #include "onehot_train.hip.h"
+#include "train_teacher.hip.h"
 
 namespace farnn {
 
@@ -125,12 +126,15 @@ inline int train_ctx_time(const char *name, TrainCtxBase *c, double *total_ms, i
 // validate() (its weights and outputs), plan(B, L) (host arithmetic only: every size the step refuses is refused there, before
 // anything is enqueued), carve(...) (grow the buffers, lay the workspaces out, fill the kernels' parameters) and stages() (the
 // launches, in order).  A step that returns before the end leaves no event pair behind (StepProfile::Guard).
-template <typename Step, typename Ctx, typename W, typename O>
+// `more`: what an entry point hands its step beyond the common arguments (the teacher of farnn_decomp_ifst_teacher_train_step).
+struct NoMore { template <typename Step> void operator()(Step &) const {} };
+template <typename Step, typename Ctx, typename W, typename O, typename More = NoMore>
 inline int run_train_step(Ctx *c, const W *w, const int64_t *x, const int64_t *lengths, const int64_t *labels, int B, int L,
-                          int64_t valid_tokens, const O *o, void *stream) {
+                          int64_t valid_tokens, const O *o, void *stream, More more = More()) {
     if (!c || !w || !x || !lengths || !labels || !o) return fail(FARNN_EINVAL, "%s_step: null argument%s", Step::name);
     Step t = {};
     t.c = c; t.w = w; t.o = o; t.s = reinterpret_cast<hipStream_t>(stream);
+    more(t);
     int rc, bad = 0;
     if ((rc = t.validate())) return rc;
     if (B <= 0 || L <= 0 || valid_tokens <= 0) return fail(FARNN_EINVAL, "%s_step: B, L and valid_tokens must be positive%s", Step::name);
@@ -196,6 +200,17 @@ inline int launch_train_loss(const TrainParams &p, unsigned grid, hipStream_t s)
     const LossLds l = train_loss_lds(p.S, p.K);
     return l.clds() ? launch(train_loss_kernel<true, PHASE>, grid, 512, l.bytes(), s, p)
                     : launch(train_loss_kernel<false, PHASE>, grid, 512, l.bytes(), s, p);
+}
+
+// train_teacher_loss_kernel<CLDS, PHASE> (train_teacher.hip.h): four score-wide vectors per wavefront instead of two
+inline LossLds train_teacher_lds(size_t S, size_t K) {
+    return {8 * (((S + 3) & ~(size_t)3) + 8 + 4 * K) * sizeof(float), ((K * (S + 1) + 3) & ~(size_t)3) * sizeof(float)};
+}
+template <int PHASE>
+inline int launch_teacher_loss(const TrainParams &p, unsigned grid, hipStream_t s) {
+    const LossLds l = train_teacher_lds(p.S, p.K);
+    return l.clds() ? launch(train_teacher_loss_kernel<true, PHASE>, grid, 512, l.bytes(), s, p)
+                    : launch(train_teacher_loss_kernel<false, PHASE>, grid, 512, l.bytes(), s, p);
 }
 
 // the loss of a step whose loss kernel leaves per-wavefront partials (8 per workgroup), added in order

@@ -8,6 +8,8 @@ weights are frozen on the tagging path, the per-token ``get_generalized_v_embed_
 (model_decompose.py:222-241) is folded once into a table ``Vgen[V,R]`` when the device handle is
 built -- the reference recomputes it twice per time step.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -181,11 +183,39 @@ class FARNN_S_D_W_I_S(NativeTagger):
                     'hT': 'train_hT', 'beta_vec': 'train_beta', 'embedding.weight': 'train_word_embed'}
 
     def _check_trainable(self, re_tags):
+        """Raises before any device work.  The KD / PR teacher terms (--marryup_type kd | pr) are opt-in
+        for their first release: RE2NN_DECOMP_TEACHER_TRAIN=1."""
         a = self.args
+        marryup = getattr(a, 'marryup_type', 'none')
+        teacher = marryup in ('kd', 'pr')
+        plain = re_tags is None and marryup in ('none', None)
+        opted_in = os.environ.get('RE2NN_DECOMP_TEACHER_TRAIN', '') == '1' and marryup in ('none', None, 'kd', 'pr')
         if a.farnn not in (0, 1, 2) or a.train_mode not in ('sum', 'max') or a.local_loss_func != 'CE1' \
-                or re_tags is not None or getattr(a, 'marryup_type', 'none') not in ('none', None):
+                or not (plain or opted_in):
             raise NotImplementedError('the HIP training step covers the sum and max semirings and the CE1 loss (with or '
                                       'without the CRF), no KD/PR teachers (DESIGN.md, row f3)')
+        if teacher and re_tags is None:
+            raise ValueError('--marryup_type {} needs the RE teacher\'s scores: forward_local(..., re_tags=...)'.format(marryup))
+        if re_tags is not None and not teacher:
+            raise ValueError('re_tags were given but --marryup_type is {!r}: the teacher term would be dropped silently'.format(marryup))
+        if teacher and a.train_mode == 'max':
+            raise NotImplementedError('the KD / PR teacher terms are built for the sum semiring only; --train_mode max walks the '
+                                      'valid positions only (DESIGN.md, row f3)')
+        return teacher
+
+    # PR's pi = max(c2_kdpr, c3_pr ** t) (ref :299).  The reference sets t = 1 in the constructor (model_decompose.py:42) and
+    # the decomposed models never advance it, so the exponent stays 1 here as well.
+    t = 1
+
+    def _teacher(self, re_tags, Lmax):
+        """(scores [B, Lmax, K], mode, c1, pi) of the teacher step: the zero columns of ref :213-218 (one without the CRF,
+        three with it), the cut to Lmax of :292-298, and the weight of the original loss."""
+        a = self.args
+        B, L, _ = re_tags.shape
+        re = torch.cat([re_tags.float(), torch.zeros(B, L, 3 if self.use_crf else 1, dtype=torch.float32, device=re_tags.device)],
+                       dim=2)[:, :Lmax]
+        pi = float(a.c2_kdpr) if a.marryup_type == 'kd' else max(float(a.c2_kdpr), float(a.c3_pr) ** self.t)
+        return re, a.marryup_type, float(a.c1_kdpr), pi
 
     def enable_training(self):
         """Device-resident leaf tensors for the optimizer (returned by parameters()) and the library context."""
@@ -261,7 +291,7 @@ class FARNN_S_D_W_I_S(NativeTagger):
             self.sync_from_training()
             return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
         from .train_step import decomp_ifst_train_step
-        self._check_trainable(re_tags)
+        teacher = self._check_trainable(re_tags)
         self.enable_training()
         tp = self._tp
         Lmax = int(lengths.max().item())
@@ -270,7 +300,8 @@ class FARNN_S_D_W_I_S(NativeTagger):
         loss, tags = decomp_ifst_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
                                             tp['C_output_mat'], tp['h0'], tp['hT'], self._tpP, x, lengths, lab,
                                             crf_trans=tp.get('crf.transitions'),
-                                            gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]))
+                                            gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]),
+                                            teacher=self._teacher(re_tags, Lmax) if teacher else None)
         self._dirty = True
         pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
         true = self._flatten(label, lengths).to(input.device)

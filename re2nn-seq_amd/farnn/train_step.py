@@ -11,7 +11,7 @@ computes loss and all gradients in its forward call (the stash lives in its work
 only hands them out, scaled by the incoming gradient.
 
 Scope: farnn = 0/1/2, sum or max semiring (TrainContext(semiring=...)), CE1 loss or (use_crf) the CRF
-negative log-likelihood.
+negative log-likelihood; in the sum semiring also with the KD / PR teacher term (teacher=...).
 
 The onehot i-FST (FARNN_S_O_I_S, model_onehot.py:351-428 + train_onehot.py:156-206) trains only
 language_tensor: one library call computes the loss, the tags and d loss / d language_tensor.
@@ -57,7 +57,7 @@ def _step_inputs(ref, ntok, x, lengths, labels):
 
 class _DecompIfstTrainStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cmat, h0, hT, trans, *gates):
+    def forward(ctx, tc, ntok, x, lengths, labels, teacher, P, Vgen, S1, S2, W, Cmat, h0, hT, trans, *gates):
         dev, ntok, x, lengths, labels, loss, tags = _step_inputs(Vgen, ntok, x, lengths, labels)
         B, L = x.shape
         ws = [_f32(t) for t in (Vgen, S1, S2, W, Cmat, h0, hT)]
@@ -77,8 +77,16 @@ class _DecompIfstTrainStep(torch.autograd.Function):
         for n, g, gg in zip(GATE_NAMES, gs, ggs):
             weights[n] = g.data_ptr()
             outputs['d' + n] = gg.data_ptr()
-        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if teacher is None:
+            tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs, stream)
+        else:
+            re, mode, c1, pi = teacher
+            re = re.detach().to(dev).float().contiguous()
+            if tuple(re.shape) != (B, L, Cmat.shape[0]):
+                raise ValueError('teacher scores must be [B, L, K] = {}, not {}'.format((B, L, Cmat.shape[0]), tuple(re.shape)))
+            tc.teacher_step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), re.data_ptr(), mode, c1, pi, B, L,
+                            ntok, outputs, stream)
         ctx.has_tr = gtr is not None
         ctx.n_gates = len(gs)
         ctx.save_for_backward(*(grads + ([gtr] if gtr is not None else []) + ggs))
@@ -95,15 +103,18 @@ class _DecompIfstTrainStep(torch.autograd.Function):
             gtr = saved[k] * gloss
             k += 1
         ggs = [g * gloss for g in saved[k:k + ctx.n_gates]]
-        return (None, None, None, None, None, None) + tuple(grads) + (gtr,) + tuple(ggs)
+        return (None, None, None, None, None, None, None) + tuple(grads) + (gtr,) + tuple(ggs)
 
 
 def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, labels, crf_trans=None, gates=(),
-                           valid_tokens=None):
+                           valid_tokens=None, teacher=None):
     """Returns (loss scalar tensor with grad, tags int32 [B,L] with -1 at pads).  gates: the tensors Wss1, Wrs1, bs1
     (farnn = 1) followed by Wss2, Wrs2, bs2 (farnn = 2), in that order.  valid_tokens: sum of the clamped lengths if
-    the caller already has it (device-resident lengths would otherwise cost a synchronising read per step)."""
-    return _DecompIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cmat, h0, hT, crf_trans,
+    the caller already has it (device-resident lengths would otherwise cost a synchronising read per step).
+    teacher: None, or (re_scores [B,L,K] with the zero columns appended, 'kd' | 'pr', c1, pi) for
+    loss = pi * original + (1 - pi) * KL (farnn_decomp_ifst_teacher_train_step, include/farnn.h); the teacher scores get no
+    gradient."""
+    return _DecompIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, teacher, P, Vgen, S1, S2, W, Cmat, h0, hT, crf_trans,
                                       *gates)
 
 

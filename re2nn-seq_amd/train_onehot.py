@@ -97,7 +97,11 @@ def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
         t0 = time.perf_counter()
         for batch in iter_batches(splits['train'], args.bz):
             optimizer.zero_grad()
-            loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True)
+            if args.method == 'decompose' and getattr(args, 'marryup_type', 'none') in ('kd', 'pr'):
+                # the RE teacher's scores of the batch (ref train_decompose.py:177-190; the step moves them to the device)
+                loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True, re_tags=batch['re'])
+            else:
+                loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True)
             loss.backward()
             optimizer.step()
             avg_loss += float(loss.detach())

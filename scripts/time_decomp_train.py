@@ -8,6 +8,11 @@ batch 256 x seqlen 64.  Prints one JSON line with, per semiring,
 
     python scripts/time_decomp_train.py [--steps 20] [--warmup 3] [--states 104] [--rank 250] [--farnn 2] [--crf 1]
 
+--teacher kd|pr times, in one job and `--repeats` times each in turn, the plain sum step on the ragged batch, the plain sum
+step on a full-length batch (the teacher's chains run B L steps instead of sum(len): that is its yardstick) and the teacher
+step (farnn_decomp_ifst_teacher_train_step) on the ragged batch, and prints their medians and spreads, the ratios and the
+hash of the sources the library was built from.
+
 Each GPU step of a job script runs it under its own time limit (timeout -k 10 ...)."""
 import argparse
 import json
@@ -20,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(a, semiring):
+def run(a, semiring, teacher=None, full=False):
     import torch
     from re2nn_seq_amd import _lib, synth
     from re2nn_seq_amd.farnn.train_step import decomp_ifst_train_step
@@ -45,17 +50,25 @@ def run(a, semiring):
         tr[K - 1, :] = -10000.0
         p['trans'] = torch.from_numpy(tr).to(dev).requires_grad_(True)
     x, lengths = synth.random_batch(V, B, L, brng)
+    if full:
+        lengths[:] = L
     labels = brng.randint(0, K - (2 if a.crf else 0), size=(B, L)).astype(np.int64)
     xd, ld, lab = torch.from_numpy(x).to(dev), torch.from_numpy(lengths).to(dev), torch.from_numpy(labels).to(dev)
     tc = _lib.TrainContext(V, S, R, K, nl='tanh', threshold=0.5, o_idx=0, use_crf=a.crf, farnn=a.farnn, sigmoid_exponent=5.0,
                            semiring=semiring)
     ntok = int(lengths.sum())
     opt = torch.optim.Adam(list(p.values()), lr=1e-4)
+    tch = None
+    if teacher:
+        re = (brng.rand(B, L, K) * 0.1).astype(np.float32)
+        re[brng.rand(B, L, K) < 0.15] = 0.95
+        re[..., K - (3 if a.crf else 1):] = 0.0
+        tch = (torch.from_numpy(re).to(dev), teacher, 2.0, 0.5)
 
     def one():
         opt.zero_grad(set_to_none=True)
         loss, _ = decomp_ifst_train_step(tc, p['Vgen'], p['S1'], p['S2'], p['W'], p['C'], p['h0'], p['hT'], None, xd, ld, lab,
-                                         crf_trans=p.get('trans'), gates=tuple(p[n] for n in gate_names), valid_tokens=ntok)
+                                         crf_trans=p.get('trans'), gates=tuple(p[n] for n in gate_names), valid_tokens=ntok, teacher=tch)
         loss.backward()
         opt.step()
         return loss
@@ -77,6 +90,34 @@ def run(a, semiring):
                 final_loss=float(loss.detach())), ntok, (V, S, R, K, B, L)
 
 
+def source_hash():
+    import hashlib
+    h = hashlib.sha256()
+    src = os.path.join(ROOT, 're2nn-seq_amd', 'csrc')
+    for fn in sorted(os.listdir(src)):
+        if fn.endswith(('.hip', '.h')):
+            with open(os.path.join(src, fn), 'rb') as f:
+                h.update(fn.encode() + b'\0' + f.read())
+    return h.hexdigest()[:16]
+
+
+def teacher_timing(a):
+    legs = {'plain_ragged': dict(), 'plain_full_length': dict(full=True), 'teacher_ragged': dict(teacher=a.teacher)}
+    times = {k: [] for k in legs}
+    for _ in range(a.repeats):                       # in turn, so that drift of the machine falls on all three alike
+        for k, kw in legs.items():
+            r, ntok, shape = run(a, 'sum', **kw)
+            times[k].append(r['lib_us_per_step'])
+    V, S, R, K, B, L = shape
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    out = dict(workload='decomp_train_teacher', teacher=a.teacher, V=V, S=S, R=R, K=K, B=B, L=L, farnn=a.farnn, crf=bool(a.crf),
+               steps=a.steps, repeats=a.repeats, source_hash=source_hash(), lib=os.environ.get('FARNN_LIB', 'default'),
+               lib_us_per_step={k: dict(median=med[k], min=min(v), max=max(v), runs=v) for k, v in times.items()},
+               teacher_over_plain_ragged=round(med['teacher_ragged'] / med['plain_ragged'], 3),
+               teacher_over_plain_full_length=round(med['teacher_ragged'] / med['plain_full_length'], 3))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
@@ -85,7 +126,11 @@ def main():
     ap.add_argument('--rank', type=int, default=250)
     ap.add_argument('--farnn', type=int, default=2)
     ap.add_argument('--crf', type=int, default=1)
+    ap.add_argument('--teacher', choices=('kd', 'pr'), default=None)
+    ap.add_argument('--repeats', type=int, default=5)
     a = ap.parse_args()
+    if a.teacher:
+        return teacher_timing(a)
     out = {}
     for semiring in ('sum', 'max'):
         out[semiring], ntok, shape = run(a, semiring)
