@@ -149,9 +149,15 @@ __device__ __forceinline__ void fma_h16(float &acc, const float blk, const float
     }
 }
 
-template <bool NLX, int D, int LPR, bool H16>
+// ONE (chain_regs_one_kernel: recurrence-only launch on the 16-bit image, `hist` in rows of HS = RD_XS floats): the chain's exchange word
+//      is its `hist` word bit for bit -- the forward chain's always (c_post == 1), the backward chain's because the model's o is absent
+//      or all ones (decided at create; a model with a general o keeps the two-store kernel) -- so a step stores ONE word, into `hist` row
+//      t + 1, with the wavefront's flag in lane 63 of that store, and the partners read the state of step t from `hist` row t (zeros
+//      behind S up to column RD_XS - 1: the set-up's).  No exchange rows, no parity; every row is stored once and never overwritten.
+//      Six LDS instructions per step instead of seven.
+template <bool NLX, int D, int LPR, bool H16, bool ONE = false>
 __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int dir, const int w, const int lane_in, const int nsteps,
-                                                  const long long *tokoff, float *flags, const float *ol, float *hist, float *xd,
+                                                  const long long *tokoff, float *flags, const float *ol, float *hist, const int HS, float *xd,
                                                   const bool probe, const int b, DestRing<D, LPR, H16> &ring) {
     static_assert(D == 2 || D == 4, "an even ring depth that divides 64 (the exchange row's parity and the address window)");
     static_assert(LPR == 4 || LPR == 5, "four or five lanes per output row");
@@ -185,11 +191,14 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
     float *dumpa = xd + 2 * RD_XS, *dumpb = dumpa + 64;
     // where this lane's results go: `hist` row t + 1 (advancing) and the exchange row of parity (t + 1) & 1; lanes without an
     // output store to dump slots, lane 63 stores the wavefront's flag with the exchange store
-    float *hptr = my_writer ? hist + SP + my_row : dumpa + lane;
-    const int hstep = my_writer ? SP : 0;
+    // (ONE: the flag rides in the `hist` store)
+    float *hptr = my_writer ? hist + HS + my_row : ((ONE && is_flane) ? flags + 4 * w : dumpa + lane);
+    const int hstep = my_writer ? HS : 0;
     float *xw0 = my_writer ? xbuf + my_row : (is_flane ? flags + 4 * w : dumpb + lane);              // into buffer 0
     float *xw1 = my_writer ? xbuf + RD_XS + my_row : (is_flane ? flags + 4 * w : dumpb + lane);      // into buffer 1
-    const float *xr = xbuf + 4 * rs;                     // this lane's chunks: xr + 4 LPR i (+ RD_XS for the odd buffer)
+    // this lane's chunks: xr + 4 LPR i (+ RD_XS for the odd buffer); ONE: of `hist` row t0, the first of the D rows a pass of the
+    // unrolled loop reads (row t0 + d at the immediate offset d RD_XS), moved on by D rows behind every pass
+    const float *xr = (ONE ? hist : xbuf) + 4 * rs;
     const int nl_mode = p.nl;
     const bool nl_relu = nl_mode == FARNN_NL_RELU;
     const int *pflag = reinterpret_cast<const int *>(flags) + 4 * (lane < RG_NWC ? lane : 0);
@@ -249,7 +258,7 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
     // t + D is conditional.  Unchecked: the caller guarantees t + D < nsteps (the steady state below).
     auto step = [&](auto checked, const int d, const int t) __attribute__((always_inline)) {
         constexpr bool CK = decltype(checked)::value;
-        const int roff = (d & 1) * RD_XS;                // the exchange buffer this step reads (t and d have the same parity)
+        const int roff = ONE ? d * RD_XS : (d & 1) * RD_XS;      // the exchange buffer this step reads (t and d have the same parity); ONE: `hist` row t
         // the partners' flags FIRST, this lane's five state chunks behind them in the same batch
         v4f st[NS];
         {
@@ -316,11 +325,17 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
         float hn;
         if (NLX) hn = apply_nl(pre, nl_mode);            // tanh, relu-tanh, sigmoid
         else     hn = nl_relu ? fmaxf(pre, 0.0f) : pre;  // none / relu: no branch in the step
-        const float hx = is_flane ? __int_as_float(t + 2) : hn * c_post;      // what the next step multiplies with; lane 63: the flag
         asm volatile("" ::: "memory");
-        *hptr = hn;                                      // row t + 1 of `hist` (or a dump slot)
-        hptr += hstep;
-        if (d & 1) *xw0 = hx; else *xw1 = hx;            // the exchange row of parity (t + 1) & 1, the flag behind it in the same store
+        if constexpr (ONE) {
+            // (hn * c_post == hn: c_post is exactly 1 in this chain)
+            *hptr = is_flane ? __int_as_float(t + 2) : hn;       // row t + 1 of `hist` = what the next step multiplies with; lane 63: the flag
+            hptr += hstep;
+        } else {
+            const float hx = is_flane ? __int_as_float(t + 2) : hn * c_post;      // what the next step multiplies with; lane 63: the flag
+            *hptr = hn;                                      // row t + 1 of `hist` (or a dump slot)
+            hptr += hstep;
+            if (d & 1) *xw0 = hx; else *xw1 = hx;            // the exchange row of parity (t + 1) & 1, the flag behind it in the same store
+        }
         asm volatile("" ::: "memory");
         // the slot's registers are dead: the block of step t + D
         // (16-bit form: the slot's old values are named here as inputs, which keeps them live up to the issue, so the compiler finds no
@@ -344,6 +359,7 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
         for (; t0 + 2 * D <= nsteps; t0 += D) {
 #pragma unroll
             for (int d = 0; d < D; d++) step(std::false_type{}, d, t0 + d);
+            if constexpr (ONE) xr += D * RD_XS;
         }
     }
     for (; t0 < nsteps; t0 += D) {
@@ -353,6 +369,7 @@ __device__ __forceinline__ void regs_compute_dest(const RegsParams &p, const int
             if (t >= nsteps) break;
             step(std::true_type{}, d, t);
         }
+        if constexpr (ONE) xr += D * RD_XS;
     }
     // (the last step stored nsteps + 1: writer / scorer count the rows of `hist` by these flags)
 #if defined(FARNN_PROBES)

@@ -2,6 +2,7 @@
 // build-flags: -fno-slp-vectorize
 // build-check: ring-registers Lb1ELb0EEEvNS_10RegsParamsE
 // build-check: ring-registers Lb1ELb1EEEvNS_10RegsParamsE
+// build-check: ring-registers chain_regs_one_kernel
 // (the destination-split kernels -- template arguments <.., DEST = true, H16 = false | true> -- keep a ring of in-flight global loads in ordinary asm outputs
 //  (chain_dest.hip.h): csrc/build.py fails the build if the compiler ever copies or spills one of them while its load is in flight)
 // (the step's sixteen FMAs and its add tree stay scalar: hipcc's SLP pass packs them into v_pk_fma_f32 / v_pk_add_f32, which
@@ -18,13 +19,32 @@ namespace farnn {
 int launch_chain_regs(const RegsParams &p, bool maxsr, bool score, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int NP = RG_NWC * p.G;
     const bool dest = p.dest && !maxsr;                                   // the destination-split compute wavefronts (chain_dest.hip.h)
-    const size_t lds = (size_t)regs_lds(p.L, p.SP, NP, p.sp.c16, p.sp.Kc, score, RG_RQ, score && bs_label_map_path(p.sp), dest).total * sizeof(float);
-    const dim3 grid(2 * p.B), block(RG_WAVES * 64);
     const bool half = dest && !score && p.half && p.Mf16 && p.Mb16;      // (farnn_hip.hip, launch_chain, decides; here: what the kernel needs)
+    const size_t lds = (size_t)regs_lds(p.L, p.SP, NP, p.sp.c16, p.sp.Kc, score, RG_RQ, score && bs_label_map_path(p.sp), dest,
+                                        dest && !score && p.row80 && p.o_ones && half).total * sizeof(float);
+    const dim3 grid(2 * p.B), block(RG_WAVES * 64);
     int rc;
     // NLX: tanh / relu-tanh / sigmoid between the steps (the kernel's none / relu form has no branch in the step)
     const bool nlx = p.nl != FARNN_NL_NONE && p.nl != FARNN_NL_RELU;
     const bool lmo = score && bs_label_map_path(p.sp);                     // the label-map instantiation (no matrix-core tile code)
+#if FARNN_STEP_ONESTORE && FARNN_CHAIN_HEAD
+    // one store per step (chain_dest.hip.h): the recurrence-only launch on the 16-bit image of a model whose o is absent or all ones,
+    // `hist` in rows of RD_XS floats
+    if (dest && !score && p.row80 && p.o_ones && half) {
+#define FARNN_LAUNCH_ONE(NX)                                                                   \
+    do {                                                                                       \
+        if ((rc = raise_lds_limit(chain_regs_one_kernel<NX>, lds))) return rc;                 \
+        if (e0 && e1)                                                                          \
+            hipExtLaunchKernelGGL((chain_regs_one_kernel<NX>), grid, block, (uint32_t)lds, s, e0, e1, 0, p); \
+        else                                                                                   \
+            chain_regs_one_kernel<NX><<<grid, block, lds, s>>>(p);                             \
+    } while (0)
+        if (nlx) FARNN_LAUNCH_ONE(true); else FARNN_LAUNCH_ONE(false);
+#undef FARNN_LAUNCH_ONE
+        FARNN_HIP_TRY(hipGetLastError());
+        return FARNN_OK;
+    }
+#endif
 #define FARNN_LAUNCH_REGS6(MX, SC, NX, LM, DS, HF)                                             \
     do {                                                                                       \
         if ((rc = raise_lds_limit(chain_regs_kernel<MX, SC, NX, LM, DS, HF>, lds))) return rc; \

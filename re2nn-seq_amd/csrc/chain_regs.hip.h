@@ -131,7 +131,9 @@ constexpr int RGM_SEL = 30;      // misc[30], misc[31]: {sequence, length} from 
 // LMO: label-map path only (the paired wide form): the matrix-core tile code is compiled out.
 // DEST: the compute wavefronts split the block by destination (chain_dest.hip.h; narrow form, sum semiring).
 // H16: ... and read the blocks' 16-bit image (recurrence-only launch of a model whose every block entry is an f16 exactly).
-template <bool MAXSR, bool SCORE, bool NLX, int RQ = RG_RQ, int D = RG_D, bool LMO = false, bool DEST = false, bool H16 = false>
+// ONE: ... with `hist` in rows of RD_XS floats and one store per step in both chains (a model whose o is absent or all ones:
+//      chain_regs_one_kernel, picked by the host -- RegsParams::row80).
+template <bool MAXSR, bool SCORE, bool NLX, int RQ = RG_RQ, int D = RG_D, bool LMO = false, bool DEST = false, bool H16 = false, bool ONE = false>
 __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem, const int tid, const int item, int *b_out) {
     constexpr bool WIDE = RQ != RG_RQ;
     static_assert(!DEST || (!WIDE && !MAXSR), "the destination-split form exists for the narrow kernel and the sum semiring");
@@ -146,7 +148,12 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
     const int S = p.S, SP = p.SP, G = p.G, RPG = p.RPG, NP = RG_NWC * G;
     const int PS = WIDE ? p.PS : SP;                                  // floats between two partial-sum vectors
     const bool lm_path = SCORE && (LMO || bs_label_map_path(p.sp));     // the tiles are scored through the label map: no tile areas in LDS
-    const RegsLds lds = regs_lds(p.L, SP, NP, p.sp.c16, p.sp.Kc, SCORE, RQ, lm_path, DEST);
+    // ONE: `hist` in rows of RD_XS floats (HS = floats between two rows) and ONE store per step: the chain's exchange word is its `hist`
+    // word (chain_dest.hip.h) -- the forward chain's always (c_post == 1), the backward chain's because o is absent or all ones
+    static_assert(!ONE || (DEST && !SCORE && H16 && (FARNN_CHAIN_HEAD != 0) && (FARNN_STEP_ONESTORE != 0)), "the one-store step belongs to the recurrence-only launch's head");
+    constexpr bool row80 = ONE;
+    const int HS = row80 ? RD_XS : SP;
+    const RegsLds lds = regs_lds(p.L, SP, NP, p.sp.c16, p.sp.Kc, SCORE, RQ, lm_path, DEST, row80);
     long long *tokoff = reinterpret_cast<long long *>(smem + lds.tok);     // [nsteps] byte offset of step k's block
     float *part = smem + lds.part, *ol = smem + lds.ol, *hist = smem + lds.hist;
     float *ab = smem + lds.ab, *scl = smem + lds.scl, *obuf = smem + lds.obuf;
@@ -176,16 +183,19 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
             // Of `hist` only what is read before it is written: row 0, and the pad columns S .. SP - 1 of rows 1 .. L (the compute
             // lanes write every column below S of a row they finish; the writer copies whole SP-wide rows, and the stash's readers
             // take the pads as exact zeros).  At most three words a row, at S not a multiple of four: nothing wider than a dword fits.
+            // (ONE: rows of RD_XS floats, pads up to column RD_XS - 1 -- 80 - S words a row)
             const int t = tid - 64;
             constexpr int nt = nthreads - 64;
-            for (int j = t; j < SP; j += nt) {
-                ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
+            // (rows of RD_XS floats: the pads reach column RD_XS - 1 -- the compute lanes of a one-store chain read whole rows as their
+            //  state, chunks behind the row's columns included, and multiply them with whatever finite bytes the block holds there)
+            for (int j = t; j < HS; j += nt) {
+                if (j < SP) ol[j] = (p.o && j < S) ? p.o[j] : 1.0f;
                 hist[j] = (j < S) ? hinit[j] : 0.0f;
             }
-            const int npad = SP - S;
+            const int npad = HS - S;
             for (int j = t; j < p.L * npad; j += nt) {
                 const int r = j / npad;
-                hist[(r + 1) * SP + S + (j - r * npad)] = 0.0f;
+                hist[(r + 1) * HS + S + (j - r * npad)] = 0.0f;
             }
             if (t < RGM_SEL) misc[t] = t == RGM_ACQ ? -1 : 0;
             if (t < 2) part[t * PSTR + PSTR - 1] = 0.0f;                        // the reduction's identity (masked reads)
@@ -300,7 +310,7 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
 #endif
                 if constexpr (!PRIME_EARLY) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
                 if (w == 0) FARNN_HD_STAMP(3);
-                regs_compute_dest<NLX, RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, smem + lds.xd, probe_, b, dring);
+                regs_compute_dest<NLX, RD_D, RD_LPR, H16, ONE>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, HS, smem + lds.xd, probe_, b, dring);
                 __builtin_amdgcn_s_setprio(0);
                 if (w == 0) { FARNN_RG_STAMP(2); FARNN_HD_STAMP(4); }
 #if defined(FARNN_PROBES)
@@ -588,7 +598,15 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
             const float *src = hist + r0 * SP;
             float *dst = stash + (long long)r0 * SP;
             const int nfl = (r1 - r0 + 1) * SP;
-            if (SCORE) {
+            if constexpr (row80) {
+                // rows of RD_XS floats in LDS, of SP floats in the stash: row by row, SP <= 72 floats = two words a lane at most
+                for (int r = r0; r <= r1; r++) {
+                    const float *s_ = hist + r * HS;
+                    float *d_ = stash + (long long)r * SP;
+                    if (lane < SP) d_[lane] = s_[lane];
+                    if (lane + WAVE < SP) d_[lane + WAVE] = s_[lane + WAVE];
+                }
+            } else if (SCORE) {
                 for (int j = 2 * lane; j < nfl; j += 2 * WAVE) st2_agent(dst + j, src[j], src[j + 1]);
             } else {
                 for (int j = lane; j < nfl; j += WAVE) dst[j] = src[j];
@@ -774,6 +792,31 @@ chain_wide_kernel(const RegsParams p) {
     extern __shared__ __align__(16) float smem[];
     chain_regs_body<MAXSR, SCORE, NLX, RQ, D>(p, smem, (int)threadIdx.x, (int)blockIdx.x, nullptr);
 }
+
+#if FARNN_STEP_ONESTORE && FARNN_CHAIN_HEAD
+// the recurrence-only launch of the destination split on the 16-bit image for a model whose o is absent or all ones: ONE store per
+// step (chain_dest.hip.h).  (The f32 blocks keep the two-store kernel: with the one-store step the compiler copied ring registers of
+// the f32 ring while their loads were in flight -- the build's ring-register check, 18 and 42 findings -- so that form is not built.)
+template <bool NLX>
+__global__ void __launch_bounds__(RG_WAVES * 64, 4)
+chain_regs_one_kernel(const RegsParams p) {
+    extern __shared__ __align__(16) float smem[];
+#if defined(FARNN_PROBES)
+    long long w0r = 0, w0c = 0;                          // (FARNN_DBG & 2048: chain_regs_kernel says what these are)
+    if ((p.dbg & 2048) && threadIdx.x == 0) { w0r = (long long)__builtin_amdgcn_s_memrealtime(); w0c = (long long)__builtin_amdgcn_s_memtime(); }
+    int b_probe = -1;
+    chain_regs_body<false, false, NLX, RG_RQ, RG_D, false, true, true, true>(p, smem, (int)threadIdx.x, (int)blockIdx.x, &b_probe);
+    if ((p.dbg & 2048) && threadIdx.x == 0 && blockIdx.x < WG_STAMP_MAX) {
+        const long long w1r = (long long)__builtin_amdgcn_s_memrealtime(), w1c = (long long)__builtin_amdgcn_s_memtime();
+        long long *o = g_wg_stamps + 16 * (long long)blockIdx.x;
+        o[0] = b_probe; o[1] = b_probe >= 0 ? (long long)p.len[b_probe] : -1; o[2] = w0r; o[3] = w1r; o[4] = w1c - w0c;
+        o[5] = 0; o[6] = 0; o[7] = 0;
+    }
+#else
+    chain_regs_body<false, false, NLX, RG_RQ, RG_D, false, true, true, true>(p, smem, (int)threadIdx.x, (int)blockIdx.x, nullptr);
+#endif
+}
+#endif
 
 // the wide form PAIRED: a ring of two steps fits 128 VGPRs (RQ <= 9), the label-map path's LDS half a compute unit
 template <bool MAXSR, bool NLX, int RQ>

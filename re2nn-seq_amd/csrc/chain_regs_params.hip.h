@@ -5,6 +5,20 @@
 #include "common.hip.h"
 #include "score_params.hip.h"
 
+// The lone step's LDS instructions (chain_dest.hip.h; the recurrence-only launch of the destination split).
+// 0 gives the step as it was: a variant build for A/B runs.
+#ifndef FARNN_CHAIN_HEAD
+#define FARNN_CHAIN_HEAD 1      /* (chain_regs.hip.h) */
+#endif
+// (Not in the profiling build: the build's ring-register check does not run there, and with the probes compiled in the compiler
+//  copied the one-store kernel's ring registers while their loads were in flight -- wrong tags.  It runs the two-store kernel.)
+#if defined(FARNN_PROBES) && !defined(FARNN_STEP_ONESTORE)
+#define FARNN_STEP_ONESTORE 0
+#endif
+#ifndef FARNN_STEP_ONESTORE
+#define FARNN_STEP_ONESTORE 1   /* a chain whose exchange word is its `hist` word stores ONE word per step, into `hist` rows of RD_XS floats */
+#endif
+
 namespace farnn {
 
 constexpr int RG_NWC = 6;        // compute wavefronts
@@ -57,6 +71,9 @@ struct RegsParams {
     int solo_margin;             // the scorer starts a tile alone only if the chain has at least this many steps left after it
     int dest;                    // 1: the destination-split form of the compute wavefronts (chain_dest.hip.h; narrow form, sum semiring)
     int half;                    // 1: ... reading the 16-bit image (recurrence-only launch; Mf16 / Mb16 set)
+    int row80;                   // 1: ... with `hist` rows RD_XS floats apart and one store per step (recurrence-only launch of a model with
+                                 //    o_ones, where the carve fits: chain_regs_one_kernel)
+    int o_ones;                  // 1: o is absent or every entry is exactly 1.0f (decided at create)
     ScoreParams sp;
 };
 constexpr int RG_NG = 5;         // state groups of 16 the scoring stage of this kernel reaches (S <= 72 -> c16 <= 5)
@@ -104,7 +121,9 @@ struct RegsLds {
 // rq: rows per lane and step of the form (RG_RQ: S <= 72; larger: the wide form, whose partial-sum buffers and exchange area differ)
 // lm: the label-map path scores the tiles (label_map.hip.h): no products, no score tiles in LDS
 // dest: the destination-split form (chain_dest.hip.h): its exchange rows
-__host__ __device__ inline RegsLds regs_lds(int L, int SP, int NP, int c16, int Kc, bool score, int rq = RG_RQ, bool lm = false, bool dest = false) {
+// row80: ... its recurrence-only launch with `hist` rows RD_XS floats apart (RegsParams::row80)
+__host__ __device__ inline RegsLds regs_lds(int L, int SP, int NP, int c16, int Kc, bool score, int rq = RG_RQ, bool lm = false, bool dest = false,
+                                            bool row80 = false) {
     const bool wide = rq != RG_RQ;
     RegsLds l;
     int at = 0;
@@ -112,7 +131,7 @@ __host__ __device__ inline RegsLds regs_lds(int L, int SP, int NP, int c16, int 
     l.hp = at;
     l.part = at; at += 2 * (wide ? rgw_part_stride(rq) : RG_PART_STRIDE) + 64 * 4;     // two partial-sum buffers + the idle lanes' dump slots
     l.ol = at;   at += SP;
-    l.hist = at; at += (L + 1) * SP + 16;          // + the launch-order scratch's tail
+    l.hist = at; at += (L + 1) * (row80 ? RD_XS : SP) + 16;          // + the launch-order scratch's tail
     l.ab = at;   at += (score && !lm) ? 2 * RG_TT * (16 * c16 + 4) : 0;    // two tiles' products
     l.scl = at;  at += (score && !lm) ? 2 * RG_TT * Kc : 0;               // two tiles' scores
     l.obuf = at; at += score ? 2 * RG_TT * SP : 0;    // RG_NOB tiles of the other direction's rows

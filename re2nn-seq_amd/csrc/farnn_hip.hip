@@ -169,6 +169,7 @@ static RegsParams make_regs_params(farnn_model *m, const int64_t *x, const int64
     rp.nl = m->nl; rp.full = full; rp.dbg = tun(TUN_DBG);
     rp.dest = (!rg.wide && m->semiring != FARNN_SEMIRING_MAX && !tun(TUN_NODEST)) ? 1 : 0;     // chain_dest.hip.h
     rp.Mf16 = m->Mf16; rp.Mb16 = m->Mb16; rp.blk16 = (long long)m->SP * RD_XS * 2;              // (null: no image, build_half_image)
+    rp.o_ones = (!m->o || m->o_ones) ? 1 : 0;                                                    // (build_output_matrix)
     return rp;
 }
 
@@ -215,6 +216,14 @@ static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, in
             score = false;
             lds = (size_t)regs_lds(m->curL, m->SP, rg.NP, 0, 0, false, rg.RQ, false, dest).total * sizeof(float);
         }
+        // the destination split's recurrence-only launch on the 16-bit image of a model whose o is absent or all ones keeps `hist` in rows of RD_XS floats
+        // where that fits beside a second workgroup (chain_dest.hip.h: one store per step, chain_regs_one_kernel); where it does not --
+        // the longest sequences this kernel takes -- rows of SP floats and two stores as before
+        bool row80 = false;
+        if (dest && !score && (!m->o || m->o_ones) && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF) && FARNN_STEP_ONESTORE && FARNN_CHAIN_HEAD) {
+            const size_t lds80 = (size_t)regs_lds(m->curL, m->SP, rg.NP, 0, 0, false, rg.RQ, false, dest, true).total * sizeof(float);
+            if (lds80 <= lds_cap) { row80 = true; lds = lds80; }
+        }
         if (lds <= lds_cap) {
             RegsParams rp = make_regs_params(m, x, len, B, full);
             if (score) {
@@ -232,6 +241,7 @@ static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, in
             // the 16-bit image where the handle has one (an eligible model, build_half_image): the recurrence-only launch of the
             // destination split reads half the bytes with half the load instructions; FARNN_NOHALF=1 keeps the f32 blocks
             rp.half = (rp.dest && !score && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF)) ? 1 : 0;
+            rp.row80 = row80 ? 1 : 0;
             KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
             if (paired && score) { rp.D = 2; rp.pair = 1; }
             const int rc = (paired && score) ? launch_chain_wide_paired(rp, m->semiring == FARNN_SEMIRING_MAX, s, kt.e0, kt.e1)

@@ -28,6 +28,15 @@ __global__ void colsum_kernel(const float *src, float *dst, int rows, int cols) 
     dst[c] = s;
 }
 
+// *bad = 1 if any of the n floats is not exactly 1.0f (o of a model whose every state carries one label: the backward chain's
+// exchange word then is its `hist` word bit for bit -- chain_dest.hip.h, one store per step)
+__global__ void not_all_ones_kernel(const float *v, int n, int *bad) {
+    bool no = false;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        no |= __float_as_uint(v[i]) != 0x3f800000u;
+    if (no) atomicExch(bad, 1);
+}
+
 // Mf[v][s][jp] = (T[v][s][j] + W[s][j]) * mask[s][j];  Mb[v][j][sp] = the same value transposed.
 // grid = (ceil(S*SP/256), V)
 __global__ void premix_kernel(const float *T, const float *W, const float *mask, float *Mf, float *Mb,

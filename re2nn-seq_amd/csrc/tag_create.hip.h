@@ -207,9 +207,14 @@ static int build_output_matrix(farnn_model *m, const float *src, int rows, int o
     colsum_kernel<<<(m->S + 255) / 256, 256>>>(O, m->o, rows, m->S);
     int n = rows * m->S;
     transpose_pad_kernel<<<(n + 255) / 256, 256>>>(O, m->OT, rows, m->S, m->Kc);
+    int *bad = nullptr, bad_h = 1;
+    if ((rc = tmp.zeros(&bad, 1))) return rc;
+    not_all_ones_kernel<<<1, 256>>>(m->o, m->S, bad);
     FARNN_HIP_TRY(hipGetLastError());
     if ((rc = build_ot_image(m))) return rc;
     FARNN_HIP_TRY(hipDeviceSynchronize());
+    FARNN_HIP_TRY(hipMemcpy(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost));
+    m->o_ones = bad_h == 0;
     if ((rc = build_label_map(m))) return rc;
     m->dw.o = m->o;
     return FARNN_OK;
@@ -638,6 +643,7 @@ static int upload_ones_o(farnn_model *m) {
     int rc = dev_upload(m, &m->o, ones.data(), m->SP, m->SP, 0);
     if (rc) return rc;
     m->dw.o = m->o;
+    m->o_ones = true;
     return FARNN_OK;
 }
 

@@ -67,6 +67,7 @@ struct farnn_model {
     float *A4 = nullptr;                    // fst4: [V][C][S][SP] premixed T4+W4
     float *Oten = nullptr;                  // ind1: [C][S][SP]
     float *o = nullptr, *h0 = nullptr, *hT = nullptr;
+    bool o_ones = false;                    // every entry of o below S is exactly 1.0f (build_output_matrix: a device-side test at create)
     float *OT = nullptr, *P = nullptr, *tr = nullptr;
     float *OTm = nullptr; int c16 = 0;       // matrix-core image of OT for score_tiles (ot_to_mfma_kernel)
     LabelMap lm = {nullptr, 0, 0, -1, 0.0f, 0, 0, 0.0f}; // the output matrix as a label map, when it is one (label_map.hip.h)
