@@ -648,6 +648,28 @@ void farnn_decomp_ind1_train_destroy(farnn_decomp_ind1_train_ctx *ctx);
 int  farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_decomp_ind1_train_weights *w, const int64_t *x,
                                   const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                   int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *out, void *stream);
+/* The same step under --use_crf 1, on the same context (as farnn_decomp_ifst_teacher_train_step sits beside the plain f3 step).
+ * The context's C is the score width, labels + 2 (model_decompose_independent.py:45-47, :78-80): tags C-2 / C-1 are START / STOP.
+ *   emissions = scores [. P]                                                      (model_decompose_independent.py:277-278)
+ *   loss = sum over the sequences of log Z - gold (:293; baselines/crf.py:253-260): a SUM, valid_tokens does not scale it.
+ *     log Z: alpha_0[j] = trans[START][j] + f_0[j]; alpha_t[j] = logsumexp_i(alpha_{t-1}[i] + trans[i][j]) + f_t[j] over the
+ *     valid positions; log Z = logsumexp_i(alpha_{n-1}[i] + trans[i][STOP])       (crf.py:48-99)
+ *     gold = sum_t (f_t[y_t] + trans[y_{t-1}][y_t]) with y_{-1} = START, + trans[y_{n-1}][STOP]: no START energy beyond the
+ *     bigram of position 0                                                        (crf.py:202-251)
+ *   dtrans [C][C] = expected - gold transition counts, the sequences' slices added in sequence order; the gradients of `out`
+ *     follow from d loss / d emissions = marginals - gold one-hot through the priority layer and the plain step's backward.
+ *   tags: the Viterbi path of the emissions with column C-3 clamped at threshold, the first index winning a tie, column C-3
+ *     written as o_idx (model_decompose.py:339-371; crf.py:102-195), -1 at the pads.
+ * The context's semiring applies to the two recurrences as in the plain step (the reference sends nothing else through
+ * semiring_func).  A sequence of length 0 contributes nothing to the loss, to dtrans or to any gradient; its tags are -1 (the
+ * reference cannot run one: crf.py:232 gathers at length - 1).
+ * FARNN_EINVAL: crf_trans or dtrans NULL, C < 4.  FARNN_ERANGE, naming the quantity, before anything is enqueued and with the
+ * outputs untouched: the CRF kernel's LDS at this (C, L), C (C + 1) * 4 + 9 L C + ... bytes in its large-tag-set form, beyond
+ * 160 KiB (the largest C accepted: 190 at L = 8, 140 at L = 64).  No float atomics: two steps on the same inputs are bit-identical. */
+int  farnn_decomp_ind1_crf_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_decomp_ind1_train_weights *w,
+                                      const float *crf_trans /* [C][C] */, const int64_t *x, const int64_t *lengths,
+                                      const int64_t *labels, int32_t B, int32_t L, int64_t valid_tokens,
+                                      const farnn_decomp_ind1_train_outputs *out, float *dtrans /* [C][C] */, void *stream);
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);

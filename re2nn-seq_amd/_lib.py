@@ -220,6 +220,9 @@ SIGNATURES = {
     'farnn_decomp_ind1_train_step': (C.c_int, [C.c_void_p, C.POINTER(Decomp1TrainWeights), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                                C.POINTER(Decomp1TrainOutputs), C.c_void_p]),
+    'farnn_decomp_ind1_crf_train_step': (C.c_int, [C.c_void_p, C.POINTER(Decomp1TrainWeights), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                                   C.POINTER(Decomp1TrainOutputs), C.c_void_p, C.c_void_p]),
     'farnn_decomp_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_decomp_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -722,6 +725,15 @@ class Decomp1TrainContext(_TrainContextBase):
         self._open(Decomp1TrainDims(int(V), int(S), int(R), int(RO), int(n_cols), NL[nl], float(threshold), int(o_idx)), device,
                    semiring)
         self.dims = (int(V), int(S), int(R), int(RO), int(n_cols))
+
+    def step_crf(self, weights, trans_ptr, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, dtrans_ptr, stream=None):
+        """step() under --use_crf 1 (farnn_decomp_ind1_crf_train_step): trans_ptr / dtrans_ptr are the device pointers of the
+        float [C][C] CRF transitions and of their gradient; n_cols counts START and STOP."""
+        w = self._weights(**{k: (weights.get(k) or None) for k, _ in self._weights._fields_})
+        o = self._outputs(**{k: outputs.get(k) for k, _ in self._outputs._fields_})
+        check(load().farnn_decomp_ind1_crf_train_step(self._raw, C.byref(w), trans_ptr, x_ptr, len_ptr, labels_ptr, int(B), int(L),
+                                                      int(valid_tokens), C.byref(o), dtrans_ptr, stream),
+              'farnn_decomp_ind1_crf_train_step')
 
 
 class Optim:

@@ -21,6 +21,7 @@
 #include "fst4_train.hip.h"
 #include "ind1_train.hip.h"
 #include "decomp1_train.hip.h"
+#include "train_bucketed_crf.hip.h"
 #include "optim.hip.h"
 
 using namespace farnn;
@@ -915,6 +916,10 @@ struct Decomp1Step : BucketedStep<farnn_decomp_ind1_train_ctx, farnn_decomp_ind1
     static constexpr const char *name = "decomp_ind1_train", *label_range = "C";
     size_t R, RO;
     D1BackParams bp;
+    // farnn_decomp_ind1_crf_train_step: the CRF stage in loss_on_scores' place (train_bucketed_crf.hip.h)
+    bool crf;
+    const float *crf_trans; float *dtrans;
+    BucketedCrf cs;
     float *BR, *DBR, *Nw, *dN, *Kfac, *Ofac, *E, *Osum, *dOsum, *zero, *csum, *dcsum, *fpart, *HP;
     size_t carve_ws(float *base);
     int validate(); int plan(int B, int L);
@@ -939,6 +944,7 @@ size_t Decomp1Step::carve_ws(float *base) {
     fpart = a.take(V * RO * 2 * S);                             // the words' shares of dS1_output / dS2_output
     HP = a.take((size_t)B * 2 * S);                               // the sequences' shares of dh0 / dhT
     carve_max(a);
+    if (crf) cs.carve(a, B, L, K, w->P != nullptr);               // (behind everything the plain step lays out)
     return a.off;
 }
 // Stage 1: the arguments
@@ -951,6 +957,8 @@ int Decomp1Step::validate() {
 int Decomp1Step::plan(int B_, int L_) {
     R = c->d.R; RO = c->d.RO;
     if (int rc = plan_bucketed(name, B_, L_, RO, ind1_train_lds_floats)) return rc;
+    if (crf)
+        if (int rc = BucketedCrf::plan_check(name, K, L)) return rc;
     need = carve_ws(nullptr);
     return FARNN_OK;
 }
@@ -971,6 +979,7 @@ int Decomp1Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *
     bp.dN = dN; bp.fpart = fpart; bp.L = L; bp.S = (int)S; bp.SP = f.SP; bp.RO = (int)RO; bp.CPR = f.CPR; bp.GW = f.GW;
     // max semiring: UF / DQ hold dM entries, not adjoint rows -- BPTT itself carries on into row 0 (onehot_max_bptt_carry_kernel)
     if (mx && (o->dh0 || o->dhT)) carry0 = HP;
+    if (crf) cs.fill(crf_trans, w->P, SC, DS, lengths, labels_, o->tags, c->err.dev, B, L, K, c->d.o_idx, c->d.threshold);
     return FARNN_OK;
 }
 // C[m][n] = sum_k A[m am + k ak] B[k bk + n bn] (+ add[n]); rows: the rows read as zero (decomp1_gemm_kernel)
@@ -1005,10 +1014,12 @@ int Decomp1Step::scores() {
         return launch(ind1_train_kernel<RPT(), MODE>, dim3((unsigned)V, ngrp), I1_THREADS, lds_sc, s, f);
     });
 }
-// Stage 8: score = br C_output^T (:206); the loss on the scores; d br = d score C_output
+// Stage 8: score = br C_output^T (:206); the loss on the scores (CRF: the negative log-likelihood of the emissions, a sum over
+// the sequences, :293); d br = d score C_output
 int Decomp1Step::loss() {
     int rc;
-    if ((rc = gemm(BR, RO, 1, w->C, 1, RO, SC, K, N0, K, RO)) || (rc = loss_on_scores())) return rc;
+    if ((rc = gemm(BR, RO, 1, w->C, 1, RO, SC, K, N0, K, RO)) ||
+        (rc = crf ? cs.run(SC, lgrid, dtrans, o->loss, s) : loss_on_scores())) return rc;
     return gemm(DS, K, 1, w->C, RO, 1, DBR, RO, N0, RO, K);
 }
 // Stage 12: dN[w] and the words' shares of dS1_output / dS2_output, one workgroup per word over all output ranks
@@ -1045,6 +1056,14 @@ extern "C" int farnn_decomp_ind1_train_step(farnn_decomp_ind1_train_ctx *c, cons
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *o, void *stream) {
     return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
+}
+extern "C" int farnn_decomp_ind1_crf_train_step(farnn_decomp_ind1_train_ctx *c, const farnn_decomp_ind1_train_weights *w,
+                                                const float *crf_trans, const int64_t *x, const int64_t *lengths,
+                                                const int64_t *labels, int32_t B, int32_t L, int64_t valid_tokens,
+                                                const farnn_decomp_ind1_train_outputs *o, float *dtrans, void *stream) {
+    if (!crf_trans || !dtrans) return fail(FARNN_EINVAL, "decomp_ind1_train_crf_step: CRF transitions / their gradient missing%s%s");
+    return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
+                                       [&](Decomp1Step &t) { t.crf = true; t.crf_trans = crf_trans; t.dtrans = dtrans; });
 }
 
 // ---- the optimizer step (farnn_optim_*; optim.hip.h) -------------------------------------------------------------------

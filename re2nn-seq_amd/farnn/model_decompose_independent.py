@@ -2,7 +2,8 @@
 (src_seq/farnn/model_decompose_independent.py:11-300): a rank-R language tensor plus a separate
 rank-R_O output tensor (C_output, S1_output, S2_output).  Same constructor arguments and state-dict
 keys as the reference; inference runs in the HIP library (farnn_decomp_ind1_create).
-Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step.
+Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step; with --use_crf 1
+(RE2NN_DECOMP_IND1_CRF_TRAIN=1 beside it): farnn_decomp_ind1_crf_train_step.
 """
 import os
 
@@ -115,6 +116,11 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
         """RE2NN_DECOMP_IND1_TRAIN=1: this model's training step (opt-in for its first release, as RE2NN_ONEHOT_IND1_TRAIN)"""
         return os.environ.get('RE2NN_DECOMP_IND1_TRAIN', '') == '1'
 
+    @staticmethod
+    def _decomp_ind1_crf_train_enabled():
+        """RE2NN_DECOMP_IND1_CRF_TRAIN=1: the step under --use_crf 1 (opt-in for its first release)"""
+        return os.environ.get('RE2NN_DECOMP_IND1_CRF_TRAIN', '') == '1'
+
     def _check_trainable(self, re_tags=None):
         """The cases the HIP training step does not cover, refused before any device work."""
         if not self._decomp_ind1_train_enabled():     # before self.args is touched: the refusal needs the type only
@@ -126,7 +132,7 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             why = 'the gated recurrences (--farnn {})'.format(a.farnn)
         elif a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             why = 'the max semiring (--train_mode {})'.format(a.train_mode)
-        elif a.use_crf:
+        elif a.use_crf and not self._decomp_ind1_crf_train_enabled():
             why = 'the CRF (--use_crf 1)'
         elif a.local_loss_func != 'CE1':
             why = 'a loss other than CE1 (--local_loss_func {})'.format(a.local_loss_func)
@@ -154,6 +160,8 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             t = src[k].detach().to(dev).float().clone()
             t.requires_grad_(True if flag is None else bool(getattr(self.args, flag, 0)))
             self._tp[k] = t
+        if self.use_crf:              # an nn.Parameter of the reference's CRF, always trainable (baselines/crf.py:46)
+            self._tp['crf.transitions'] = self.crf_transitions.detach().to(dev).float().clone().requires_grad_(True)
         self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
             if self.args.use_priority else None
         S, R = self._tp['S1'].shape
@@ -179,7 +187,7 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
         lab = label[:, :Lmax]
         loss, tags = decomp_ind1_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
                                             tp['C_output'], tp['S1_output'], tp['S2_output'], tp['h0'], tp['hT'], self._tpP,
-                                            x, lengths, lab, valid_tokens=ntok)
+                                            x, lengths, lab, valid_tokens=ntok, crf_trans=tp.get('crf.transitions'))
         self._dirty = True
         pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
         true = self._flatten(label, lengths).to(input.device)

@@ -24,7 +24,8 @@ only: one library call.
 
 The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.py:148-300): the word table as
 for f3 through torch's autograd, and one library call (farnn_decomp_ind1_train_step) for the loss, the tags and the gradients of
-Vgen, S1, S2, wildcard_mat, C_output, S1_output, S2_output, h0 and hT.
+Vgen, S1, S2, wildcard_mat, C_output, S1_output, S2_output, h0 and hT.  Under --use_crf 1 (crf_trans given) the call is
+farnn_decomp_ind1_crf_train_step: the CRF's negative log-likelihood, the Viterbi tags and the transitions' gradient as well.
 """
 import torch
 
@@ -195,22 +196,29 @@ _D1_OPTIONAL = ('W', 'C', 'S1o', 'S2o', 'h0', 'hT')       # gradients the librar
 
 class _DecompInd1TrainStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT):
+    def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, trans):
         dev, ntok, x, lengths, labels, loss, tags = _step_inputs(S1, ntok, x, lengths, labels)
         B, L = x.shape
         ts = dict(zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT)))
         ws = {n: _f32(t) for n, t in ts.items()}
-        Pc = _f32(P)
+        Pc, tr = _f32(P), _f32(trans)
         grads = {n: torch.empty_like(ws[n]) for n in _D1_NAMES if n not in _D1_OPTIONAL or ts[n].requires_grad}
         weights = {n: t.data_ptr() for n, t in ws.items()}
         weights['P'] = None if Pc is None else Pc.data_ptr()
         outputs = {'d' + n: (grads[n].data_ptr() if n in grads else None) for n in _D1_NAMES}
         outputs['loss'] = loss.data_ptr()
         outputs['tags'] = tags.data_ptr()
-        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                torch.cuda.current_stream(dev).cuda_stream)
-        ctx.have = tuple(n in grads for n in _D1_NAMES)
-        ctx.save_for_backward(*[grads[n] for n in _D1_NAMES if n in grads])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if tr is None:
+            tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs, stream)
+        else:
+            if tuple(tr.shape) != (Cout.shape[0],) * 2:
+                raise ValueError('CRF transitions must be [C, C] = {}, not {}'.format((Cout.shape[0],) * 2, tuple(tr.shape)))
+            grads['trans'] = torch.empty_like(tr)
+            tc.step_crf(weights, tr.data_ptr(), x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
+                        grads['trans'].data_ptr(), stream)
+        ctx.have = tuple(n in grads for n in _D1_NAMES + ('trans',))
+        ctx.save_for_backward(*[grads[n] for n in _D1_NAMES + ('trans',) if n in grads])
         ctx.mark_non_differentiable(tags)
         return loss.reshape(()), tags
 
@@ -220,9 +228,12 @@ class _DecompInd1TrainStep(torch.autograd.Function):
         return (None,) * 6 + tuple(next(saved) * gloss if h else None for h in ctx.have)
 
 
-def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, lengths, labels, valid_tokens=None):
+def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, lengths, labels, valid_tokens=None,
+                           crf_trans=None):
     """The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.py:219-300): returns
     (loss scalar tensor with grad, tags int32 [B,L] with -1 at pads).  Vgen [V,R] (its gradient flows on through torch's
     autograd to V_embed, embed_r_generalized, embedding.weight and beta_vec), S1 and S2 always get a gradient; wildcard_mat W,
-    C_output, S1_output, S2_output, h0 and hT get one when they require it and None otherwise.  P is read only."""
-    return _DecompInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT)
+    C_output, S1_output, S2_output, h0 and hT get one when they require it and None otherwise.  P is read only.
+    crf_trans [C,C] (C counts START and STOP): the loss is the CRF's negative log-likelihood, a sum over the sequences, the
+    tags are the Viterbi path, and crf_trans gets a gradient (farnn_decomp_ind1_crf_train_step)."""
+    return _DecompInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, crf_trans)

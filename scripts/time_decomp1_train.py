@@ -7,7 +7,15 @@ lengths, rotating through four batches of the same lengths.  Prints one JSON lin
   stage_us            (--stages 1) torch.profiler's device time per kernel name over the timed steps, divided by the steps,
                       largest first, and `dominant` the first of them; a run of its own, after the event-timed steps
 
-    python scripts/time_decomp1_train.py [--steps 10] [--warmup 2] [--stages 1]
+  result_sha          sha256 over the loss and every gradient of the last timed step (bytes): two builds whose plain step
+                      shares every kernel must print the same one
+
+    python scripts/time_decomp1_train.py [--steps 10] [--warmup 2] [--stages 1] [--use_crf 1] [--parent_lib 1]
+
+--use_crf 1: farnn_decomp_ind1_crf_train_step with the same 73 labels (the score width becomes 75: START and STOP; the
+transitions are the reference's initial ones plus seeded noise in (-0.5, 0.5) where they are not -10000).
+--parent_lib 1: the library named by FARNN_LIB is a build of an earlier commit without the CRF entry point (its binding is
+dropped before the library is loaded); for the plain step only.
 
 The line carries no rate: none was measured.  Each GPU step of a job script runs it under its own time limit
 (timeout -k 10 ...)."""
@@ -29,9 +37,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--train_mode', choices=('sum', 'max'), default='sum')       # the semiring of the chains
     ap.add_argument('--stages', type=int, default=1)
+    ap.add_argument('--use_crf', type=int, default=0)
+    ap.add_argument('--parent_lib', type=int, default=0)
     a = ap.parse_args()
     import torch
     from re2nn_seq_amd import _lib, synth
+    if a.parent_lib:
+        assert not a.use_crf, 'an earlier build has no CRF step'
+        _lib.SIGNATURES.pop('farnn_decomp_ind1_crf_train_step')
     from re2nn_seq_amd.farnn.train_step import decomp_ind1_train_step
     V, S, C, R, RO, B, L = 11000, 104, 73, 50, 70, 256, 64
     rng = np.random.RandomState(1234)
@@ -45,6 +58,13 @@ def main():
         xk[np.arange(L)[None, :] >= lengths[:, None]] = V - 1
         xs.append(xk)
     labels = [rng.randint(0, C, size=(B, L)).astype(np.int64) for _ in xs]
+    trans = None
+    if a.use_crf:                                 # (drawn after everything the plain step draws: its inputs stay the same)
+        C += 2
+        trans = np.zeros((C, C), np.float32)
+        trans[:, C - 2] = -10000.0
+        trans[C - 1, :] = -10000.0
+        trans += np.where(trans > -5000.0, np.random.RandomState(99).uniform(-0.5, 0.5, size=(C, C)), 0.0).astype(np.float32)
     ntok = int(lengths.sum())
     dev = torch.device('cuda', 0)
     d = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev).requires_grad_(True)      # noqa: E731
@@ -54,11 +74,14 @@ def main():
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
     tc = _lib.Decomp1TrainContext(V, S, R, RO, C, nl='tanh', device=0, semiring=a.train_mode)
+    td = None if trans is None else d(trans)
 
     def one(i):
         for t in ws:
             t.grad = None
-        loss, _ = decomp_ind1_train_step(tc, *ws, None, xd[i % 4], ld, labd[i % 4], valid_tokens=ntok)
+        if td is not None:
+            td.grad = None
+        loss, _ = decomp_ind1_train_step(tc, *ws, None, xd[i % 4], ld, labd[i % 4], valid_tokens=ntok, crf_trans=td)
         loss.backward()
         return loss
 
@@ -73,6 +96,9 @@ def main():
         ms, n = tc.time()
         per.append(1e3 * ms / max(n, 1))
     tc.set_profiling(0)
+    sha = hashlib.sha256(loss.detach().cpu().numpy().tobytes())
+    for t in ws + ([td] if td is not None else []):
+        sha.update(t.grad.cpu().numpy().tobytes())
     words = [int(len(np.unique(v[np.arange(L)[None, :] < lengths[:, None]]))) for v in xs]
     # the stamp of what was measured: sha256 over the library's sources (csrc/*.hip, csrc/*.h, include/farnn.h), names in order
     h = hashlib.sha256()
@@ -83,7 +109,7 @@ def main():
             h.update(os.path.basename(path).encode() + b'\0' + fh.read())
     tree = h.hexdigest()[:16]
     out = {'shape': {'V': V, 'S': S, 'C': C, 'R': R, 'RO': RO, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok, 'train_mode': a.train_mode,
-           'steps': a.steps, 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
+           'steps': a.steps, 'use_crf': a.use_crf, 'result_sha': sha.hexdigest()[:16], 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
            'lib_us_max': float(max(per)), 'distinct_words': words, 'loss': float(loss.detach()), 'tree': tree}
     if a.stages:
         from torch.profiler import ProfilerActivity, profile
