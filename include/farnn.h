@@ -430,6 +430,18 @@ int  farnn_decomp_ifst_teacher_train_step(farnn_train_ctx *ctx, const farnn_trai
                                           const int64_t *lengths, const int64_t *labels, const float *re_scores,
                                           const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
                                           const farnn_train_outputs *out, void *stream);
+/* The teacher step on a context set to FARNN_SEMIRING_MAX (--train_mode max --marryup_type kd | pr; main.py:163,
+ * model_decompose_single.py:159-166 for the recurrences, :291-300 for the loss).  Same arguments, same loss and same refusals as
+ * above, with one exchanged: FARNN_EINVAL on a context in the SUM semiring (the entry above is the one for it).  Only the two
+ * recurrences are max-times (utils._maxmul: ONE source state per target state, the first maximal one); the scores, the KL term
+ * and the original loss are sum-times, as the reference sends nothing else through semiring_func.  Both max-times chains of
+ * every sequence run L steps through the raw pad tokens, every one of the B L positions is bucketed by word, and a word that
+ * occurs at pad positions only gets a block Tr_w and a non-zero row of dVgen (a zero one with pi = 1).  S <= 192 as
+ * farnn_train_set_semiring demands. */
+int  farnn_decomp_ifst_teacher_max_train_step(farnn_train_ctx *ctx, const farnn_train_weights *w, const int64_t *x,
+                                              const int64_t *lengths, const int64_t *labels, const float *re_scores,
+                                              const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
+                                              const farnn_train_outputs *out, void *stream);
 /* accumulated HIP-event time of the step's launches since the last call (ms) and the number of steps timed;
  * profiling is enabled with farnn_train_set_profiling(ctx, 1) */
 int  farnn_train_set_profiling(farnn_train_ctx *ctx, int32_t enable);

@@ -234,6 +234,9 @@ SIGNATURES = {
     'farnn_decomp_ifst_teacher_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.POINTER(Teacher), C.c_int32, C.c_int32,
                                                        C.c_int64, C.POINTER(TrainOutputs), C.c_void_p]),
+    'farnn_decomp_ifst_teacher_max_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.POINTER(Teacher), C.c_int32, C.c_int32,
+                                                           C.c_int64, C.POINTER(TrainOutputs), C.c_void_p]),
     'farnn_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -618,12 +621,14 @@ class _TrainContextBase:
         out = C.c_void_p()
         check(getattr(load(), self._create)(C.byref(dims), int(device), C.byref(out)), self._create)
         self._raw = out
+        self.semiring = 'sum'
         if semiring != 'sum':
             self.set_semiring(semiring)
 
     def set_semiring(self, semiring):
         """'sum' or 'max' (the reference's --train_mode) for the following steps."""
         check(getattr(load(), self._set_semiring)(self._raw, SEMIRING[semiring]), self._set_semiring)
+        self.semiring = semiring
 
     def close(self):
         if self._raw:
@@ -660,20 +665,29 @@ class TrainContext(_TrainContextBase):
     _weights, _outputs = TrainWeights, TrainOutputs
 
     def __init__(self, V, S, R, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0,
-                 sigmoid_exponent=5.0, semiring='sum'):
+                 sigmoid_exponent=5.0, semiring='sum', teacher_max=False):
         self._open(TrainDims(int(V), int(S), int(R), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
                              float(sigmoid_exponent), int(bool(use_crf))), device, semiring)
         self.dims = (int(V), int(S), int(R), int(K))
+        # the KD / PR teacher in the max semiring is opt-in for its first release: without it teacher_step() on a max context
+        # goes to the sum entry as before, and that entry refuses the context
+        self.teacher_max = bool(teacher_max)
 
-    def teacher_step(self, weights, x_ptr, len_ptr, labels_ptr, re_ptr, mode, c1, pi, B, L, valid_tokens, outputs, stream=None):
-        """step() with the KD / PR teacher (farnn_decomp_ifst_teacher_train_step): re_ptr is the device pointer of the float
-        [B][L][K] teacher scores, mode 'kd' or 'pr' (or the raw FARNN_TEACHER_* value), pi the weight of the original loss."""
+    def teacher_step(self, weights, x_ptr, len_ptr, labels_ptr, re_ptr, mode, c1, pi, B, L, valid_tokens, outputs, stream=None,
+                     max_entry=None):
+        """step() with the KD / PR teacher: re_ptr is the device pointer of the float [B][L][K] teacher scores, mode 'kd' or
+        'pr' (or the raw FARNN_TEACHER_* value), pi the weight of the original loss.  The entry is the context's semiring's:
+        farnn_decomp_ifst_teacher_train_step (sum) or, on a context opened with teacher_max=True,
+        farnn_decomp_ifst_teacher_max_train_step (max).  max_entry = True / False names the entry instead (each refuses a
+        context in the other semiring)."""
         w = self._weights(**{k: (weights.get(k) or None) for k, _ in self._weights._fields_})
         o = self._outputs(**{k: outputs.get(k) for k, _ in self._outputs._fields_})
         t = Teacher(int(TEACHER.get(mode, mode)), float(c1), float(pi))
-        check(load().farnn_decomp_ifst_teacher_train_step(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, re_ptr, C.byref(t),
-                                                          int(B), int(L), int(valid_tokens), C.byref(o), stream),
-              'farnn_decomp_ifst_teacher_train_step')
+        if max_entry is None:
+            max_entry = self.semiring == 'max' and self.teacher_max
+        entry = 'farnn_decomp_ifst_teacher_max_train_step' if max_entry else 'farnn_decomp_ifst_teacher_train_step'
+        check(getattr(load(), entry)(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, re_ptr, C.byref(t),
+                                     int(B), int(L), int(valid_tokens), C.byref(o), stream), entry)
 
 
 class OnehotTrainContext(_TrainContextBase):

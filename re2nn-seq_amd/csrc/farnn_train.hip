@@ -252,6 +252,7 @@ struct TrainStep : TrainPlan {
     TrainParams p; MaxWs m; PrepJobs prep; AtbJobs gate_jobs, grad_jobs;
     float *dGVT;                        // dGV^T ([S][V]) as the A operand of dVgen += dGV Wrs^T
     const float *re; const farnn_teacher *tch;      // the teacher's scores [B][L][K] and parameters; null: the plain step
+    bool tch_max;                       // the entry is farnn_decomp_ifst_teacher_max_train_step: the context must be in the max semiring
     int validate() { return train_validate(c, w, o); }
     int plan(int B_, int L_) {
         if (int rc = teacher_check()) return rc;
@@ -404,7 +405,8 @@ int TrainStep::forward() {
 // Stage 5, max semiring: the positions bucketed by word (onehot_train.hip.h), the distinct words' slots, their blocks, both chains
 int TrainStep::max_forward() {
     int rc;
-    if ((rc = clear_bucket_counts(m.bk, V, N0, s)) || (rc = launch_bucketing(p.x, p.len, B, L, (int)V, m.bk, nullptr, s))) return rc;
+    // (with a teacher every position is bucketed: the chains run through the pad tokens, whose words need their blocks too)
+    if ((rc = clear_bucket_counts(m.bk, V, N0, s)) || (rc = launch_bucketing(p.x, p.len, B, L, (int)V, m.bk, nullptr, s, teacher))) return rc;
     tmax_slots_kernel<<<1, 1024, 0, s>>>(m.bk.wcount, (int)V, m.wslot, m.wlist, m.nwords);
     const unsigned nt = (unsigned)((S + 31) / 32);
     tmax_premix_kernel<<<dim3((unsigned)nwmax, nt * nt), 256, 0, s>>>(w->Vgen, w->S1, w->S2, w->W, m.wlist, m.nwords, m.M, m.MT, (int)S, (int)R);
@@ -430,8 +432,10 @@ int TrainStep::teacher_check() const {
         return fail(FARNN_EINVAL, "teacher_train_step: mode must be FARNN_TEACHER_KD or FARNN_TEACHER_PR%s%s");
     if (!(tch->c1 >= 1.0f) || !std::isfinite(tch->c1)) return fail(FARNN_EINVAL, "teacher_train_step: c1 must be at least 1 (main.py asserts it)%s%s");
     if (!(tch->pi >= 0.0f && tch->pi <= 1.0f)) return fail(FARNN_EINVAL, "teacher_train_step: pi must lie in [0, 1]%s%s");
-    if (c->semiring == FARNN_SEMIRING_MAX)
+    if (!tch_max && c->semiring == FARNN_SEMIRING_MAX)
         return fail(FARNN_EINVAL, "teacher_train_step: the max semiring has no KD / PR teacher (its kernels walk the valid positions only)%s%s");
+    if (tch_max && c->semiring != FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "teacher_max_train_step: the context is in the sum semiring (farnn_train_set_semiring, or farnn_decomp_ifst_teacher_train_step)%s%s");
     return FARNN_OK;
 }
 // Stage 6 with a teacher (train_teacher.hip.h): the same split around the CRF kernel, every position walked, then the loss
@@ -493,6 +497,18 @@ extern "C" int farnn_decomp_ifst_teacher_train_step(farnn_train_ctx *c, const fa
     if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_train_step: null teacher argument%s%s");
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
                                      [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; });
+}
+
+// The same step on a context in the max semiring (--train_mode max --marryup_type kd | pr): the tmax_* chains run L steps for
+// every sequence, every position is bucketed, and the loss kernels are the sum step's -- only the recurrences are max-times.
+extern "C" int farnn_decomp_ifst_teacher_max_train_step(farnn_train_ctx *c, const farnn_train_weights *w, const int64_t *x,
+                                                        const int64_t *lengths, const int64_t *labels, const float *re_scores,
+                                                        const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
+                                                        const farnn_train_outputs *o, void *stream) {
+    TunScope tun_scope(c ? &c->tun : nullptr);
+    if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_max_train_step: null teacher argument%s%s");
+    return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
+                                     [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; t.tch_max = true; });
 }
 
 // ---- training step of the onehot i-FST (FARNN_S_O_I_S; onehot_train.hip.h) -------------------------------

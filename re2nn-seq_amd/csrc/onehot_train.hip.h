@@ -286,6 +286,33 @@ onehot_bucket_fill_kernel(const int64_t *__restrict__ x, const int64_t *__restri
     list[off[(size_t)w * nch + blockIdx.x] + rank] = (int)pos;
 }
 
+// The same two passes over EVERY one of the B L positions, the pads included: the max-semiring step of the decomposed i-FST
+// with a KD / PR teacher runs its chains through the pad tokens x[b, len:] (train_max.hip.h), so a word that occurs only there
+// needs its block and its bucket too.  An id outside 0..V-1 is flagged at a pad as at a valid position (the reference's
+// V_embed[inp] indexes the pads as well).  A second pair, not a flag: the pair above is launched by every other step and its
+// code objects stay what they were.
+__global__ void __launch_bounds__(OT_CH)
+onehot_bucket_count_all_kernel(const int64_t *__restrict__ x, int B, int L, int V, int nch, int *cnt, int *err) {
+    const long long pos = (long long)blockIdx.x * OT_CH + threadIdx.x;
+    if (pos >= (long long)B * L) return;
+    const long long v = x[pos];
+    if ((v < 0 || v >= V) && err) atomicOr(err, 2);
+    atomicAdd(&cnt[(size_t)oh_token(x, V, pos) * nch + blockIdx.x], 1);
+}
+__global__ void __launch_bounds__(OT_CH)
+onehot_bucket_fill_all_kernel(const int64_t *__restrict__ x, int B, int L, int V, int nch, const int *__restrict__ off,
+                              int *list) {
+    __shared__ int wd[OT_CH];
+    const long long pos = (long long)blockIdx.x * OT_CH + threadIdx.x;
+    const int w = pos < (long long)B * L ? oh_token(x, V, pos) : -1;
+    wd[threadIdx.x] = w;
+    __syncthreads();
+    if (w < 0) return;
+    int rank = 0;
+    for (int q = 0; q < (int)threadIdx.x; q++) rank += wd[q] == w;
+    list[off[(size_t)w * nch + blockIdx.x] + rank] = (int)pos;
+}
+
 // ---- dT: one workgroup per run of up to OT_G positions of one word --------------------------------------------
 // The run's rows are staged in LDS -- per position: f_{t-1} = A[i] and dp_t o = UF[i+1] (forward, t = i+1), dq_t = DQ[len-i]
 // and b_{t-1} o = Bk[len-i-1] o (backward, t = len-i, i >= 1) -- then thread (ty, tx) of 16 x 16 adds the rank-one

@@ -173,14 +173,17 @@ inline int clear_bucket_counts(const Buckets &b, size_t V, size_t N0, hipStream_
     return FARNN_OK;
 }
 // count / scan (the counts in LDS when they fit) / fill; b.cnt is zero before.  err: the step's error word (bit 1: a word
-// outside 0..V-1) or null
-inline int launch_bucketing(const int64_t *x, const int64_t *len, int B, int L, int V, const Buckets &b, int *err, hipStream_t s) {
+// outside 0..V-1) or null.  all: every one of the B L positions is counted and listed, the pads included (the teacher's max step)
+inline int launch_bucketing(const int64_t *x, const int64_t *len, int B, int L, int V, const Buckets &b, int *err, hipStream_t s,
+                            bool all = false) {
     const int nch = bucket_chunks((size_t)B * L);
     const size_t lds_s = (size_t)V * nch * sizeof(int) <= 144 * 1024 ? (size_t)V * nch * sizeof(int) : 0;
-    onehot_bucket_count_kernel<<<nch, OT_CH, 0, s>>>(x, len, B, L, V, nch, b.cnt, err);
+    if (all) onehot_bucket_count_all_kernel<<<nch, OT_CH, 0, s>>>(x, B, L, V, nch, b.cnt, err);
+    else onehot_bucket_count_kernel<<<nch, OT_CH, 0, s>>>(x, len, B, L, V, nch, b.cnt, err);
     if (int rc = launch(onehot_bucket_scan_kernel, 1, 1024, lds_s, s, b.cnt, V, nch, b.wstart, b.wcount, b.itoff, b.psoff,
                         lds_s ? V * nch : 0)) return rc;
-    onehot_bucket_fill_kernel<<<nch, OT_CH, 0, s>>>(x, len, B, L, V, nch, b.cnt, b.list);
+    if (all) onehot_bucket_fill_all_kernel<<<nch, OT_CH, 0, s>>>(x, B, L, V, nch, b.cnt, b.list);
+    else onehot_bucket_fill_kernel<<<nch, OT_CH, 0, s>>>(x, len, B, L, V, nch, b.cnt, b.list);
     return FARNN_OK;
 }
 

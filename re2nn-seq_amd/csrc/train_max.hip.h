@@ -105,6 +105,10 @@ tmax_premix_kernel(const float *__restrict__ Vgen, const float *__restrict__ S1,
 // grid (B, 2): blockIdx.y = 0 forward, 1 backward chain.  Thread s: the gate pre-activations of state s (Wss read
 // through L2 along rows), then n[s] = max_j in[j] G[j][s] with G = M (forward) or MT (backward) of the step's word.
 // Writes A / Bk, PRE and the gate stash (ZG, RG, CD) as train_forward_kernel does, plus IN and IDX.
+// With a KD / PR teacher (p.full_chain, train_teacher.hip.h) both chains of every sequence, the empty ones too, run L steps:
+// the forward chain over x[b, t-1], the backward chain over its len reversed tokens and then the raw pad tokens x[b, len:], and
+// every row 1..L of the stashes is written.  The back-propagation then starts at row L; the teacher's loss kernel has left
+// the adjoint of a pad position i in row i + 1 of both GA and GB.
 // LDS: in[2][TM_MAX_S] (by step parity), hv[TM_MAX_S] raw state, toks[L]
 __global__ void __launch_bounds__(TM_THREADS)
 tmax_forward_kernel(const TrainParams p, const TrainMaxParams m) {
@@ -112,9 +116,11 @@ tmax_forward_kernel(const TrainParams p, const TrainMaxParams m) {
     __shared__ float hv[TM_MAX_S];
     extern __shared__ int toks[];                              // [L]: the token of step t at t - 1
     const int b = blockIdx.x, dir = blockIdx.y, s = threadIdx.x, S = p.S, L = p.L;
-    const int len = clamp_len(p.len[b], L);
+    // len: the steps of the chain -- the valid length, or L with a teacher (full_chain), whose chains go on through the pad
+    // tokens; vlen: the valid length, which only decides the order of the tokens (train_forward_kernel, train.hip.h)
+    const int vlen = clamp_len(p.len[b], L), len = p.full_chain ? L : vlen;
     for (int i = s; i < len; i += blockDim.x)
-        toks[i] = oh_token(p.x, p.V, (long long)b * L + (dir == 0 ? i : len - 1 - i));
+        toks[i] = oh_token(p.x, p.V, (long long)b * L + ((dir == 0 || i >= vlen) ? i : vlen - 1 - i));
     const bool own = s < S;
     const size_t row0 = (size_t)b * (L + 1), SS = (size_t)S * S;
     float *stash = dir == 0 ? p.A : p.Bk;
@@ -206,9 +212,11 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
     __shared__ int jj[TM_MAX_S];
     extern __shared__ int toks[];
     const int b = blockIdx.x, dir = blockIdx.y, s = threadIdx.x, S = p.S, L = p.L;
-    const int len = clamp_len(p.len[b], L);
+    // len: the steps of the chain -- the valid length, or L with a teacher (full_chain), whose chains go on through the pad
+    // tokens; vlen: the valid length, which only decides the order of the tokens (train_forward_kernel, train.hip.h)
+    const int vlen = clamp_len(p.len[b], L), len = p.full_chain ? L : vlen;
     for (int i = s; i < len; i += blockDim.x)
-        toks[i] = oh_token(p.x, p.V, (long long)b * L + (dir == 0 ? i : len - 1 - i));
+        toks[i] = oh_token(p.x, p.V, (long long)b * L + ((dir == 0 || i >= vlen) ? i : vlen - 1 - i));
     const bool own = s < S;
     const size_t row0 = (size_t)b * (L + 1), SS = (size_t)S * S;
     const float *stash = dir == 0 ? p.A : p.Bk, *Gadj = dir == 0 ? p.GA : p.GB;
@@ -294,8 +302,9 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
 
 // ---- dM_w: one workgroup per distinct word, [S][S] in LDS ------------------------------------------------------
 // The word's positions in bucket order (flat position order); first every forward entry (thread s owns column s: entry
-// (j*, s) of step i + 1), then every backward entry (thread s owns row s: entry (s, j*) of step len - i).  Each element
-// is added in a fixed order by one thread: two steps on the same inputs give the same bits.
+// (j*, s) of step i + 1), then every backward entry (thread s owns row s: entry (s, j*) of step len - i; of step i + 1 at a
+// pad position i >= len, which only the teacher's bucketing of every position lists).  Each element is added in a fixed
+// order by one thread: two steps on the same inputs give the same bits.
 __global__ void __launch_bounds__(TM_THREADS)
 tmax_dM_kernel(const TrainParams p, const TrainMaxParams m, const int *__restrict__ list, const int *__restrict__ wstart,
                const int *__restrict__ wcount, float *dM) {
@@ -318,7 +327,7 @@ tmax_dM_kernel(const TrainParams p, const TrainMaxParams m, const int *__restric
         for (int q = 0; q < n; q++) {
             const int pos = list[st + q], bb = pos / L, i = pos - bb * L;
             const int len = clamp_len(p.len[bb], L);
-            const size_t row = ((size_t)bb * (L + 1) + (len - i)) * S + s;
+            const size_t row = ((size_t)bb * (L + 1) + (i < len ? len - i : i + 1)) * S + s;      // (a pad: full_chain only)
             tile[s * S + m.IDXb[row]] += m.GMb[row];
         }
     }

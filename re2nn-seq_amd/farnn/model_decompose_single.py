@@ -184,7 +184,7 @@ class FARNN_S_D_W_I_S(NativeTagger):
 
     def _check_trainable(self, re_tags):
         """Raises before any device work.  The KD / PR teacher terms (--marryup_type kd | pr) are opt-in
-        for their first release: RE2NN_DECOMP_TEACHER_TRAIN=1."""
+        for their first release: RE2NN_DECOMP_TEACHER_TRAIN=1, and under --train_mode max RE2NN_DECOMP_TEACHER_MAX_TRAIN=1 beside it."""
         a = self.args
         marryup = getattr(a, 'marryup_type', 'none')
         teacher = marryup in ('kd', 'pr')
@@ -198,7 +198,7 @@ class FARNN_S_D_W_I_S(NativeTagger):
             raise ValueError('--marryup_type {} needs the RE teacher\'s scores: forward_local(..., re_tags=...)'.format(marryup))
         if re_tags is not None and not teacher:
             raise ValueError('re_tags were given but --marryup_type is {!r}: the teacher term would be dropped silently'.format(marryup))
-        if teacher and a.train_mode == 'max':
+        if teacher and a.train_mode == 'max' and os.environ.get('RE2NN_DECOMP_TEACHER_MAX_TRAIN', '') != '1':
             raise NotImplementedError('the KD / PR teacher terms are built for the sum semiring only; --train_mode max walks the '
                                       'valid positions only (DESIGN.md, row f3)')
         return teacher
@@ -241,7 +241,8 @@ class FARNN_S_D_W_I_S(NativeTagger):
                                      nl=self.args.update_nonlinear, threshold=self.args.threshold, o_idx=self.o_idx,
                                      device=self.device_index, use_crf=self.use_crf, farnn=int(self.args.farnn),
                                      sigmoid_exponent=float(self.args.sigmoid_exponent),
-                                     semiring=self.args.train_mode)
+                                     semiring=self.args.train_mode,
+                                     teacher_max=os.environ.get('RE2NN_DECOMP_TEACHER_MAX_TRAIN', '') == '1')
         self._dirty = False
         return self
 

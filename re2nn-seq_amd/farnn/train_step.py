@@ -11,7 +11,8 @@ computes loss and all gradients in its forward call (the stash lives in its work
 only hands them out, scaled by the incoming gradient.
 
 Scope: farnn = 0/1/2, sum or max semiring (TrainContext(semiring=...)), CE1 loss or (use_crf) the CRF
-negative log-likelihood; in the sum semiring also with the KD / PR teacher term (teacher=...).
+negative log-likelihood; in either semiring also with the KD / PR teacher term (teacher=...; on a max context through
+farnn_decomp_ifst_teacher_max_train_step, TrainContext(teacher_max=True)).
 
 The onehot i-FST (FARNN_S_O_I_S, model_onehot.py:351-428 + train_onehot.py:156-206) trains only
 language_tensor: one library call computes the loss, the tags and d loss / d language_tensor.
@@ -113,7 +114,7 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
     (farnn = 1) followed by Wss2, Wrs2, bs2 (farnn = 2), in that order.  valid_tokens: sum of the clamped lengths if
     the caller already has it (device-resident lengths would otherwise cost a synchronising read per step).
     teacher: None, or (re_scores [B,L,K] with the zero columns appended, 'kd' | 'pr', c1, pi) for
-    loss = pi * original + (1 - pi) * KL (farnn_decomp_ifst_teacher_train_step, include/farnn.h); the teacher scores get no
+    loss = pi * original + (1 - pi) * KL (farnn_decomp_ifst_teacher_train_step / _teacher_max_train_step, include/farnn.h); the teacher scores get no
     gradient."""
     return _DecompIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, teacher, P, Vgen, S1, S2, W, Cmat, h0, hT, crf_trans,
                                       *gates)

@@ -7,8 +7,9 @@ under CE1.  The epoch loop (:155-220) runs on the HIP training step (csrc/train.
 train_onehot.train_epochs) for the decomposed i-FST (``--independent 2``) with farnn 0/1/2, with or without the CRF,
 CE + CRF NLL losses, and, opt-in (RE2NN_DECOMP_IND1_TRAIN=1, csrc/decomp1_train.hip.h), for ``--independent 1``
 with farnn 0 and the CE1 loss.  The KD / PR teacher terms (``--marryup_type kd | pr``, :177-190: the loop hands ``batch['re']`` to
-forward_local) train the i-FST in the sum semiring, opt-in (RE2NN_DECOMP_TEACHER_TRAIN=1, csrc/train_teacher.hip.h, row f3); for
-``--independent 1`` and the max semiring they, and ``--independent 0``, are evaluated with --epoch 0."""
+forward_local) train the i-FST, opt-in (RE2NN_DECOMP_TEACHER_TRAIN=1, csrc/train_teacher.hip.h, row f3; under --train_mode max
+RE2NN_DECOMP_TEACHER_MAX_TRAIN=1 beside it); for
+``--independent 1`` they, and ``--independent 0``, are evaluated with --epoch 0."""
 from .farnn.model_decompose import FARNN_S_D_W
 from .farnn.model_decompose_independent import FARNN_S_D_W_I
 from .farnn.model_decompose_single import FARNN_S_D_W_I_S

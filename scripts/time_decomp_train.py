@@ -13,6 +13,13 @@ step on a full-length batch (the teacher's chains run B L steps instead of sum(l
 step (farnn_decomp_ifst_teacher_train_step) on the ragged batch, and prints their medians and spreads, the ratios and the
 hash of the sources the library was built from.
 
+--teacher-max kd|pr does the same for the teacher step in the max semiring (farnn_decomp_ifst_teacher_max_train_step): the
+plain sum and plain max steps on the ragged batch, the plain max step on a full-length batch, and the teacher-max step on the
+ragged and on the full-length batch; every leg also reports a hash of the tags of its first step (fresh weights, fixed inputs).
+--plain-only times the two plain ragged legs alone: with FARNN_LIB naming a library built from another commit (which may lack
+the newer entry points) it is the other side of an A/B.  A job script alternates the two and keeps every printed line;
+--merge FILE [FILE ...] reads such lines back and writes the medians and spreads per library as one JSON document.
+
 Each GPU step of a job script runs it under its own time limit (timeout -k 10 ...)."""
 import argparse
 import json
@@ -25,7 +32,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def older_library_ok():
+    """FARNN_LIB may name a library built from an earlier commit: the entry points it lacks are left unbound (its legs never
+    call them)"""
+    import ctypes
+    import torch  # noqa: F401  (one HIP runtime per process: the library is loaded after torch)
+    from re2nn_seq_amd import _lib
+    if os.environ.get('FARNN_LIB'):
+        lib = ctypes.CDLL(_lib.LIB_PATH)
+        for name in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:
+            del _lib.SIGNATURES[name]
+
+
 def run(a, semiring, teacher=None, full=False):
+    import hashlib
     import torch
     from re2nn_seq_amd import _lib, synth
     from re2nn_seq_amd.farnn.train_step import decomp_ifst_train_step
@@ -55,7 +75,7 @@ def run(a, semiring, teacher=None, full=False):
     labels = brng.randint(0, K - (2 if a.crf else 0), size=(B, L)).astype(np.int64)
     xd, ld, lab = torch.from_numpy(x).to(dev), torch.from_numpy(lengths).to(dev), torch.from_numpy(labels).to(dev)
     tc = _lib.TrainContext(V, S, R, K, nl='tanh', threshold=0.5, o_idx=0, use_crf=a.crf, farnn=a.farnn, sigmoid_exponent=5.0,
-                           semiring=semiring)
+                           semiring=semiring, **(dict(teacher_max=True) if teacher and semiring == 'max' else {}))
     ntok = int(lengths.sum())
     opt = torch.optim.Adam(list(p.values()), lr=1e-4)
     tch = None
@@ -65,10 +85,14 @@ def run(a, semiring, teacher=None, full=False):
         re[..., K - (3 if a.crf else 1):] = 0.0
         tch = (torch.from_numpy(re).to(dev), teacher, 2.0, 0.5)
 
+    first_tags = []
+
     def one():
         opt.zero_grad(set_to_none=True)
-        loss, _ = decomp_ifst_train_step(tc, p['Vgen'], p['S1'], p['S2'], p['W'], p['C'], p['h0'], p['hT'], None, xd, ld, lab,
+        loss, tags = decomp_ifst_train_step(tc, p['Vgen'], p['S1'], p['S2'], p['W'], p['C'], p['h0'], p['hT'], None, xd, ld, lab,
                                          crf_trans=p.get('trans'), gates=tuple(p[n] for n in gate_names), valid_tokens=ntok, teacher=tch)
+        if not first_tags:
+            first_tags.append(hashlib.sha256(tags.cpu().numpy().tobytes()).hexdigest()[:16])
         loss.backward()
         opt.step()
         return loss
@@ -87,7 +111,7 @@ def run(a, semiring, teacher=None, full=False):
     lib_ms, n = tc.time()
     tc.close()
     return dict(lib_us_per_step=round(1e3 * lib_ms / max(n, 1), 1), step_us_per_step=round(1e3 * e0.elapsed_time(e1) / a.steps, 1),
-                final_loss=float(loss.detach())), ntok, (V, S, R, K, B, L)
+                final_loss=float(loss.detach()), first_tags=first_tags[0]), ntok, (V, S, R, K, B, L)
 
 
 def source_hash():
@@ -118,6 +142,52 @@ def teacher_timing(a):
     print(json.dumps(out))
 
 
+MAX_LEGS = {'plain_sum_ragged': ('sum', dict()), 'plain_max_ragged': ('max', dict()),
+            'plain_max_full_length': ('max', dict(full=True)), 'teacher_max_ragged': ('max', dict(teacher=True)),
+            'teacher_max_full_length': ('max', dict(teacher=True, full=True))}
+
+
+def teacher_max_timing(a):
+    """one JSON line: every leg `--repeats` times in turn; --plain-only: the two plain ragged legs"""
+    older_library_ok()
+    legs = {k: v for k, v in MAX_LEGS.items() if not a.plain_only or k in ('plain_sum_ragged', 'plain_max_ragged')}
+    times, tags, ntoks = {k: [] for k in legs}, {}, {}
+    for _ in range(a.repeats):
+        for k, (semiring, kw) in legs.items():
+            kw = dict(kw, teacher=a.teacher_max) if kw.get('teacher') else kw
+            r, ntok, shape = run(a, semiring, **kw)
+            times[k].append(r['lib_us_per_step'])
+            tags[k], ntoks[k] = r['first_tags'], ntok
+    V, S, R, K, B, L = shape
+    print(json.dumps(dict(workload='decomp_train_teacher_max', teacher=a.teacher_max, V=V, S=S, R=R, K=K, B=B, L=L, farnn=a.farnn,
+                          crf=bool(a.crf), steps=a.steps, lib=os.environ.get('FARNN_LIB', 'default'),
+                          source_hash=None if os.environ.get('FARNN_LIB') else source_hash(), valid_tokens=ntoks, positions=B * L, lib_us_per_step=times, first_tags=tags)))
+
+
+def merge(files, other):
+    """the lines a job kept, per library (`other` names the one FARNN_LIB pointed to): medians, spreads and the tag hashes"""
+    rows = []
+    for fn in files:
+        with open(fn) as f:
+            rows += [json.loads(line) for line in f if line.startswith('{')]
+    libs = {}
+    for r in rows:
+        mine = r['lib'] == 'default'
+        d = libs.setdefault('this' if mine else other, dict(source_hash=r['source_hash'] if mine else None, lib_us_per_step={}, first_tags={}))
+        for k, v in r['lib_us_per_step'].items():
+            d['lib_us_per_step'].setdefault(k, []).extend(v)
+        for k, v in r['first_tags'].items():
+            d['first_tags'].setdefault(k, set()).add(v)
+    out = {k: rows[0][k] for k in ('workload', 'teacher', 'V', 'S', 'R', 'K', 'B', 'L', 'farnn', 'crf', 'steps', 'positions')}
+    out['valid_tokens'] = max((r['valid_tokens'] for r in rows), key=len)
+    out['libraries'] = {}
+    for lib, d in libs.items():
+        out['libraries'][lib] = dict(source_hash=d['source_hash'], first_tags={k: sorted(v) for k, v in d['first_tags'].items()},
+                                     lib_us_per_step={k: dict(median=float(np.median(v)), min=min(v), max=max(v), runs=v)
+                                                      for k, v in d['lib_us_per_step'].items()})
+    print(json.dumps(out, indent=1, sort_keys=True))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
@@ -128,7 +198,15 @@ def main():
     ap.add_argument('--crf', type=int, default=1)
     ap.add_argument('--teacher', choices=('kd', 'pr'), default=None)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--teacher-max', choices=('kd', 'pr'), default=None)
+    ap.add_argument('--plain-only', action='store_true')
+    ap.add_argument('--merge', nargs='+', default=None)
+    ap.add_argument('--other-label', default='other', help='--merge: the name of the library FARNN_LIB pointed to')
     a = ap.parse_args()
+    if a.merge:
+        return merge(a.merge, a.other_label)
+    if a.teacher_max or a.plain_only:
+        return teacher_max_timing(a)
     if a.teacher:
         return teacher_timing(a)
     out = {}
