@@ -3,7 +3,8 @@
 PyTorch-ROCm tensors are used only as device-memory containers; every number is produced by
 libfarnn_hip.so.  The method contract mirrors what the reference's callers consume
 (SURVEY.md 8b): ``val.val_onehot`` calls ``forward_local(x, label, lengths, train=False)`` and
-``RE.get_RE_prediction`` calls ``forward_RE(x, label, lengths, train=False)``.
+``RE.get_RE_prediction`` calls ``forward_RE(x, label, lengths, train=False)``.  The training surface of the five trainable
+mirrors is farnn/_trainable.py; the reader of their opt-in switches (opted_in) and the semiring's name (_semiring) live here.
 """
 import os
 
@@ -20,11 +21,25 @@ def default_device():
     return torch.cuda.current_device() if torch.cuda.is_available() else 0
 
 
+# The opt-in switches of the training steps (each opt-in for its first release), all read through opted_in():
+#   RE2NN_<name>=1            what it opens                                                                   DESIGN.md row
+#   ONEHOT_MAX_TRAIN          --train_mode max for the onehot i-FST (FARNN_S_O_I_S)                           f5
+#   ONEHOT_FST_TRAIN          the onehot FST's training step (FARNN_S_O)                                      f7
+#   ONEHOT_IND1_TRAIN         the onehot independent=1 model's training step (FARNN_S_O_I)                    f8
+#   DECOMP_IND1_TRAIN         the decomposed independent=1 model's training step (FARNN_S_D_W_I)              f9
+#   DECOMP_IND1_CRF_TRAIN     that step under --use_crf 1, beside DECOMP_IND1_TRAIN                           f9
+#   BUCKETED_MAX_TRAIN        --train_mode max for the three steps over bucketed per-word blocks (the onehot
+#                             FST, the onehot and the decomposed independent=1 model), beside each model's own f7 - f9
+#   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3
+#   DECOMP_TEACHER_MAX_TRAIN  those terms under --train_mode max, beside DECOMP_TEACHER_TRAIN                 f3
+#   NATIVE_OPTIM              the library's one-launch Adam / SGD in train_onehot.train_epochs                f6
+def opted_in(name):
+    """True only for RE2NN_<name>=1, read from the environment at call time."""
+    return os.environ.get('RE2NN_' + name, '') == '1'
+
+
 def bucketed_max_train_enabled():
-    """RE2NN_BUCKETED_MAX_TRAIN=1: --train_mode max for the three training steps over bucketed per-word blocks (the onehot FST,
-    the onehot and the decomposed independent=1 model), beside each model's own switch (opt-in for its
-    first release, as RE2NN_ONEHOT_MAX_TRAIN)"""
-    return os.environ.get('RE2NN_BUCKETED_MAX_TRAIN', '') == '1'
+    return opted_in('BUCKETED_MAX_TRAIN')
 
 
 class PendingLocal:
@@ -120,6 +135,10 @@ class NativeTagger:
 
     def _build_handle(self):
         raise NotImplementedError
+
+    def _semiring(self):
+        """The library's name of --train_mode, for the tagging handles and the training contexts."""
+        return 'max' if self.args.train_mode == 'max' else 'sum'
 
     # ---- the call --------------------------------------------------------------------------
     def _dev(self):

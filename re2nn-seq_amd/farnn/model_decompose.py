@@ -96,7 +96,6 @@ class FARNN_S_D_W(FARNN_S_D_W_I_S):
             self.wildcard_wildcard.numpy(), self.h0.numpy(), self.hT.numpy(),
             P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
             sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear,
-            semiring='max' if a.train_mode == 'max' else 'sum', threshold=a.threshold,
-            o_idx=self.o_idx, use_crf=self.use_crf,
+            semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx, use_crf=self.use_crf,
             crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(),
             device=self.device_index)

@@ -5,14 +5,13 @@ keys as the reference; inference runs in the HIP library (farnn_decomp_ind1_crea
 Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step; with --use_crf 1
 (RE2NN_DECOMP_IND1_CRF_TRAIN=1 beside it): farnn_decomp_ind1_crf_train_step.
 """
-import os
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .model_decompose_single import FARNN_S_D_W_I_S, crf_default_transitions, _GATE_KEYS
-from ._native import NativeTagger, bucketed_max_train_enabled
+from . import train_step
+from ._native import NativeTagger, bucketed_max_train_enabled, opted_in
 from .priority import expand_priority
 
 _PARAM_KEYS = ('S1', 'S2', 'V_embed', 'embed_r_generalized', 'C_output', 'S1_output', 'S2_output',
@@ -98,8 +97,7 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             self.S2_output.numpy(), self.h0.numpy(), self.hT.numpy(), Wo=Wo,
             P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
             sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear,
-            semiring='max' if a.train_mode == 'max' else 'sum', threshold=a.threshold,
-            o_idx=self.o_idx, use_crf=self.use_crf,
+            semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx, use_crf=self.use_crf,
             crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(),
             device=self.device_index)
 
@@ -111,19 +109,11 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
                     'wildcard_mat': 'train_wildcard_wildcard', 'h0': 'train_h0', 'hT': 'train_hT',
                     'beta_vec': 'train_beta', 'embedding.weight': 'train_word_embed'}
 
-    @staticmethod
-    def _decomp_ind1_train_enabled():
-        """RE2NN_DECOMP_IND1_TRAIN=1: this model's training step (opt-in for its first release, as RE2NN_ONEHOT_IND1_TRAIN)"""
-        return os.environ.get('RE2NN_DECOMP_IND1_TRAIN', '') == '1'
-
-    @staticmethod
-    def _decomp_ind1_crf_train_enabled():
-        """RE2NN_DECOMP_IND1_CRF_TRAIN=1: the step under --use_crf 1 (opt-in for its first release)"""
-        return os.environ.get('RE2NN_DECOMP_IND1_CRF_TRAIN', '') == '1'
+    _check_needs_re_tags = False     # every refusal but the teacher's is known without a batch
 
     def _check_trainable(self, re_tags=None):
         """The cases the HIP training step does not cover, refused before any device work."""
-        if not self._decomp_ind1_train_enabled():     # before self.args is touched: the refusal needs the type only
+        if not opted_in('DECOMP_IND1_TRAIN'):          # before self.args is touched: the refusal needs the type only
             from ..train_onehot import no_training_step
             raise no_training_step(self)
         a = self.args
@@ -132,7 +122,7 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             why = 'the gated recurrences (--farnn {})'.format(a.farnn)
         elif a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             why = 'the max semiring (--train_mode {})'.format(a.train_mode)
-        elif a.use_crf and not self._decomp_ind1_crf_train_enabled():
+        elif a.use_crf and not opted_in('DECOMP_IND1_CRF_TRAIN'):
             why = 'the CRF (--use_crf 1)'
         elif a.local_loss_func != 'CE1':
             why = 'a loss other than CE1 (--local_loss_func {})'.format(a.local_loss_func)
@@ -146,49 +136,16 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             raise NotImplementedError('training the decomposed independent=1 model covers farnn 0, the sum semiring and the CE1 '
                                       'loss on one GPU; {} is not built (DESIGN.md, row f9)'.format(why))
 
-    def enable_training(self):
-        """Device-resident leaf tensors for the optimizer (returned by parameters()) and the library context."""
-        self._check_trainable()
-        if getattr(self, '_tp', None) is not None:
-            return self
-        if not torch.cuda.is_available():
-            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
-        dev = self._dev()
-        src = dict(self.state_dict())
-        self._tp = {}
-        for k, flag in self._TRAIN_FLAGS.items():
-            t = src[k].detach().to(dev).float().clone()
-            t.requires_grad_(True if flag is None else bool(getattr(self.args, flag, 0)))
-            self._tp[k] = t
-        if self.use_crf:              # an nn.Parameter of the reference's CRF, always trainable (baselines/crf.py:46)
-            self._tp['crf.transitions'] = self.crf_transitions.detach().to(dev).float().clone().requires_grad_(True)
-        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
-            if self.args.use_priority else None
-        S, R = self._tp['S1'].shape
-        C, RO = self._tp['C_output'].shape
-        self._tc = _lib.Decomp1TrainContext(self._tp['V_embed'].shape[0], S, R, RO, C, nl=self.args.update_nonlinear,
-                                            threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
-                                            semiring='max' if self.args.train_mode == 'max' else 'sum')
-        self._dirty = False
-        return self
-
-    def forward_local(self, input, label, lengths, train=True, re_tags=None):
-        if not train:
-            self.sync_from_training()
-            return NativeTagger.forward_local(self, input, label, lengths, train=False, re_tags=re_tags)
-        from .train_step import decomp_ind1_train_step
-        self._check_trainable(re_tags)
-        self.enable_training()
+    def _train_context(self):
         tp = self._tp
-        on_host = lengths.device.type == 'cpu'
-        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
-        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
-        x = input[:, :Lmax]
-        lab = label[:, :Lmax]
-        loss, tags = decomp_ind1_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
-                                            tp['C_output'], tp['S1_output'], tp['S2_output'], tp['h0'], tp['hT'], self._tpP,
-                                            x, lengths, lab, valid_tokens=ntok, crf_trans=tp.get('crf.transitions'))
-        self._dirty = True
-        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
-        true = self._flatten(label, lengths).to(input.device)
-        return loss, pred, true
+        S, R = tp['S1'].shape
+        C, RO = tp['C_output'].shape
+        return _lib.Decomp1TrainContext(tp['V_embed'].shape[0], S, R, RO, C, nl=self.args.update_nonlinear,
+                                        threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
+                                        semiring=self._semiring())
+
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp
+        return train_step.decomp_ind1_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
+                                                 tp['C_output'], tp['S1_output'], tp['S2_output'], tp['h0'], tp['hT'], self._tpP,
+                                                 x, lengths, lab, valid_tokens=ntok, crf_trans=tp.get('crf.transitions'))

@@ -8,13 +8,13 @@ weights are frozen on the tagging path, the per-token ``get_generalized_v_embed_
 (model_decompose.py:222-241) is folded once into a table ``Vgen[V,R]`` when the device handle is
 built -- the reference recomputes it twice per time step.
 """
-import os
-
 import numpy as np
 import torch
 
 from .. import _lib
-from ._native import NativeTagger
+from . import train_step
+from ._native import NativeTagger, opted_in
+from ._trainable import Trainable
 from .priority import expand_priority
 
 _GATE_KEYS = ('Wss1', 'Wrs1', 'bs1', 'Wss2', 'Wrs2', 'bs2')
@@ -31,9 +31,10 @@ def crf_default_transitions(tagset_size):
     return tr
 
 
-class FARNN_S_D_W_I_S(NativeTagger):
+class FARNN_S_D_W_I_S(Trainable, NativeTagger):
     _param_keys = _PARAM_KEYS
     local_uses_max_len = True        # forward_local iterates lengths.max() positions (ref :221)
+    _check_needs_re_tags = True      # so enable_training() and train_onehot.check_trainable() leave the check to forward_local
 
     def __init__(self, V=None, S1=None, S2=None, C_output_mat=None, wildcard_mat=None,
                  wildcard_output_vector=None, final_vector=None, start_vector=None,
@@ -168,8 +169,7 @@ class FARNN_S_D_W_I_S(NativeTagger):
             add_nl=a.additional_nonlinear,
             P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
             sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear,
-            semiring='max' if a.train_mode == 'max' else 'sum', threshold=a.threshold,
-            o_idx=self.o_idx, use_crf=self.use_crf,
+            semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx, use_crf=self.use_crf,
             crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(),
             device=self.device_index)
 
@@ -189,16 +189,16 @@ class FARNN_S_D_W_I_S(NativeTagger):
         marryup = getattr(a, 'marryup_type', 'none')
         teacher = marryup in ('kd', 'pr')
         plain = re_tags is None and marryup in ('none', None)
-        opted_in = os.environ.get('RE2NN_DECOMP_TEACHER_TRAIN', '') == '1' and marryup in ('none', None, 'kd', 'pr')
+        with_teacher = opted_in('DECOMP_TEACHER_TRAIN') and marryup in ('none', None, 'kd', 'pr')
         if a.farnn not in (0, 1, 2) or a.train_mode not in ('sum', 'max') or a.local_loss_func != 'CE1' \
-                or not (plain or opted_in):
+                or not (plain or with_teacher):
             raise NotImplementedError('the HIP training step covers the sum and max semirings and the CE1 loss (with or '
                                       'without the CRF), no KD/PR teachers (DESIGN.md, row f3)')
         if teacher and re_tags is None:
             raise ValueError('--marryup_type {} needs the RE teacher\'s scores: forward_local(..., re_tags=...)'.format(marryup))
         if re_tags is not None and not teacher:
             raise ValueError('re_tags were given but --marryup_type is {!r}: the teacher term would be dropped silently'.format(marryup))
-        if teacher and a.train_mode == 'max' and os.environ.get('RE2NN_DECOMP_TEACHER_MAX_TRAIN', '') != '1':
+        if teacher and a.train_mode == 'max' and not opted_in('DECOMP_TEACHER_MAX_TRAIN'):
             raise NotImplementedError('the KD / PR teacher terms are built for the sum semiring only; --train_mode max walks the '
                                       'valid positions only (DESIGN.md, row f3)')
         return teacher
@@ -217,61 +217,23 @@ class FARNN_S_D_W_I_S(NativeTagger):
         pi = float(a.c2_kdpr) if a.marryup_type == 'kd' else max(float(a.c2_kdpr), float(a.c3_pr) ** self.t)
         return re, a.marryup_type, float(a.c1_kdpr), pi
 
-    def enable_training(self):
-        """Device-resident leaf tensors for the optimizer (returned by parameters()) and the library context."""
-        if getattr(self, '_tp', None) is not None:
-            return self
-        if not torch.cuda.is_available():
-            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
-        dev = self._dev()
-        src = dict(self.state_dict())
-        self._tp = {}
-        for k, flag in self._TRAIN_FLAGS.items():
-            t = src[k].detach().to(dev).float().clone()
-            t.requires_grad_(True if flag is None else bool(getattr(self.args, flag, 0)))
-            self._tp[k] = t
-        for k in _GATE_KEYS[:3 * int(self.args.farnn)]:
-            self._tp[k] = src[k].detach().to(dev).float().clone().requires_grad_(True)
-        if self.use_crf:
-            self._tp['crf.transitions'] = self.crf_transitions.detach().to(dev).float().clone().requires_grad_(True)
-        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
-            if self.args.use_priority else None
-        S, R = self._tp['S1'].shape
-        self._tc = _lib.TrainContext(self._tp['V_embed'].shape[0], S, R, self._tp['C_output_mat'].shape[0],
-                                     nl=self.args.update_nonlinear, threshold=self.args.threshold, o_idx=self.o_idx,
-                                     device=self.device_index, use_crf=self.use_crf, farnn=int(self.args.farnn),
-                                     sigmoid_exponent=float(self.args.sigmoid_exponent),
-                                     semiring=self.args.train_mode,
-                                     teacher_max=os.environ.get('RE2NN_DECOMP_TEACHER_MAX_TRAIN', '') == '1')
-        self._dirty = False
-        return self
+    def _train_decl(self):
+        """_TRAIN_FLAGS, then the gates of --farnn 1 / 2 and the CRF's transitions: nn.Parameters of the reference, always trainable
+        (baselines/crf.py:46)."""
+        extra = _GATE_KEYS[:3 * int(self.args.farnn)] + (('crf.transitions',) if self.use_crf else ())
+        return super()._train_decl() + [(k, True) for k in extra]
 
-    def parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+    def _train_context(self):
+        tp, a = self._tp, self.args
+        S, R = tp['S1'].shape
+        return _lib.TrainContext(tp['V_embed'].shape[0], S, R, tp['C_output_mat'].shape[0], nl=a.update_nonlinear,
+                                 threshold=a.threshold, o_idx=self.o_idx, device=self.device_index, use_crf=self.use_crf,
+                                 farnn=int(a.farnn), sigmoid_exponent=float(a.sigmoid_exponent), semiring=self._semiring(),
+                                 teacher_max=opted_in('DECOMP_TEACHER_MAX_TRAIN'))
 
-    def named_parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
-
-    def sync_from_training(self):
-        """Copy the trained tensors back into the host attributes the tagging handle is built from."""
-        tp = getattr(self, '_tp', None)
-        if tp is None or not self._dirty:
-            return
+    def _copy_back(self, tp):
         for k, t in tp.items():
-            if k == 'embedding.weight':
-                self.embedding = t.detach().cpu()
-            elif k == 'crf.transitions':
-                self.crf_transitions = t.detach().cpu()
-            else:
-                setattr(self, k, t.detach().cpu())
-        self._dirty = False
-        self.invalidate()
-
-    def eval(self):
-        self.sync_from_training()
-        return super().eval()
+            setattr(self, {'embedding.weight': 'embedding', 'crf.transitions': 'crf_transitions'}.get(k, k), t.detach().cpu())
 
     def _train_vgen(self):
         tp = self._tp
@@ -287,23 +249,13 @@ class FARNN_S_D_W_I_S(NativeTagger):
             gen = torch.tanh(torch.relu(gen))
         return tp['V_embed'] * tp['beta_vec'] + gen * (1 - tp['beta_vec'])
 
-    def forward_local(self, input, label, lengths, train=True, re_tags=None):
-        if not train:
-            self.sync_from_training()
-            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
-        from .train_step import decomp_ifst_train_step
-        teacher = self._check_trainable(re_tags)
-        self.enable_training()
-        tp = self._tp
-        Lmax = int(lengths.max().item())
-        x = input[:, :Lmax]
-        lab = label[:, :Lmax]
-        loss, tags = decomp_ifst_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
-                                            tp['C_output_mat'], tp['h0'], tp['hT'], self._tpP, x, lengths, lab,
-                                            crf_trans=tp.get('crf.transitions'),
-                                            gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]),
-                                            teacher=self._teacher(re_tags, Lmax) if teacher else None)
-        self._dirty = True
-        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
-        true = self._flatten(label, lengths).to(input.device)
-        return loss, pred, true
+    def _check_step(self, re_tags):
+        self._check_trainable(re_tags)
+
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp                  # past _check_trainable, re_tags are given exactly under --marryup_type kd | pr
+        return train_step.decomp_ifst_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
+                                                 tp['C_output_mat'], tp['h0'], tp['hT'], self._tpP, x, lengths, lab,
+                                                 crf_trans=tp.get('crf.transitions'),
+                                                 gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]), valid_tokens=ntok,
+                                                 teacher=None if re_tags is None else self._teacher(re_tags, x.shape[1]))

@@ -8,13 +8,13 @@ HIP library through the C-ABI (include/farnn.h).
   FARNN_S_O_I    two 3-D tensors          (--independent 1)   ref :184-306
   FARNN_S_O_I_S  i-FST, T[V,S,S] + O[C,S] (--independent 2)   ref :310-428
 """
-import os
-
 import numpy as np
 import torch
 
 from .. import _lib
-from ._native import NativeTagger, bucketed_max_train_enabled
+from . import train_step
+from ._native import NativeTagger, bucketed_max_train_enabled, opted_in
+from ._trainable import Trainable
 from .priority import expand_priority
 
 
@@ -39,7 +39,7 @@ class _OnehotBase(NativeTagger):
         return self.priority_full if self.args.use_priority else None
 
 
-class FARNN_S_O_I_S(_OnehotBase):
+class FARNN_S_O_I_S(Trainable, _OnehotBase):
     def __init__(self, language_tensor=None, output_mat=None, wildcard_mat=None,
                  output_wildcard_vector=None, final_vector=None, start_vector=None, priority_mat=None,
                  args=None, o_idx=0, is_cuda=False):
@@ -102,9 +102,8 @@ class FARNN_S_O_I_S(_OnehotBase):
         a = self.args
         if a.local_loss_func != 'CE1':
             raise NotImplementedError('only CE1 is reachable from main.py (:127)')
-        kw = dict(P=self._P(), nl=a.update_nonlinear, semiring='max' if a.train_mode == 'max' else 'sum',
-                  threshold=a.threshold, o_idx=self.o_idx, use_crf=self.use_crf,
-                  crf_trans=self.crf_transitions, device=self.device_index)
+        kw = dict(P=self._P(), nl=a.update_nonlinear, semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx,
+                  use_crf=self.use_crf, crf_trans=self.crf_transitions, device=self.device_index)
         if getattr(self, 'edges', None) is not None:
             word, frm, to, label = self.edges
             return _lib.create_onehot_ifst_from_edges(self.V, self.S, self.C, word, frm, to, label,
@@ -116,7 +115,7 @@ class FARNN_S_O_I_S(_OnehotBase):
     def _check_trainable(self):
         """The cases the HIP training step does not cover, refused before any device work."""
         a = self.args
-        if a.train_mode != 'sum' and not (a.train_mode == 'max' and self._max_train_enabled()):
+        if a.train_mode != 'sum' and not (a.train_mode == 'max' and opted_in('ONEHOT_MAX_TRAIN')):
             raise NotImplementedError('training the onehot i-FST covers the sum semiring only by default; --train_mode max '
                                       'is opt-in (set RE2NN_ONEHOT_MAX_TRAIN=1), --train_mode {} was asked for '
                                       '(DESIGN.md, row f5)'.format(a.train_mode))
@@ -130,78 +129,25 @@ class FARNN_S_O_I_S(_OnehotBase):
             raise NotImplementedError('multi-GPU data-parallel training of the onehot i-FST is not built; train on one '
                                       'GPU (DESIGN.md, row f5)')
 
-    @staticmethod
-    def _max_train_enabled():
-        """RE2NN_ONEHOT_MAX_TRAIN=1: the max-semiring training step (opt-in for its first release, as RE2NN_NATIVE_OPTIM)"""
-        return os.environ.get('RE2NN_ONEHOT_MAX_TRAIN', '') == '1'
+    _TRAIN_FLAGS = {'language_tensor': None, 'wildcard_mat': False, 'output_mat': False, 'h0': False, 'hT': False}   # ref :326-337
 
-    def enable_training(self):
-        """Device-resident tensors (language_tensor the only one with requires_grad, as in the reference :326-337) and
-        the library context.  An edge-built model gets its dense tensors here (_dense())."""
-        self._check_trainable()
-        if getattr(self, '_tp', None) is not None:
-            return self
-        if not torch.cuda.is_available():
-            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
-        dev = self._dev()
-        sd = self.state_dict()
-        self._tp = {}
-        for k in ('language_tensor', 'wildcard_mat', 'output_mat', 'h0', 'hT'):
-            t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).clone()
-            self._tp[k] = t.requires_grad_(k == 'language_tensor')
-        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
-            if self.args.use_priority else None
+    def _train_context(self):
         V, S, _ = self._tp['language_tensor'].shape
-        self._tc = _lib.OnehotTrainContext(V, S, self.C, nl=self.args.update_nonlinear, threshold=self.args.threshold,
-                                           o_idx=self.o_idx, device=self.device_index,
-                                           semiring='max' if self.args.train_mode == 'max' else 'sum')
-        self._dirty = False
-        return self
+        return _lib.OnehotTrainContext(V, S, self.C, nl=self.args.update_nonlinear, threshold=self.args.threshold,
+                                       o_idx=self.o_idx, device=self.device_index, semiring=self._semiring())
 
-    def parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp
+        return train_step.onehot_ifst_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_mat'],
+                                                 tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
 
-    def named_parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
-
-    def sync_from_training(self):
-        """Copy the trained language_tensor back into the host attributes the tagging handle is built from.  An
-        edge-built model becomes a dense one (its edges no longer describe the weights)."""
-        tp = getattr(self, '_tp', None)
-        if tp is None or not self._dirty:
-            return
+    def _copy_back(self, tp):
+        """An edge-built model becomes a dense one (its edges no longer describe the weights)."""
         if getattr(self, 'edges', None) is not None:
             self.language_tensor, self.wildcard_mat, self.output_mat = self._dense()
             self.output_wildcard_vector = np.zeros(self.S, np.float32)
             self.edges = None
         self.language_tensor = tp['language_tensor'].detach().cpu().numpy()
-        self._dirty = False
-        self.invalidate()
-
-    def eval(self):
-        self.sync_from_training()
-        return super().eval()
-
-    def forward_local(self, input, label, lengths, train=True, re_tags=None):
-        if not train:
-            self.sync_from_training()
-            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
-        from .train_step import onehot_ifst_train_step
-        self.enable_training()
-        tp = self._tp
-        on_host = lengths.device.type == 'cpu'
-        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
-        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
-        x = input[:, :Lmax]
-        lab = label[:, :Lmax]
-        loss, tags = onehot_ifst_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_mat'],
-                                            tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
-        self._dirty = True
-        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
-        true = self._flatten(label, lengths).to(input.device)
-        return loss, pred, true
 
     def state_dict(self):
         self.sync_from_training()
@@ -214,7 +160,7 @@ class FARNN_S_O_I_S(_OnehotBase):
                 'output_wildcard_vector': self.output_wildcard_vector}
 
 
-class FARNN_S_O(_OnehotBase):
+class FARNN_S_O(Trainable, _OnehotBase):
     def __init__(self, language_tensor=None, wildcard_tensor=None, wildcard_wildcard_mat=None,
                  final_vector=None, start_vector=None, priority_mat=None, args=None, o_idx=0,
                  is_cuda=False):
@@ -250,12 +196,10 @@ class FARNN_S_O(_OnehotBase):
             word, frm, to, label = self.edges
             return _lib.create_onehot_fst4_from_edges(
                 self.V, self.S, self.C, word, frm, to, label, self.h0, self.hT, P=self._P(),
-                semiring='max' if a.train_mode == 'max' else 'sum', threshold=a.threshold,
-                o_idx=self.o_idx, device=self.device_index)
+                semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx, device=self.device_index)
         return _lib.create_onehot_fst4(
             self.language_tensor, self.wildcard_tensor, self.h0, self.hT, P=self._P(),
-            semiring='max' if a.train_mode == 'max' else 'sum', threshold=a.threshold,
-            o_idx=self.o_idx, device=self.device_index)
+            semiring=self._semiring(), threshold=a.threshold, o_idx=self.o_idx, device=self.device_index)
 
     def _dense(self):
         """language_tensor / wildcard_tensor of an edge-built model, on demand (enable_training, state_dict)."""
@@ -269,17 +213,12 @@ class FARNN_S_O(_OnehotBase):
         return T, W
 
     # ---- training step (reference :66-146 with train=True + train_onehot.py:156-206) ----
-    @staticmethod
-    def _fst_train_enabled():
-        """RE2NN_ONEHOT_FST_TRAIN=1: the FST's training step (opt-in for its first release, as RE2NN_ONEHOT_MAX_TRAIN)"""
-        return os.environ.get('RE2NN_ONEHOT_FST_TRAIN', '') == '1'
-
     def _check_trainable(self):
         """The cases the HIP training step does not cover, refused before any device work."""
-        a = self.args
-        if not self._fst_train_enabled():
+        if not opted_in('ONEHOT_FST_TRAIN'):           # before self.args is touched: the refusal needs the type only
             from ..train_onehot import no_training_step
             raise no_training_step(self)              # today's refusal, word for word
+        a = self.args
         if a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
             raise NotImplementedError('training the onehot FST covers the sum semiring only, --train_mode {} was asked for '
                                       '(DESIGN.md, row f7)'.format(a.train_mode))
@@ -293,73 +232,24 @@ class FARNN_S_O(_OnehotBase):
             raise NotImplementedError('multi-GPU data-parallel training of the onehot FST is not built; train on one GPU '
                                       '(DESIGN.md, row f7)')
 
-    def enable_training(self):
-        """Device-resident tensors (language_tensor with requires_grad, wildcard_tensor iff args.train_wildcard, as in
-        the reference :32-37) and the library context.  An edge-built model gets its dense tensors here (_dense())."""
-        self._check_trainable()
-        if getattr(self, '_tp', None) is not None:
-            return self
-        if not torch.cuda.is_available():
-            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
-        dev = self._dev()
-        sd = self.state_dict()
-        grad = {'language_tensor': True, 'wildcard_tensor': bool(getattr(self.args, 'train_wildcard', 0))}
-        self._tp = {}
-        for k in ('language_tensor', 'wildcard_tensor', 'h0', 'hT'):
-            t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).clone()
-            self._tp[k] = t.requires_grad_(grad.get(k, False))
-        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
-            if self.args.use_priority else None
-        V = self._tp['language_tensor'].shape[0]
-        self._tc = _lib.Fst4TrainContext(V, self.S, self.C, threshold=self.args.threshold, o_idx=self.o_idx,
-                                         device=self.device_index, semiring='max' if self.args.train_mode == 'max' else 'sum')
-        self._dirty = False
-        return self
+    _TRAIN_FLAGS = {'language_tensor': None, 'wildcard_tensor': 'train_wildcard', 'h0': False, 'hT': False}          # ref :32-37
 
-    def parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+    def _train_context(self):
+        return _lib.Fst4TrainContext(self._tp['language_tensor'].shape[0], self.S, self.C, threshold=self.args.threshold,
+                                     o_idx=self.o_idx, device=self.device_index, semiring=self._semiring())
 
-    def named_parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp
+        return train_step.onehot_fst4_train_step(self._tc, tp['language_tensor'], tp['wildcard_tensor'], tp['h0'], tp['hT'],
+                                                 self._tpP, x, lengths, lab, valid_tokens=ntok)
 
-    def sync_from_training(self):
-        """Copy the trained tensors back into the host attributes the tagging handle is built from (the handle's own
-        premixed copy is stale after an optimizer step).  An edge-built model becomes a dense one."""
-        tp = getattr(self, '_tp', None)
-        if tp is None or not self._dirty:
-            return
+    def _copy_back(self, tp):
+        """An edge-built model becomes a dense one."""
         if getattr(self, 'edges', None) is not None:
             self.wildcard_wildcard_mat = np.zeros((self.S, self.S), np.float32)
             self.edges = None
         self.language_tensor = tp['language_tensor'].detach().cpu().numpy()
         self.wildcard_tensor = tp['wildcard_tensor'].detach().cpu().numpy()
-        self._dirty = False
-        self.invalidate()
-
-    def eval(self):
-        self.sync_from_training()
-        return super().eval()
-
-    def forward_local(self, input, label, lengths, train=True, re_tags=None):
-        if not train:
-            self.sync_from_training()
-            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
-        from .train_step import onehot_fst4_train_step
-        self.enable_training()
-        tp = self._tp
-        on_host = lengths.device.type == 'cpu'
-        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
-        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
-        x = input[:, :Lmax]
-        lab = label[:, :Lmax]
-        loss, tags = onehot_fst4_train_step(self._tc, tp['language_tensor'], tp['wildcard_tensor'], tp['h0'], tp['hT'],
-                                            self._tpP, x, lengths, lab, valid_tokens=ntok)
-        self._dirty = True
-        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
-        true = self._flatten(label, lengths).to(input.device)
-        return loss, pred, true
 
     def state_dict(self):
         self.sync_from_training()
@@ -372,7 +262,7 @@ class FARNN_S_O(_OnehotBase):
                 'wildcard_wildcard_mat': self.wildcard_wildcard_mat}
 
 
-class FARNN_S_O_I(_OnehotBase):
+class FARNN_S_O_I(Trainable, _OnehotBase):
     def __init__(self, language_tensor=None, output_tensor=None, wildcard_mat=None,
                  output_wildcard_mat=None, final_vector=None, start_vector=None, priority_mat=None,
                  args=None, o_idx=0, is_cuda=False):
@@ -410,12 +300,11 @@ class FARNN_S_O_I(_OnehotBase):
             word, frm, to, label = self.edges
             return _lib.create_onehot_ind1_from_edges(
                 self.V, self.S, self.C, word, frm, to, label, self.h0, self.hT, P=self._P(),
-                semiring='max' if a.train_mode == 'max' else 'sum', mask_by_output=(a.independent == 2),
+                semiring=self._semiring(), mask_by_output=(a.independent == 2),
                 threshold=a.threshold, o_idx=self.o_idx, device=self.device_index)
         return _lib.create_onehot_ind1(
             self.language_tensor, self.wildcard_mat, self.output_tensor, self.h0, self.hT, P=self._P(),
-            semiring='max' if a.train_mode == 'max' else 'sum',
-            mask_by_output=(a.independent == 2), threshold=a.threshold, o_idx=self.o_idx,
+            semiring=self._semiring(), mask_by_output=(a.independent == 2), threshold=a.threshold, o_idx=self.o_idx,
             device=self.device_index)
 
     def _dense(self):
@@ -435,14 +324,9 @@ class FARNN_S_O_I(_OnehotBase):
         return T, W, O
 
     # ---- training step (reference :229-306 with train=True + train_onehot.py:156-206) ----
-    @staticmethod
-    def _ind1_train_enabled():
-        """RE2NN_ONEHOT_IND1_TRAIN=1: this model's training step (opt-in for its first release, as RE2NN_ONEHOT_FST_TRAIN)"""
-        return os.environ.get('RE2NN_ONEHOT_IND1_TRAIN', '') == '1'
-
     def _check_trainable(self):
         """The cases the HIP training step does not cover, refused before any device work."""
-        if not self._ind1_train_enabled():            # before self.args is touched: the refusal needs the type only
+        if not opted_in('ONEHOT_IND1_TRAIN'):          # before self.args is touched: the refusal needs the type only
             from ..train_onehot import no_training_step
             raise no_training_step(self)              # today's refusal, word for word
         a = self.args
@@ -456,73 +340,25 @@ class FARNN_S_O_I(_OnehotBase):
             raise NotImplementedError('multi-GPU data-parallel training of the onehot independent=1 model is not built; '
                                       'train on one GPU (DESIGN.md, row f8)')
 
-    def enable_training(self):
-        """Device-resident tensors (language_tensor the only one with requires_grad, as in the reference :209-223) and the
-        library context.  An edge-built model gets its dense tensors here (_dense())."""
-        self._check_trainable()
-        if getattr(self, '_tp', None) is not None:
-            return self
-        if not torch.cuda.is_available():
-            raise _lib.FarnnError('no MI355X visible; the training step has no CPU fallback')
-        dev = self._dev()
-        sd = self.state_dict()
-        self._tp = {}
-        for k in ('language_tensor', 'wildcard_mat', 'output_tensor', 'h0', 'hT'):
-            t = torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)).to(dev).clone()
-            self._tp[k] = t.requires_grad_(k == 'language_tensor')
-        self._tpP = torch.from_numpy(np.ascontiguousarray(self.priority_full, dtype=np.float32)).to(dev) \
-            if self.args.use_priority else None
-        V = self._tp['language_tensor'].shape[0]
-        self._tc = _lib.Ind1TrainContext(V, self.S, self.C, mask_by_output=(self.args.independent == 2),
-                                         threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
-                                         semiring='max' if self.args.train_mode == 'max' else 'sum')
-        self._dirty = False
-        return self
+    _TRAIN_FLAGS = {'language_tensor': None, 'wildcard_mat': False, 'output_tensor': False, 'h0': False, 'hT': False}   # ref :209-223
 
-    def parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([t for t in tp.values() if t.requires_grad])
+    def _train_context(self):
+        return _lib.Ind1TrainContext(self._tp['language_tensor'].shape[0], self.S, self.C,
+                                     mask_by_output=(self.args.independent == 2), threshold=self.args.threshold,
+                                     o_idx=self.o_idx, device=self.device_index, semiring=self._semiring())
 
-    def named_parameters(self):
-        tp = getattr(self, '_tp', None)
-        return iter(()) if tp is None else iter([(k, t) for k, t in tp.items() if t.requires_grad])
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp
+        return train_step.onehot_ind1_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_tensor'],
+                                                 tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
 
-    def sync_from_training(self):
-        """Copy the trained language_tensor back into the host attributes the tagging handle is built from.  An
-        edge-built model becomes a dense one (its edges no longer describe the weights)."""
-        tp = getattr(self, '_tp', None)
-        if tp is None or not self._dirty:
-            return
+    def _copy_back(self, tp):
+        """An edge-built model becomes a dense one (its edges no longer describe the weights)."""
         if getattr(self, 'edges', None) is not None:
             self.language_tensor, self.wildcard_mat, self.output_tensor = self._dense()
             self.output_wildcard_mat = None
             self.edges = None
         self.language_tensor = tp['language_tensor'].detach().cpu().numpy()
-        self._dirty = False
-        self.invalidate()
-
-    def eval(self):
-        self.sync_from_training()
-        return super().eval()
-
-    def forward_local(self, input, label, lengths, train=True, re_tags=None):
-        if not train:
-            self.sync_from_training()
-            return super().forward_local(input, label, lengths, train=False, re_tags=re_tags)
-        from .train_step import onehot_ind1_train_step
-        self.enable_training()
-        tp = self._tp
-        on_host = lengths.device.type == 'cpu'
-        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
-        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
-        x = input[:, :Lmax]
-        lab = label[:, :Lmax]
-        loss, tags = onehot_ind1_train_step(self._tc, tp['language_tensor'], tp['wildcard_mat'], tp['output_tensor'],
-                                            tp['h0'], tp['hT'], self._tpP, x, lengths, lab, valid_tokens=ntok)
-        self._dirty = True
-        pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
-        true = self._flatten(label, lengths).to(input.device)
-        return loss, pred, true
 
     def state_dict(self):
         self.sync_from_training()

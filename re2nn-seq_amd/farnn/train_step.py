@@ -1,5 +1,7 @@
-"""The training steps on the HIP path, as torch.autograd.Functions around farnn_decomp_ifst_train_step,
+"""The training steps on the HIP path: one torch.autograd.Function (_TrainStep) around farnn_decomp_ifst_train_step,
 farnn_onehot_ifst_train_step, farnn_fst4_train_step, farnn_ind1_train_step and farnn_decomp_ind1_train_step (include/farnn.h).
+Each public function below describes its weights to it (the C struct's field, the tensor, when its gradient is asked of the
+library) and, where the call is not the context's plain step(), makes the library call itself (teacher_step, step_crf).
 
 What the reference does in FARNN_S_D_W_I_S.forward_local(train=True) + loss.backward()
 (model_decompose_single.py:207-304, train_decompose.py:186-190) is split like this: the word table
@@ -57,55 +59,45 @@ def _step_inputs(ref, ntok, x, lengths, labels):
     return dev, ntok, x, lengths, labels, loss, tags
 
 
-class _DecompIfstTrainStep(torch.autograd.Function):
+ALWAYS, IF_REQUIRED, NEVER = 'always', 'if it requires one', 'never'      # when a weight's gradient is asked of the library
+_GRAD_FIELD = {'crf_trans': 'dtrans'}                                      # the outputs struct's field, where it is not 'd' + name
+
+
+class _TrainStep(torch.autograd.Function):
+    """One library step.  names / wants / tensors describe the weights: the field of the C weights struct, when the gradient
+    is wanted, and the tensor (None: a null pointer and no gradient).  call(weights, ptrs, dims, outputs, stream) makes the
+    library call, with ptrs = the device pointers of x, lengths and labels and dims = (B, L, valid_tokens); None is tc.step."""
     @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, teacher, P, Vgen, S1, S2, W, Cmat, h0, hT, trans, *gates):
-        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(Vgen, ntok, x, lengths, labels)
-        B, L = x.shape
-        ws = [_f32(t) for t in (Vgen, S1, S2, W, Cmat, h0, hT)]
-        Pc, tr = _f32(P), _f32(trans)
-        gs = [_f32(g) for g in gates]
-        grads = [torch.empty_like(t) for t in ws]
-        gtr = None if tr is None else torch.empty_like(tr)
-        ggs = [torch.empty_like(g) for g in gs]
-        names = ('Vgen', 'S1', 'S2', 'W', 'C', 'h0', 'hT')
-        weights = {n: t.data_ptr() for n, t in zip(names, ws)}
-        weights['P'] = None if Pc is None else Pc.data_ptr()
-        weights['crf_trans'] = None if tr is None else tr.data_ptr()
-        outputs = {'d' + n: g.data_ptr() for n, g in zip(names, grads)}
+    def forward(ctx, tc, ntok, x, lengths, labels, call, names, wants, *tensors):
+        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(tensors[0], ntok, x, lengths, labels)
+        ws = [_f32(t) for t in tensors]
+        grads = [torch.empty_like(w) if w is not None and (want == ALWAYS or (want == IF_REQUIRED and t.requires_grad)) else None
+                 for t, w, want in zip(tensors, ws, wants)]
+        weights = {n: None if w is None else w.data_ptr() for n, w in zip(names, ws)}
+        outputs = {_GRAD_FIELD.get(n, 'd' + n): None if g is None else g.data_ptr() for n, g in zip(names, grads)}
         outputs['loss'] = loss.data_ptr()
         outputs['tags'] = tags.data_ptr()
-        outputs['dtrans'] = None if gtr is None else gtr.data_ptr()
-        for n, g, gg in zip(GATE_NAMES, gs, ggs):
-            weights[n] = g.data_ptr()
-            outputs['d' + n] = gg.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if teacher is None:
-            tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs, stream)
-        else:
-            re, mode, c1, pi = teacher
-            re = re.detach().to(dev).float().contiguous()
-            if tuple(re.shape) != (B, L, Cmat.shape[0]):
-                raise ValueError('teacher scores must be [B, L, K] = {}, not {}'.format((B, L, Cmat.shape[0]), tuple(re.shape)))
-            tc.teacher_step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), re.data_ptr(), mode, c1, pi, B, L,
-                            ntok, outputs, stream)
-        ctx.has_tr = gtr is not None
-        ctx.n_gates = len(gs)
-        ctx.save_for_backward(*(grads + ([gtr] if gtr is not None else []) + ggs))
+        (call or _plain(tc))(weights, (x.data_ptr(), lengths.data_ptr(), labels.data_ptr()), tuple(x.shape) + (ntok,), outputs,
+                             torch.cuda.current_stream(dev).cuda_stream)
+        ctx.have = tuple(g is not None for g in grads)
+        ctx.save_for_backward(*[g for g in grads if g is not None])
         ctx.mark_non_differentiable(tags)
         return loss.reshape(()), tags
 
     @staticmethod
     def backward(ctx, gloss, _gtags):
-        saved = ctx.saved_tensors
-        grads = [g * gloss for g in saved[:7]]
-        k = 7
-        gtr = None
-        if ctx.has_tr:
-            gtr = saved[k] * gloss
-            k += 1
-        ggs = [g * gloss for g in saved[k:k + ctx.n_gates]]
-        return (None, None, None, None, None, None, None) + tuple(grads) + (gtr,) + tuple(ggs)
+        saved = iter(ctx.saved_tensors)
+        return (None,) * 8 + tuple(next(saved) * gloss if h else None for h in ctx.have)
+
+
+def _plain(tc):
+    return lambda weights, ptrs, dims, outputs, stream: tc.step(weights, *ptrs, *dims, outputs, stream)
+
+
+def _step(tc, ntok, x, lengths, labels, spec, call=None):
+    """spec: (name, tensor, ALWAYS | IF_REQUIRED | NEVER) per weight; the first one is a tensor and names the device."""
+    names, tensors, wants = zip(*spec)
+    return _TrainStep.apply(tc, ntok, x, lengths, labels, call, names, wants, *tensors)
 
 
 def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, labels, crf_trans=None, gates=(),
@@ -116,117 +108,49 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
     teacher: None, or (re_scores [B,L,K] with the zero columns appended, 'kd' | 'pr', c1, pi) for
     loss = pi * original + (1 - pi) * KL (farnn_decomp_ifst_teacher_train_step / _teacher_max_train_step, include/farnn.h); the teacher scores get no
     gradient."""
-    return _DecompIfstTrainStep.apply(tc, valid_tokens, x, lengths, labels, teacher, P, Vgen, S1, S2, W, Cmat, h0, hT, crf_trans,
-                                      *gates)
+    call = None
+    if teacher is not None:
+        def call(weights, ptrs, dims, outputs, stream):
+            re, mode, c1, pi = teacher
+            re = re.detach().to(Vgen.device).float().contiguous()
+            if tuple(re.shape) != dims[:2] + (Cmat.shape[0],):
+                raise ValueError('teacher scores must be [B, L, K] = {}, not {}'.format(dims[:2] + (Cmat.shape[0],), tuple(re.shape)))
+            tc.teacher_step(weights, *ptrs, re.data_ptr(), mode, c1, pi, *dims, outputs, stream)
+    spec = [(n, t, ALWAYS) for n, t in zip(('Vgen', 'S1', 'S2', 'W', 'C', 'h0', 'hT'), (Vgen, S1, S2, W, Cmat, h0, hT))]
+    spec += [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)] + [(n, g, ALWAYS) for n, g in zip(GATE_NAMES, gates)]
+    return _step(tc, valid_tokens, x, lengths, labels, spec, call)
 
 
-class _OnehotTTrainStep(torch.autograd.Function):
+def _onehot_t_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens):
     """The onehot i-FST and the onehot independent=1 step: the same weights T, W, O, h0, hT and the one gradient dT; which
     library step runs is the context's (OnehotTrainContext or Ind1TrainContext)."""
-    @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, W, O, h0, hT, T):
-        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T, ntok, x, lengths, labels)
-        B, L = x.shape
-        ws = {n: _f32(t) for n, t in (('T', T), ('W', W), ('O', O), ('h0', h0), ('hT', hT))}
-        Pc = _f32(P)
-        dT = torch.empty_like(ws['T'])
-        weights = {n: t.data_ptr() for n, t in ws.items()}
-        weights['P'] = None if Pc is None else Pc.data_ptr()
-        outputs = {'loss': loss.data_ptr(), 'dT': dT.data_ptr(), 'tags': tags.data_ptr()}
-        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                torch.cuda.current_stream(dev).cuda_stream)
-        ctx.save_for_backward(dT)
-        ctx.mark_non_differentiable(tags)
-        return loss.reshape(()), tags
-
-    @staticmethod
-    def backward(ctx, gloss, _gtags):
-        dT, = ctx.saved_tensors
-        return (None,) * 10 + (dT * gloss,)
+    return _step(tc, valid_tokens, x, lengths, labels,
+                 [('T', T, ALWAYS)] + [(n, t, NEVER) for n, t in (('W', W), ('O', O), ('h0', h0), ('hT', hT), ('P', P))])
 
 
 def onehot_ifst_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens=None):
     """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W, O, h0, hT and P are read
     but receive no gradient (the reference's requires_grad=False, model_onehot.py:326-337).  valid_tokens: the sum of
     the clamped lengths if the caller already has it."""
-    return _OnehotTTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
-
-
-class _OnehotFst4TrainStep(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, h0, hT, T4, W4):
-        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(T4, ntok, x, lengths, labels)
-        B, L = x.shape
-        ws = {n: _f32(t) for n, t in (('T4', T4), ('W4', W4), ('h0', h0), ('hT', hT))}
-        Pc = _f32(P)
-        dT4 = torch.empty_like(ws['T4'])
-        dW4 = torch.empty_like(ws['W4']) if W4.requires_grad else None
-        weights = {n: t.data_ptr() for n, t in ws.items()}
-        weights['P'] = None if Pc is None else Pc.data_ptr()
-        outputs = {'loss': loss.data_ptr(), 'dT4': dT4.data_ptr(), 'dW4': None if dW4 is None else dW4.data_ptr(),
-                   'tags': tags.data_ptr()}
-        tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                torch.cuda.current_stream(dev).cuda_stream)
-        ctx.has_w = dW4 is not None
-        ctx.save_for_backward(*([dT4] + ([dW4] if dW4 is not None else [])))
-        ctx.mark_non_differentiable(tags)
-        return loss.reshape(()), tags
-
-    @staticmethod
-    def backward(ctx, gloss, _gtags):
-        saved = ctx.saved_tensors
-        return (None,) * 8 + (saved[0] * gloss, saved[1] * gloss if ctx.has_w else None)
+    return _onehot_t_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens)
 
 
 def onehot_fst4_train_step(tc, T4, W4, h0, hT, P, x, lengths, labels, valid_tokens=None):
     """Returns (loss scalar tensor with grad towards T4 and, if it requires grad, W4; tags int32 [B,L] with -1 at pads).
     h0, hT and P are read but receive no gradient (model_onehot.py:32-33)."""
-    return _OnehotFst4TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, h0, hT, T4, W4)
+    return _step(tc, valid_tokens, x, lengths, labels,
+                 [('T4', T4, ALWAYS), ('W4', W4, IF_REQUIRED), ('h0', h0, NEVER), ('hT', hT, NEVER), ('P', P, NEVER)])
 
 
 def onehot_ind1_train_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens=None):
     """Returns (loss scalar tensor with grad towards T, tags int32 [B,L] with -1 at pads).  W [S,S], O [C,S,S], h0, hT and
     P are read but receive no gradient (the reference's requires_grad=False, model_onehot.py:209-223).  Whether the chains
     run on (T + W) * O.sum(0) (args.independent == 2) is the context's mask_by_output."""
-    return _OnehotTTrainStep.apply(tc, valid_tokens, x, lengths, labels, P, W, O, h0, hT, T)
+    return _onehot_t_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens)
 
 
 _D1_NAMES = ('Vgen', 'S1', 'S2', 'W', 'C', 'S1o', 'S2o', 'h0', 'hT')
 _D1_OPTIONAL = ('W', 'C', 'S1o', 'S2o', 'h0', 'hT')       # gradients the library writes only when asked (include/farnn.h)
-
-
-class _DecompInd1TrainStep(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tc, ntok, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, trans):
-        dev, ntok, x, lengths, labels, loss, tags = _step_inputs(S1, ntok, x, lengths, labels)
-        B, L = x.shape
-        ts = dict(zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT)))
-        ws = {n: _f32(t) for n, t in ts.items()}
-        Pc, tr = _f32(P), _f32(trans)
-        grads = {n: torch.empty_like(ws[n]) for n in _D1_NAMES if n not in _D1_OPTIONAL or ts[n].requires_grad}
-        weights = {n: t.data_ptr() for n, t in ws.items()}
-        weights['P'] = None if Pc is None else Pc.data_ptr()
-        outputs = {'d' + n: (grads[n].data_ptr() if n in grads else None) for n in _D1_NAMES}
-        outputs['loss'] = loss.data_ptr()
-        outputs['tags'] = tags.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if tr is None:
-            tc.step(weights, x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs, stream)
-        else:
-            if tuple(tr.shape) != (Cout.shape[0],) * 2:
-                raise ValueError('CRF transitions must be [C, C] = {}, not {}'.format((Cout.shape[0],) * 2, tuple(tr.shape)))
-            grads['trans'] = torch.empty_like(tr)
-            tc.step_crf(weights, tr.data_ptr(), x.data_ptr(), lengths.data_ptr(), labels.data_ptr(), B, L, ntok, outputs,
-                        grads['trans'].data_ptr(), stream)
-        ctx.have = tuple(n in grads for n in _D1_NAMES + ('trans',))
-        ctx.save_for_backward(*[grads[n] for n in _D1_NAMES + ('trans',) if n in grads])
-        ctx.mark_non_differentiable(tags)
-        return loss.reshape(()), tags
-
-    @staticmethod
-    def backward(ctx, gloss, _gtags):
-        saved = iter(ctx.saved_tensors)
-        return (None,) * 6 + tuple(next(saved) * gloss if h else None for h in ctx.have)
 
 
 def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, lengths, labels, valid_tokens=None,
@@ -237,4 +161,11 @@ def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, le
     C_output, S1_output, S2_output, h0 and hT get one when they require it and None otherwise.  P is read only.
     crf_trans [C,C] (C counts START and STOP): the loss is the CRF's negative log-likelihood, a sum over the sequences, the
     tags are the Viterbi path, and crf_trans gets a gradient (farnn_decomp_ind1_crf_train_step)."""
-    return _DecompInd1TrainStep.apply(tc, valid_tokens, x, lengths, labels, P, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, crf_trans)
+    call = None
+    if crf_trans is not None:
+        def call(weights, ptrs, dims, outputs, stream):
+            if tuple(crf_trans.shape) != (Cout.shape[0],) * 2:
+                raise ValueError('CRF transitions must be [C, C] = {}, not {}'.format((Cout.shape[0],) * 2, tuple(crf_trans.shape)))
+            tc.step_crf(weights, weights['crf_trans'], *ptrs, *dims, outputs, outputs['dtrans'], stream)
+    spec = [(n, t, IF_REQUIRED if n in _D1_OPTIONAL else ALWAYS) for n, t in zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT))]
+    return _step(tc, valid_tokens, x, lengths, labels, spec + [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)], call)

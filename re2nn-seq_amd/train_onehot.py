@@ -66,25 +66,24 @@ def check_trainable(model):
     """Refuses a model the HIP training step does not cover (raises NotImplementedError; no device work)."""
     if not hasattr(model, 'enable_training'):
         raise no_training_step(model)
-    from .farnn.model_onehot import FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S
-    from .farnn.model_decompose_independent import FARNN_S_D_W_I
-    if isinstance(model, (FARNN_S_O, FARNN_S_O_I, FARNN_S_O_I_S, FARNN_S_D_W_I)):
+    from .farnn._trainable import Trainable
+    if isinstance(model, Trainable) and not model._check_needs_re_tags:      # FARNN_S_D_W_I_S checks in forward_local(re_tags=...)
         model._check_trainable()                  # max semiring, CRF extension, several GPUs; a model without its opt-in
 
 
 def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
     """The epoch loop of the reference (train_decompose.py:161-221): forward_local(train=True), loss.backward(),
     optimizer.step() per batch, then the three evaluations and the best-model record."""
-    import os
     import time
 
     import torch
+    from .farnn._native import opted_in
     from .metrics.metrics import eval_seq_token, get_ner_fmeasure
 
     model.enable_training()                       # raises for the configurations the HIP training step does not cover
     params = list(model.parameters())
     optim = torch.optim
-    if os.environ.get('RE2NN_NATIVE_OPTIM', '') == '1':      # opt-in: the library's one-launch optimizer step (DESIGN.md, row f6)
+    if opted_in('NATIVE_OPTIM'):                  # opt-in: the library's one-launch optimizer step (DESIGN.md, row f6)
         from .farnn import optim
     if args.optimizer == 'SGD':
         optimizer = optim.SGD(params, lr=args.lr, weight_decay=0)

@@ -39,6 +39,7 @@ def main():
     a = ap.parse_args()
     import torch
     from re2nn_seq_amd import _lib, synth
+    from re2nn_seq_amd.farnn._native import opted_in
     from re2nn_seq_amd.farnn.train_step import onehot_ifst_train_step
     V, S, C, B, L = 950, a.states, 128, 256, 64
     rng = np.random.RandomState(1234)
@@ -62,7 +63,7 @@ def main():
     tc = _lib.OnehotTrainContext(V, S, C, nl='none', device=0)
     if a.semiring != 'sum':
         tc.set_semiring(a.semiring)
-    native = os.environ.get('RE2NN_NATIVE_OPTIM', '') == '1'      # as train_onehot.train_epochs picks its optimizer
+    native = opted_in('NATIVE_OPTIM')      # as train_onehot.train_epochs picks its optimizer
     if native:
         from re2nn_seq_amd.farnn import optim
     else:
