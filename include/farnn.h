@@ -682,6 +682,39 @@ int  farnn_decomp_ind1_crf_train_step(farnn_decomp_ind1_train_ctx *ctx, const fa
                                       const float *crf_trans /* [C][C] */, const int64_t *x, const int64_t *lengths,
                                       const int64_t *labels, int32_t B, int32_t L, int64_t valid_tokens,
                                       const farnn_decomp_ind1_train_outputs *out, float *dtrans /* [C][C] */, void *stream);
+/* The same step for the gated model (--farnn 1 | 2), on the same context.  One chain step, with v = Vgen[w], k =
+ * sigmoid_exponent, h the previous state and h_init = h0 (forward chain) or hT (backward chain)
+ * (model_decompose_independent.py:148-197):
+ *   z = sigmoid(k (h Wss1 + v Wrs1 + bs1));  farnn 2: r = sigmoid(k (h Wss2 + v Wrs2 + bs2)), hbar = (1 - r) h_init + r h
+ *   (farnn 1: hbar = h);  y = nl(hbar Mc[w]) (backward chain: hbar Mc[w]^T; the gates read Wss untransposed in both chains);
+ *   h' = (1 - z) h + z y.
+ * The scores read the gated states; the score, the priority layer, the loss and the decode are the plain step's.  Beside the
+ * gradients of `out` (dVgen with the gates' share; dh0 / dhT with the (1 - r) share of every step of every sequence and what
+ * the first step carries back) the step writes the gates' gradients in full.
+ * crf_trans / dtrans: both NULL for the CE1 loss, both given for --use_crf 1 (as farnn_decomp_ind1_crf_train_step).
+ * FARNN_EINVAL, before anything is enqueued and with the outputs untouched: farnn not 1 or 2, a NULL gate pointer (weight or
+ * gradient) that farnn needs, sigmoid_exponent <= 0, only one of crf_trans / dtrans, a context in the max semiring (the gated
+ * chains are built for the sum semiring).  FARNN_ERANGE likewise: the LDS of the chain kernels -- the gate matrices, farnn S S
+ * floats, and a sequence's L + 1 tokens -- beyond 160 KiB (S = 128, farnn 2: L <= 4600).  No float atomics: two steps on the
+ * same inputs are bit-identical. */
+typedef struct {
+    int32_t farnn;                          /* 1 or 2 (:160-169)                                   */
+    const float *Wss1, *Wrs1, *bs1;         /* [S][S], [R][S], [S] (:102-104, :112-119)            */
+    const float *Wss2, *Wrs2, *bs2;         /* the same for r, farnn 2 only (NULL otherwise) (:120-126) */
+    float sigmoid_exponent;                 /* k > 0 (model_decompose.py:97-102)                   */
+} farnn_decomp_ind1_gate_weights;
+
+typedef struct {
+    float *dWss1, *dWrs1, *dbs1;            /* [S][S], [R][S], [S]                                 */
+    float *dWss2, *dWrs2, *dbs2;            /* farnn 2 only (NULL otherwise)                       */
+} farnn_decomp_ind1_gate_outputs;
+
+int  farnn_decomp_ind1_gated_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_decomp_ind1_train_weights *w,
+                                        const farnn_decomp_ind1_gate_weights *g, const float *crf_trans /* [C][C] or NULL */,
+                                        const int64_t *x, const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                        int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *out,
+                                        const farnn_decomp_ind1_gate_outputs *gout, float *dtrans /* [C][C] or NULL */,
+                                        void *stream);
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);

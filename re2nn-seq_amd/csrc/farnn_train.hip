@@ -21,6 +21,7 @@
 #include "fst4_train.hip.h"
 #include "ind1_train.hip.h"
 #include "decomp1_train.hip.h"
+#include "decomp1_gated_train.hip.h"
 #include "train_bucketed_crf.hip.h"
 #include "optim.hip.h"
 
@@ -936,8 +937,16 @@ struct Decomp1Step : BucketedStep<farnn_decomp_ind1_train_ctx, farnn_decomp_ind1
     bool crf;
     const float *crf_trans; float *dtrans;
     BucketedCrf cs;
+    // farnn_decomp_ind1_gated_train_step: the gated chains, their back-propagation and the gates' gradients in the plain stages'
+    // place (decomp1_gated_train.hip.h); null for every other entry
+    const farnn_decomp_ind1_gate_weights *gw; const farnn_decomp_ind1_gate_outputs *go;
+    D1GateParams gp;
+    size_t lds_gate;
+    float *GV1, *GV2, *dGV1, *dGV2, *GT1, *GT2;
     float *BR, *DBR, *Nw, *dN, *Kfac, *Ofac, *E, *Osum, *dOsum, *zero, *csum, *dcsum, *fpart, *HP;
     size_t carve_ws(float *base);
+    void carve_gates(Carver<float> &a);
+    int gated_chains(); int gated_bptt(); int gated_dM_words(); int gate_gradients();
     int validate(); int plan(int B, int L);
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int gemm(const float *A, size_t am, size_t ak, const float *Bm, size_t bk_, size_t bn, float *Cm, size_t ldc, size_t M_, size_t N_,
@@ -961,7 +970,17 @@ size_t Decomp1Step::carve_ws(float *base) {
     HP = a.take((size_t)B * 2 * S);                               // the sequences' shares of dh0 / dhT
     carve_max(a);
     if (crf) cs.carve(a, B, L, K, w->P != nullptr);               // (behind everything the plain step lays out)
+    if (gw) carve_gates(a);                                       // (and so is the gated step's)
     return a.off;
+}
+// the gated step's own arrays: the chains' stash of z, r, y and hbar, the gates' pre-activation adjoints, the input halves
+// GV = Vgen Wrs + bs and their adjoints per word, the gates' share of dVgen
+void Decomp1Step::carve_gates(Carver<float> &a) {
+    const size_t nS2 = 2 * N1 * S, two = gw->farnn == 2;
+    gp.Z = a.take(nS2); gp.Y = a.take(nS2); gp.DAZ = a.take(nS2);
+    gp.Rg = a.take(two * nS2); gp.HB = a.take(two * nS2); gp.DAR = a.take(two * nS2);
+    GV1 = a.take(V * S); dGV1 = a.take(V * S); GT1 = a.take(V * R);
+    GV2 = a.take(two * V * S); dGV2 = a.take(two * V * S); GT2 = a.take(two * V * R);
 }
 // Stage 1: the arguments
 int Decomp1Step::validate() {
@@ -975,6 +994,17 @@ int Decomp1Step::plan(int B_, int L_) {
     if (int rc = plan_bucketed(name, B_, L_, RO, ind1_train_lds_floats)) return rc;
     if (crf)
         if (int rc = BucketedCrf::plan_check(name, K, L)) return rc;
+    if (gw) {
+        if (gw->farnn != 1 && gw->farnn != 2) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: farnn must be 1 or 2%s%s");
+        if (!gw->Wss1 || !gw->Wrs1 || !gw->bs1 || !go->dWss1 || !go->dWrs1 || !go->dbs1 ||
+            (gw->farnn == 2 && (!gw->Wss2 || !gw->Wrs2 || !gw->bs2 || !go->dWss2 || !go->dWrs2 || !go->dbs2)))
+            return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: a gate weight or gate gradient of this farnn is null%s%s");
+        if (!(gw->sigmoid_exponent > 0.0f)) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: sigmoid_exponent must be positive%s%s");
+        if (mx) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: the context is in the max semiring; the gated chains are built for the sum semiring only%s%s");
+        lds_gate = decomp1_gated_lds_bytes(S, gw->farnn, L);
+        if (lds_gate + D1G_STATIC_LDS > 160 * 1024)
+            return fail(FARNN_ERANGE, "decomp_ind1_gated_train_step: the gate matrices (farnn S S floats) and a sequence's L + 1 tokens need more than 160 KiB of LDS%s%s");
+    }
     need = carve_ws(nullptr);
     return FARNN_OK;
 }
@@ -996,6 +1026,10 @@ int Decomp1Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *
     // max semiring: UF / DQ hold dM entries, not adjoint rows -- BPTT itself carries on into row 0 (onehot_max_bptt_carry_kernel)
     if (mx && (o->dh0 || o->dhT)) carry0 = HP;
     if (crf) cs.fill(crf_trans, w->P, SC, DS, lengths, labels_, o->tags, c->err.dev, B, L, K, c->d.o_idx, c->d.threshold);
+    if (gw) {
+        gp.Wss1 = gw->Wss1; gp.Wss2 = gw->Wss2; gp.GV1 = GV1; gp.GV2 = GV2; gp.HP = HP;
+        gp.farnn = gw->farnn; gp.k = gw->sigmoid_exponent;
+    }
     return FARNN_OK;
 }
 // C[m][n] = sum_k A[m am + k ak] B[k bk + n bn] (+ add[n]); rows: the rows read as zero (decomp1_gemm_kernel)
@@ -1021,6 +1055,47 @@ int Decomp1Step::prepare() {
     if ((rc = gemm(w->Vgen, R, 1, Kfac, SS, 1, Nw, SS, V, SS, R, w->W, bk.wcount))) return rc;
     const unsigned nt = (unsigned)((S + 31) / 32);
     ind1_premix_kernel<<<dim3((unsigned)V, nt * nt), 256, 0, s>>>(Nw, zero, Osum, bk.wcount, M, MT, (int)S);
+    if (!gw) return FARNN_OK;
+    // the gated step: the gates' input halves GV = Vgen Wrs + bs for the batch's words; the gates' adjoint rows cleared (row 0
+    // and the pad rows stay zero: the products over every row read them)
+    const size_t nS2 = 2 * N1 * S;
+    FARNN_HIP_TRY(hipMemsetAsync(gp.DAZ, 0, nS2 * sizeof(float), s));
+    if (gw->farnn == 2) FARNN_HIP_TRY(hipMemsetAsync(gp.DAR, 0, nS2 * sizeof(float), s));
+    if ((rc = gemm(w->Vgen, R, 1, gw->Wrs1, S, 1, GV1, S, V, S, R, gw->bs1, bk.wcount))) return rc;
+    if (gw->farnn == 2 && (rc = gemm(w->Vgen, R, 1, gw->Wrs2, S, 1, GV2, S, V, S, R, gw->bs2, bk.wcount))) return rc;
+    return FARNN_OK;
+}
+// Stages 6 and 10 of the gated step: decomp1_gated_chain_kernel / decomp1_gated_bptt_kernel in launch_onehot_chains' place
+int Decomp1Step::gated_chains() {
+    return with_chain_slots(S, [&](auto RS) { return launch(decomp1_gated_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_gate, s, q, gp); });
+}
+int Decomp1Step::gated_bptt() {
+    return with_chain_slots(S, [&](auto RS) { return launch(decomp1_gated_bptt_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_gate, s, q, gp); });
+}
+// Stage 11 of the gated step: dMc[w] with hbar as the row factor (farnn 2: its stash in the state stash's place; farnn 1: hbar
+// is the state) and back-propagation's u in UF / DQ as the column factor
+int Decomp1Step::gated_dM_words() {
+    OhTrainParams qd = q;
+    if (gw->farnn == 2) { qd.A = gp.HB; qd.Bk = gp.HB + N1 * S; }
+    return launch_onehot_dT(qd, bk, dM, partial, s);
+}
+// The gates stage, behind factors(): the words' dGV in bucket order, dWrs = Vgen^T dGV, dbs = sum_w dGV[w], dVgen += dGV Wrs^T,
+// dWss = H^T DAZ over every row of both chains' state stash (A and Bk are neighbours; DAZ shifted by one row)
+int Decomp1Step::gate_gradients() {
+    int rc;
+    const size_t nS = N1 * S;
+    const bool two = gw->farnn == 2;
+    assert(q.Bk == q.A + nS);
+    decomp1_gate_word_kernel<<<dim3((unsigned)V, two ? 2 : 1), 128, 0, s>>>(gp.DAZ, gp.DAR, q.len, bk.list, bk.wstart, bk.wcount, dGV1,
+                                                                             dGV2, L, (int)S, nS);
+    decomp1_gate_bias_kernel<<<two ? 2 : 1, 128, 0, s>>>(dGV1, dGV2, go->dbs1, go->dbs2, (int)V, (int)S);
+    if ((rc = gemm(w->Vgen, 1, R, dGV1, S, 1, go->dWrs1, S, R, S, V)) ||
+        (rc = gemm(dGV1, S, 1, gw->Wrs1, 1, S, GT1, R, V, R, S)) ||
+        (rc = gemm(q.A, 1, S, gp.DAZ + S, S, 1, go->dWss1, S, S, S, 2 * N1 - 1))) return rc;
+    if (two && ((rc = gemm(w->Vgen, 1, R, dGV2, S, 1, go->dWrs2, S, R, S, V)) ||
+                (rc = gemm(dGV2, S, 1, gw->Wrs2, 1, S, GT2, R, V, R, S)) ||
+                (rc = gemm(q.A, 1, S, gp.DAR + S, S, 1, go->dWss2, S, S, S, 2 * N1 - 1)))) return rc;
+    decomp1_gate_add_kernel<<<(unsigned)((V * R + 255) / 256), 256, 0, s>>>(o->dVgen, GT1, two ? GT2 : nullptr, V * R);
     return FARNN_OK;
 }
 // Stages 7 and 9: ind1_train_kernel in bucket order over the output ranks (MODE 0: br, 1: the partials of d alpha / d beta)
@@ -1055,7 +1130,7 @@ int Decomp1Step::factors() {
         (rc = gemm(w->Vgen, 1, R, dN, SS, 1, E, SS, R, SS, V))) return rc;                     // E[r] = sum_w v_r[w] dN[w]
     decomp1_in_factors_kernel<<<(unsigned)R, 128, 0, s>>>(E, w->S1, w->S2, o->dS1, o->dS2, (int)S, (int)R);
     if (o->dh0 || o->dhT) {
-        if (!mx) decomp1_init_adj_kernel<<<(unsigned)B, 128, 0, s>>>(q, HP);
+        if (!mx && !gw) decomp1_init_adj_kernel<<<(unsigned)B, 128, 0, s>>>(q, HP);      // (the gated BPTT wrote HP itself)
         decomp1_init_sum_kernel<<<1, 128, 0, s>>>(HP, o->dh0, o->dhT, B, (int)S);
     }
     return FARNN_OK;
@@ -1063,6 +1138,12 @@ int Decomp1Step::factors() {
 // Stages 4 to 13 (6 and 10: both chains, with the state stash, then back-propagation through time)
 int Decomp1Step::stages() {
     int rc;
+    if (gw) {
+        if ((rc = prepare()) || (rc = gated_chains()) || (rc = scores<0>()) || (rc = loss()) ||
+            (rc = adjoints([&] { return scores<1>(); })) || (rc = gated_bptt()) || (rc = gated_dM_words()) || (rc = back()) ||
+            (rc = factors())) return rc;
+        return gate_gradients();
+    }
     if ((rc = prepare()) || (rc = chains<false>()) || (rc = scores<0>()) || (rc = loss()) ||
         (rc = adjoints([&] { return scores<1>(); })) || (rc = chains<true>()) || (rc = dM_words()) || (rc = back())) return rc;
     return factors();
@@ -1080,6 +1161,19 @@ extern "C" int farnn_decomp_ind1_crf_train_step(farnn_decomp_ind1_train_ctx *c, 
     if (!crf_trans || !dtrans) return fail(FARNN_EINVAL, "decomp_ind1_train_crf_step: CRF transitions / their gradient missing%s%s");
     return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
                                        [&](Decomp1Step &t) { t.crf = true; t.crf_trans = crf_trans; t.dtrans = dtrans; });
+}
+extern "C" int farnn_decomp_ind1_gated_train_step(farnn_decomp_ind1_train_ctx *c, const farnn_decomp_ind1_train_weights *w,
+                                                  const farnn_decomp_ind1_gate_weights *g, const float *crf_trans, const int64_t *x,
+                                                  const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                                  int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *o,
+                                                  const farnn_decomp_ind1_gate_outputs *go, float *dtrans, void *stream) {
+    if (!g || !go) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: null gate weights / gate outputs%s%s");
+    if ((crf_trans == nullptr) != (dtrans == nullptr))
+        return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: CRF transitions and their gradient go together (both or neither)%s%s");
+    return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream, [&](Decomp1Step &t) {
+        t.gw = g; t.go = go;
+        if (crf_trans) { t.crf = true; t.crf_trans = crf_trans; t.dtrans = dtrans; }
+    });
 }
 
 // ---- the optimizer step (farnn_optim_*; optim.hip.h) -------------------------------------------------------------------

@@ -3,7 +3,8 @@
 rank-R_O output tensor (C_output, S1_output, S2_output).  Same constructor arguments and state-dict
 keys as the reference; inference runs in the HIP library (farnn_decomp_ind1_create).
 Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step; with --use_crf 1
-(RE2NN_DECOMP_IND1_CRF_TRAIN=1 beside it): farnn_decomp_ind1_crf_train_step.
+(RE2NN_DECOMP_IND1_CRF_TRAIN=1 beside it): farnn_decomp_ind1_crf_train_step; with --farnn 1 | 2
+(RE2NN_DECOMP_IND1_GATED_TRAIN=1 beside it, sum semiring): farnn_decomp_ind1_gated_train_step, with or without the CRF.
 """
 import numpy as np
 import torch
@@ -118,10 +119,11 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
             raise no_training_step(self)
         a = self.args
         why = None
-        if a.farnn != 0:
+        gated = a.farnn != 0
+        if gated and not (a.farnn in (1, 2) and opted_in('DECOMP_IND1_GATED_TRAIN')):
             why = 'the gated recurrences (--farnn {})'.format(a.farnn)
-        elif a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled()):
-            why = 'the max semiring (--train_mode {})'.format(a.train_mode)
+        elif a.train_mode != 'sum' and (gated or not (a.train_mode == 'max' and bucketed_max_train_enabled())):
+            why = 'the max semiring (--train_mode {})'.format(a.train_mode)      # (the gated chains: the sum semiring only)
         elif a.use_crf and not opted_in('DECOMP_IND1_CRF_TRAIN'):
             why = 'the CRF (--use_crf 1)'
         elif a.local_loss_func != 'CE1':
@@ -144,8 +146,13 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
                                         threshold=self.args.threshold, o_idx=self.o_idx, device=self.device_index,
                                         semiring=self._semiring())
 
+    # (the gates of --farnn 1 | 2 -- Wss1, Wrs1, bs1, then Wss2, Wrs2, bs2 -- and crf.transitions follow _TRAIN_FLAGS in
+    #  FARNN_S_D_W_I_S._train_decl: always trainable, present only for the model's farnn; _copy_back writes them back by name)
     def _train_call(self, x, lengths, lab, ntok, re_tags):
         tp = self._tp
+        farnn = int(self.args.farnn)
         return train_step.decomp_ind1_train_step(self._tc, self._train_vgen(), tp['S1'], tp['S2'], tp['wildcard_mat'],
                                                  tp['C_output'], tp['S1_output'], tp['S2_output'], tp['h0'], tp['hT'], self._tpP,
-                                                 x, lengths, lab, valid_tokens=ntok, crf_trans=tp.get('crf.transitions'))
+                                                 x, lengths, lab, valid_tokens=ntok, crf_trans=tp.get('crf.transitions'),
+                                                 gates=tuple(tp[k] for k in _GATE_KEYS[:3 * farnn]),
+                                                 sigmoid_exponent=float(self.args.sigmoid_exponent))

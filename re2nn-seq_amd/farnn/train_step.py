@@ -29,6 +29,8 @@ The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.p
 for f3 through torch's autograd, and one library call (farnn_decomp_ind1_train_step) for the loss, the tags and the gradients of
 Vgen, S1, S2, wildcard_mat, C_output, S1_output, S2_output, h0 and hT.  Under --use_crf 1 (crf_trans given) the call is
 farnn_decomp_ind1_crf_train_step: the CRF's negative log-likelihood, the Viterbi tags and the transitions' gradient as well.
+With the gates of --farnn 1 | 2 (gates=...) the call is farnn_decomp_ind1_gated_train_step, with or without crf_trans: the
+gates' gradients as well.
 """
 import torch
 
@@ -154,18 +156,28 @@ _D1_OPTIONAL = ('W', 'C', 'S1o', 'S2o', 'h0', 'hT')       # gradients the librar
 
 
 def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, lengths, labels, valid_tokens=None,
-                           crf_trans=None):
+                           crf_trans=None, gates=(), sigmoid_exponent=5.0):
     """The decomposed independent=1 model (FARNN_S_D_W_I, model_decompose_independent.py:219-300): returns
     (loss scalar tensor with grad, tags int32 [B,L] with -1 at pads).  Vgen [V,R] (its gradient flows on through torch's
     autograd to V_embed, embed_r_generalized, embedding.weight and beta_vec), S1 and S2 always get a gradient; wildcard_mat W,
     C_output, S1_output, S2_output, h0 and hT get one when they require it and None otherwise.  P is read only.
     crf_trans [C,C] (C counts START and STOP): the loss is the CRF's negative log-likelihood, a sum over the sequences, the
-    tags are the Viterbi path, and crf_trans gets a gradient (farnn_decomp_ind1_crf_train_step)."""
+    tags are the Viterbi path, and crf_trans gets a gradient (farnn_decomp_ind1_crf_train_step).
+    gates: as decomp_ifst_train_step's -- Wss1, Wrs1, bs1 (farnn = 1) followed by Wss2, Wrs2, bs2 (farnn = 2); with them the
+    call is farnn_decomp_ind1_gated_train_step (with or without crf_trans), every gate gets a gradient, and sigmoid_exponent is
+    the gates' k."""
     call = None
-    if crf_trans is not None:
+    if len(gates) not in (0, 3, 6):
+        raise ValueError('gates: none, Wss1 Wrs1 bs1 (farnn 1) or those and Wss2 Wrs2 bs2 (farnn 2), not {} tensors'.format(len(gates)))
+    if crf_trans is not None or gates:
         def call(weights, ptrs, dims, outputs, stream):
-            if tuple(crf_trans.shape) != (Cout.shape[0],) * 2:
+            if crf_trans is not None and tuple(crf_trans.shape) != (Cout.shape[0],) * 2:
                 raise ValueError('CRF transitions must be [C, C] = {}, not {}'.format((Cout.shape[0],) * 2, tuple(crf_trans.shape)))
-            tc.step_crf(weights, weights['crf_trans'], *ptrs, *dims, outputs, outputs['dtrans'], stream)
+            if gates:
+                tc.gated_step(weights, len(gates) // 3, sigmoid_exponent, *ptrs, *dims, outputs, stream,
+                              trans_ptr=weights.get('crf_trans'), dtrans_ptr=outputs.get('dtrans'))
+            else:
+                tc.step_crf(weights, weights['crf_trans'], *ptrs, *dims, outputs, outputs['dtrans'], stream)
     spec = [(n, t, IF_REQUIRED if n in _D1_OPTIONAL else ALWAYS) for n, t in zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT))]
-    return _step(tc, valid_tokens, x, lengths, labels, spec + [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)], call)
+    spec += [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)] + [(n, g, ALWAYS) for n, g in zip(GATE_NAMES, gates)]
+    return _step(tc, valid_tokens, x, lengths, labels, spec, call)

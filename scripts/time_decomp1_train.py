@@ -10,12 +10,14 @@ lengths, rotating through four batches of the same lengths.  Prints one JSON lin
   result_sha          sha256 over the loss and every gradient of the last timed step (bytes): two builds whose plain step
                       shares every kernel must print the same one
 
-    python scripts/time_decomp1_train.py [--steps 10] [--warmup 2] [--stages 1] [--use_crf 1] [--parent_lib 1]
+    python scripts/time_decomp1_train.py [--steps 10] [--warmup 2] [--stages 1] [--use_crf 1] [--farnn 1|2] [--parent_lib 1]
 
 --use_crf 1: farnn_decomp_ind1_crf_train_step with the same 73 labels (the score width becomes 75: START and STOP; the
 transitions are the reference's initial ones plus seeded noise in (-0.5, 0.5) where they are not -10000).
---parent_lib 1: the library named by FARNN_LIB is a build of an earlier commit without the CRF entry point (its binding is
-dropped before the library is loaded); for the plain step only.
+--farnn 1 | 2: farnn_decomp_ind1_gated_train_step with seeded gates (Wss ~ N(0, 0.3^2 / S), Wrs ~ N(0, 0.3^2 / R), bs ~
+N(0, 0.2^2), sigmoid_exponent 5: the sigmoids stay off saturation), drawn after everything the plain step draws.
+--parent_lib 1: the library named by FARNN_LIB is a build of an earlier commit without the CRF or the gated entry point (their
+bindings are dropped before the library is loaded); for the plain step only.
 
 The line carries no rate: none was measured.  Each GPU step of a job script runs it under its own time limit
 (timeout -k 10 ...)."""
@@ -38,13 +40,15 @@ def main():
     ap.add_argument('--train_mode', choices=('sum', 'max'), default='sum')       # the semiring of the chains
     ap.add_argument('--stages', type=int, default=1)
     ap.add_argument('--use_crf', type=int, default=0)
+    ap.add_argument('--farnn', type=int, choices=(0, 1, 2), default=0)
     ap.add_argument('--parent_lib', type=int, default=0)
     a = ap.parse_args()
     import torch
     from re2nn_seq_amd import _lib, synth
     if a.parent_lib:
-        assert not a.use_crf, 'an earlier build has no CRF step'
+        assert not a.use_crf and not a.farnn, 'an earlier build has no CRF step and no gated step'
         _lib.SIGNATURES.pop('farnn_decomp_ind1_crf_train_step')
+        _lib.SIGNATURES.pop('farnn_decomp_ind1_gated_train_step')
     from re2nn_seq_amd.farnn.train_step import decomp_ind1_train_step
     V, S, C, R, RO, B, L = 11000, 104, 73, 50, 70, 256, 64
     rng = np.random.RandomState(1234)
@@ -75,13 +79,18 @@ def main():
     labd = [torch.from_numpy(v).to(dev) for v in labels]
     tc = _lib.Decomp1TrainContext(V, S, R, RO, C, nl='tanh', device=0, semiring=a.train_mode)
     td = None if trans is None else d(trans)
+    gr = np.random.RandomState(77)
+    gates = []
+    for _ in range(a.farnn):
+        gates += [d(gr.randn(S, S) * 0.3 / np.sqrt(S)), d(gr.randn(R, S) * 0.3 / np.sqrt(R)), d(gr.randn(S) * 0.2)]
+    more = dict(gates=tuple(gates), sigmoid_exponent=5.0) if gates else {}
 
     def one(i):
-        for t in ws:
+        for t in ws + gates:
             t.grad = None
         if td is not None:
             td.grad = None
-        loss, _ = decomp_ind1_train_step(tc, *ws, None, xd[i % 4], ld, labd[i % 4], valid_tokens=ntok, crf_trans=td)
+        loss, _ = decomp_ind1_train_step(tc, *ws, None, xd[i % 4], ld, labd[i % 4], valid_tokens=ntok, crf_trans=td, **more)
         loss.backward()
         return loss
 
@@ -97,7 +106,7 @@ def main():
         per.append(1e3 * ms / max(n, 1))
     tc.set_profiling(0)
     sha = hashlib.sha256(loss.detach().cpu().numpy().tobytes())
-    for t in ws + ([td] if td is not None else []):
+    for t in ws + ([td] if td is not None else []) + gates:
         sha.update(t.grad.cpu().numpy().tobytes())
     words = [int(len(np.unique(v[np.arange(L)[None, :] < lengths[:, None]]))) for v in xs]
     # the stamp of what was measured: sha256 over the library's sources (csrc/*.hip, csrc/*.h, include/farnn.h), names in order
@@ -109,7 +118,7 @@ def main():
             h.update(os.path.basename(path).encode() + b'\0' + fh.read())
     tree = h.hexdigest()[:16]
     out = {'shape': {'V': V, 'S': S, 'C': C, 'R': R, 'RO': RO, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok, 'train_mode': a.train_mode,
-           'steps': a.steps, 'use_crf': a.use_crf, 'result_sha': sha.hexdigest()[:16], 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
+           'steps': a.steps, 'use_crf': a.use_crf, 'farnn': a.farnn, 'result_sha': sha.hexdigest()[:16], 'lib_us_per_step': float(np.median(per)), 'lib_us_min': float(min(per)),
            'lib_us_max': float(max(per)), 'distinct_words': words, 'loss': float(loss.detach()), 'tree': tree}
     if a.stages:
         from torch.profiler import ProfilerActivity, profile
