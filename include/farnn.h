@@ -693,8 +693,9 @@ int  farnn_decomp_ind1_crf_train_step(farnn_decomp_ind1_train_ctx *ctx, const fa
  * the first step carries back) the step writes the gates' gradients in full.
  * crf_trans / dtrans: both NULL for the CE1 loss, both given for --use_crf 1 (as farnn_decomp_ind1_crf_train_step).
  * FARNN_EINVAL, before anything is enqueued and with the outputs untouched: farnn not 1 or 2, a NULL gate pointer (weight or
- * gradient) that farnn needs, sigmoid_exponent <= 0, only one of crf_trans / dtrans, a context in the max semiring (the gated
- * chains are built for the sum semiring).  FARNN_ERANGE likewise: the LDS of the chain kernels -- the gate matrices, farnn S S
+ * gradient) that farnn needs, sigmoid_exponent <= 0, only one of crf_trans / dtrans, a context in the max semiring (this entry
+ * runs the gated chains of the sum semiring; farnn_decomp_ind1_gated_max_train_step below runs those of the max semiring).
+ * FARNN_ERANGE likewise: the LDS of the chain kernels -- the gate matrices, farnn S S
  * floats, and a sequence's L + 1 tokens -- beyond 160 KiB (S = 128, farnn 2: L <= 4600).  No float atomics: two steps on the
  * same inputs are bit-identical. */
 typedef struct {
@@ -715,6 +716,25 @@ int  farnn_decomp_ind1_gated_train_step(farnn_decomp_ind1_train_ctx *ctx, const 
                                         int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *out,
                                         const farnn_decomp_ind1_gate_outputs *gout, float *dtrans /* [C][C] or NULL */,
                                         void *stream);
+/* The gated step on a context in the max semiring (--farnn 1 | 2 --train_mode max): the same arguments.  Only the block product
+ * goes through the semiring (model_decompose_independent.py:177-188, utils.py:192-195); the gate products stay matrix products:
+ *   z, r, hbar as above;  q[s] = max_j hbar[j] Mc[w][j,s] (backward chain: max_j hbar[j] Mc[w][s,j]) with j*[s] the FIRST
+ *   maximal j under IEEE comparison (-0 == +0; torch.max(dim=1));  y = nl(q);  h' = (1 - z) h + z y.
+ * Back-propagation sends a step's block adjoint u = dh' z nl'(y) to the winning index only: dMc[w] gets u[s] hbar[j*[s]] at
+ * (j*[s], s) (backward chain: (s, j*[s])), dhbar[j] = the sum over the s with j*[s] = j of u[s] times the winning entry, the
+ * states s ascending.  The gates' adjoints, the carry, dh0 / dhT (with the (1 - r) share and the carry into row 0) and every
+ * gradient downstream of dMc are farnn_decomp_ind1_gated_train_step's.  crf_trans / dtrans as there.
+ * FARNN_EINVAL, before anything is enqueued and with the outputs untouched: a context in the sum semiring, and that entry's
+ * other refusals (farnn not 1 or 2, a NULL gate pointer that farnn needs, sigmoid_exponent <= 0, only one of crf_trans /
+ * dtrans).  FARNN_ERANGE likewise: the same LDS bound (the kernels' static LDS is the sum kernels').  No float atomics: two
+ * steps on the same inputs are bit-identical, and the plain, CRF, gated and plain max steps on the same context return the
+ * same bits before and after one of these. */
+int  farnn_decomp_ind1_gated_max_train_step(farnn_decomp_ind1_train_ctx *ctx, const farnn_decomp_ind1_train_weights *w,
+                                            const farnn_decomp_ind1_gate_weights *g, const float *crf_trans /* [C][C] or NULL */,
+                                            const int64_t *x, const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                            int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *out,
+                                            const farnn_decomp_ind1_gate_outputs *gout, float *dtrans /* [C][C] or NULL */,
+                                            void *stream);
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_decomp_ind1_train_set_profiling(farnn_decomp_ind1_train_ctx *ctx, int32_t enable);
 int  farnn_decomp_ind1_train_time(farnn_decomp_ind1_train_ctx *ctx, double *total_ms, int64_t *steps);

@@ -236,6 +236,10 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                                      C.POINTER(Decomp1TrainOutputs), C.POINTER(Decomp1GateOutputs), C.c_void_p,
                                                      C.c_void_p]),
+    'farnn_decomp_ind1_gated_max_train_step': (C.c_int, [C.c_void_p, C.POINTER(Decomp1TrainWeights), C.POINTER(Decomp1GateWeights),
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                                         C.POINTER(Decomp1TrainOutputs), C.POINTER(Decomp1GateOutputs), C.c_void_p,
+                                                         C.c_void_p]),
     'farnn_decomp_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_decomp_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -763,7 +767,7 @@ class Decomp1TrainContext(_TrainContextBase):
               'farnn_decomp_ind1_crf_train_step')
 
     def gated_step(self, weights, farnn, sigmoid_exponent, x_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, stream=None,
-                   trans_ptr=None, dtrans_ptr=None):
+                   trans_ptr=None, dtrans_ptr=None, entry='farnn_decomp_ind1_gated_train_step'):
         """step() for the gated model (farnn_decomp_ind1_gated_train_step): `weights` holds Wss1 .. bs2 beside the plain step's
         weights and `outputs` dWss1 .. dbs2 beside its outputs (farnn = 1: the second gate's stay None); trans_ptr / dtrans_ptr
         as step_crf's, both None for the CE1 loss."""
@@ -772,10 +776,12 @@ class Decomp1TrainContext(_TrainContextBase):
         g = Decomp1GateWeights(int(farnn), *[(weights.get(k) or None) for k in ('Wss1', 'Wrs1', 'bs1', 'Wss2', 'Wrs2', 'bs2')],
                                float(sigmoid_exponent))
         go = Decomp1GateOutputs(*[outputs.get(k) for k in ('dWss1', 'dWrs1', 'dbs1', 'dWss2', 'dWrs2', 'dbs2')])
-        check(load().farnn_decomp_ind1_gated_train_step(self._raw, C.byref(w), C.byref(g), trans_ptr, x_ptr, len_ptr, labels_ptr,
-                                                        int(B), int(L), int(valid_tokens), C.byref(o), C.byref(go), dtrans_ptr,
-                                                        stream),
-              'farnn_decomp_ind1_gated_train_step')
+        check(getattr(load(), entry)(self._raw, C.byref(w), C.byref(g), trans_ptr, x_ptr, len_ptr, labels_ptr, int(B), int(L),
+                                     int(valid_tokens), C.byref(o), C.byref(go), dtrans_ptr, stream), entry)
+
+    def gated_max_step(self, *args, **kwargs):
+        """gated_step() on a max context (farnn_decomp_ind1_gated_max_train_step): the same arguments."""
+        self.gated_step(*args, entry='farnn_decomp_ind1_gated_max_train_step', **kwargs)
 
 
 class Optim:

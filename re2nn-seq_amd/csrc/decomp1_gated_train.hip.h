@@ -1,5 +1,7 @@
 // The gated recurrences (--farnn 1 | 2) of the decomposed independent=1 training step (FARNN_S_D_W_I; decomp1_train.hip.h has
 // everything that does not depend on the gates: N, Osum, Mc, the scores in factor space, the loss, the factor gradients).
+// The two chain kernels here are the sum semiring's; decomp1_gated_max_train.hip.h has the max semiring's, and shares
+// D1GateParams, the LDS sizes and the gates' gradient kernels below.
 //
 // Reference: FARNN_S_D_W_I.get_forward_score (model_decompose_independent.py:148-197; the gate parameters :100-131, Sigmoidal
 // model_decompose.py:97-102).  With v = Vgen[w], k = sigmoid_exponent, h the previous state and h_init = h0 (forward chain) or

@@ -22,6 +22,7 @@
 #include "ind1_train.hip.h"
 #include "decomp1_train.hip.h"
 #include "decomp1_gated_train.hip.h"
+#include "decomp1_gated_max_train.hip.h"
 #include "train_bucketed_crf.hip.h"
 #include "optim.hip.h"
 
@@ -940,6 +941,9 @@ struct Decomp1Step : BucketedStep<farnn_decomp_ind1_train_ctx, farnn_decomp_ind1
     // farnn_decomp_ind1_gated_train_step: the gated chains, their back-propagation and the gates' gradients in the plain stages'
     // place (decomp1_gated_train.hip.h); null for every other entry
     const farnn_decomp_ind1_gate_weights *gw; const farnn_decomp_ind1_gate_outputs *go;
+    // farnn_decomp_ind1_gated_max_train_step: the same on a max context, the chains and their back-propagation those of
+    // decomp1_gated_max_train.hip.h, dM_words the plain max step's
+    bool gmx;
     D1GateParams gp;
     size_t lds_gate;
     float *GV1, *GV2, *dGV1, *dGV2, *GT1, *GT2;
@@ -947,6 +951,7 @@ struct Decomp1Step : BucketedStep<farnn_decomp_ind1_train_ctx, farnn_decomp_ind1
     size_t carve_ws(float *base);
     void carve_gates(Carver<float> &a);
     int gated_chains(); int gated_bptt(); int gated_dM_words(); int gate_gradients();
+    int gated_max_chains(); int gated_max_bptt();
     int validate(); int plan(int B, int L);
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int gemm(const float *A, size_t am, size_t ak, const float *Bm, size_t bk_, size_t bn, float *Cm, size_t ldc, size_t M_, size_t N_,
@@ -968,9 +973,10 @@ size_t Decomp1Step::carve_ws(float *base) {
     carve_tail(a);
     fpart = a.take(V * RO * 2 * S);                             // the words' shares of dS1_output / dS2_output
     HP = a.take((size_t)B * 2 * S);                               // the sequences' shares of dh0 / dhT
-    carve_max(a);
+    if (!gw) carve_max(a);
     if (crf) cs.carve(a, B, L, K, w->P != nullptr);               // (behind everything the plain step lays out)
     if (gw) carve_gates(a);                                       // (and so is the gated step's)
+    if (gw) carve_max(a);                                         // (the gated max step's WIN / IDX: behind all of the above)
     return a.off;
 }
 // the gated step's own arrays: the chains' stash of z, r, y and hbar, the gates' pre-activation adjoints, the input halves
@@ -995,15 +1001,17 @@ int Decomp1Step::plan(int B_, int L_) {
     if (crf)
         if (int rc = BucketedCrf::plan_check(name, K, L)) return rc;
     if (gw) {
-        if (gw->farnn != 1 && gw->farnn != 2) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: farnn must be 1 or 2%s%s");
+        const char *entry = gmx ? "decomp_ind1_gated_max_train_step" : "decomp_ind1_gated_train_step";
+        if (gw->farnn != 1 && gw->farnn != 2) return fail(FARNN_EINVAL, "%s: farnn must be 1 or 2%s", entry);
         if (!gw->Wss1 || !gw->Wrs1 || !gw->bs1 || !go->dWss1 || !go->dWrs1 || !go->dbs1 ||
             (gw->farnn == 2 && (!gw->Wss2 || !gw->Wrs2 || !gw->bs2 || !go->dWss2 || !go->dWrs2 || !go->dbs2)))
-            return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: a gate weight or gate gradient of this farnn is null%s%s");
-        if (!(gw->sigmoid_exponent > 0.0f)) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: sigmoid_exponent must be positive%s%s");
-        if (mx) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: the context is in the max semiring; the gated chains are built for the sum semiring only%s%s");
+            return fail(FARNN_EINVAL, "%s: a gate weight or gate gradient of this farnn is null%s", entry);
+        if (!(gw->sigmoid_exponent > 0.0f)) return fail(FARNN_EINVAL, "%s: sigmoid_exponent must be positive%s", entry);
+        if (mx && !gmx) return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: the context is in the max semiring; the gated chains are built for the sum semiring only%s%s");
+        if (!mx && gmx) return fail(FARNN_EINVAL, "decomp_ind1_gated_max_train_step: the context is in the sum semiring; this entry runs the gated chains of the max semiring only%s%s");
         lds_gate = decomp1_gated_lds_bytes(S, gw->farnn, L);
         if (lds_gate + D1G_STATIC_LDS > 160 * 1024)
-            return fail(FARNN_ERANGE, "decomp_ind1_gated_train_step: the gate matrices (farnn S S floats) and a sequence's L + 1 tokens need more than 160 KiB of LDS%s%s");
+            return fail(FARNN_ERANGE, "%s: the gate matrices (farnn S S floats) and a sequence's L + 1 tokens need more than 160 KiB of LDS%s", entry);
     }
     need = carve_ws(nullptr);
     return FARNN_OK;
@@ -1072,6 +1080,14 @@ int Decomp1Step::gated_chains() {
 int Decomp1Step::gated_bptt() {
     return with_chain_slots(S, [&](auto RS) { return launch(decomp1_gated_bptt_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_gate, s, q, gp); });
 }
+// The same two stages on a max context: the index and winning-entry stash beside the gated stash, back-propagation to the
+// winning index only (it writes the steps' dMc entries for dM_words and HP itself)
+int Decomp1Step::gated_max_chains() {
+    return with_chain_slots(S, [&](auto RS) { return launch(decomp1_gated_max_chain_kernel<RS()>, dim3(B, 2), OT_THREADS, lds_gate, s, q, gp, mq); });
+}
+int Decomp1Step::gated_max_bptt() {
+    return launch(decomp1_gated_max_bptt_kernel, dim3(B, 2), OT_THREADS, lds_gate, s, q, gp, mq);
+}
 // Stage 11 of the gated step: dMc[w] with hbar as the row factor (farnn 2: its stash in the state stash's place; farnn 1: hbar
 // is the state) and back-propagation's u in UF / DQ as the column factor
 int Decomp1Step::gated_dM_words() {
@@ -1139,9 +1155,9 @@ int Decomp1Step::factors() {
 int Decomp1Step::stages() {
     int rc;
     if (gw) {
-        if ((rc = prepare()) || (rc = gated_chains()) || (rc = scores<0>()) || (rc = loss()) ||
-            (rc = adjoints([&] { return scores<1>(); })) || (rc = gated_bptt()) || (rc = gated_dM_words()) || (rc = back()) ||
-            (rc = factors())) return rc;
+        if ((rc = prepare()) || (rc = mx ? gated_max_chains() : gated_chains()) || (rc = scores<0>()) || (rc = loss()) ||
+            (rc = adjoints([&] { return scores<1>(); })) || (rc = mx ? gated_max_bptt() : gated_bptt()) ||
+            (rc = mx ? dM_words() : gated_dM_words()) || (rc = back()) || (rc = factors())) return rc;
         return gate_gradients();
     }
     if ((rc = prepare()) || (rc = chains<false>()) || (rc = scores<0>()) || (rc = loss()) ||
@@ -1172,6 +1188,19 @@ extern "C" int farnn_decomp_ind1_gated_train_step(farnn_decomp_ind1_train_ctx *c
         return fail(FARNN_EINVAL, "decomp_ind1_gated_train_step: CRF transitions and their gradient go together (both or neither)%s%s");
     return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream, [&](Decomp1Step &t) {
         t.gw = g; t.go = go;
+        if (crf_trans) { t.crf = true; t.crf_trans = crf_trans; t.dtrans = dtrans; }
+    });
+}
+extern "C" int farnn_decomp_ind1_gated_max_train_step(farnn_decomp_ind1_train_ctx *c, const farnn_decomp_ind1_train_weights *w,
+                                                      const farnn_decomp_ind1_gate_weights *g, const float *crf_trans, const int64_t *x,
+                                                      const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                                      int64_t valid_tokens, const farnn_decomp_ind1_train_outputs *o,
+                                                      const farnn_decomp_ind1_gate_outputs *go, float *dtrans, void *stream) {
+    if (!g || !go) return fail(FARNN_EINVAL, "decomp_ind1_gated_max_train_step: null gate weights / gate outputs%s%s");
+    if ((crf_trans == nullptr) != (dtrans == nullptr))
+        return fail(FARNN_EINVAL, "decomp_ind1_gated_max_train_step: CRF transitions and their gradient go together (both or neither)%s%s");
+    return run_train_step<Decomp1Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream, [&](Decomp1Step &t) {
+        t.gw = g; t.go = go; t.gmx = true;
         if (crf_trans) { t.crf = true; t.crf_trans = crf_trans; t.dtrans = dtrans; }
     });
 }

@@ -29,6 +29,8 @@ def default_device():
 #   DECOMP_IND1_TRAIN         the decomposed independent=1 model's training step (FARNN_S_D_W_I)              f9
 #   DECOMP_IND1_CRF_TRAIN     that step under --use_crf 1, beside DECOMP_IND1_TRAIN                           f9
 #   DECOMP_IND1_GATED_TRAIN   that step for the gated model (--farnn 1 | 2, sum semiring), beside DECOMP_IND1_TRAIN f9
+#   DECOMP_IND1_GATED_MAX_TRAIN  the gated model under --train_mode max, beside DECOMP_IND1_TRAIN, DECOMP_IND1_GATED_TRAIN and
+#                             BUCKETED_MAX_TRAIN (and DECOMP_IND1_CRF_TRAIN under --use_crf 1)                f9
 #   BUCKETED_MAX_TRAIN        --train_mode max for the three steps over bucketed per-word blocks (the onehot
 #                             FST, the onehot and the decomposed independent=1 model), beside each model's own f7 - f9
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3

@@ -4,7 +4,9 @@ rank-R_O output tensor (C_output, S1_output, S2_output).  Same constructor argum
 keys as the reference; inference runs in the HIP library (farnn_decomp_ind1_create).
 Training (opt-in, RE2NN_DECOMP_IND1_TRAIN=1): farnn_decomp_ind1_train_step; with --use_crf 1
 (RE2NN_DECOMP_IND1_CRF_TRAIN=1 beside it): farnn_decomp_ind1_crf_train_step; with --farnn 1 | 2
-(RE2NN_DECOMP_IND1_GATED_TRAIN=1 beside it, sum semiring): farnn_decomp_ind1_gated_train_step, with or without the CRF.
+(RE2NN_DECOMP_IND1_GATED_TRAIN=1 beside it, sum semiring): farnn_decomp_ind1_gated_train_step, with or without the CRF; with
+--farnn 1 | 2 --train_mode max (RE2NN_DECOMP_IND1_GATED_MAX_TRAIN=1 beside that and RE2NN_BUCKETED_MAX_TRAIN=1):
+farnn_decomp_ind1_gated_max_train_step.
 """
 import numpy as np
 import torch
@@ -122,8 +124,9 @@ class FARNN_S_D_W_I(FARNN_S_D_W_I_S):
         gated = a.farnn != 0
         if gated and not (a.farnn in (1, 2) and opted_in('DECOMP_IND1_GATED_TRAIN')):
             why = 'the gated recurrences (--farnn {})'.format(a.farnn)
-        elif a.train_mode != 'sum' and (gated or not (a.train_mode == 'max' and bucketed_max_train_enabled())):
-            why = 'the max semiring (--train_mode {})'.format(a.train_mode)      # (the gated chains: the sum semiring only)
+        elif a.train_mode != 'sum' and not (a.train_mode == 'max' and bucketed_max_train_enabled() and
+                                            (not gated or opted_in('DECOMP_IND1_GATED_MAX_TRAIN'))):
+            why = 'the max semiring (--train_mode {})'.format(a.train_mode)      # (the gated chains: behind a switch of their own)
         elif a.use_crf and not opted_in('DECOMP_IND1_CRF_TRAIN'):
             why = 'the CRF (--use_crf 1)'
         elif a.local_loss_func != 'CE1':

@@ -30,7 +30,7 @@ for f3 through torch's autograd, and one library call (farnn_decomp_ind1_train_s
 Vgen, S1, S2, wildcard_mat, C_output, S1_output, S2_output, h0 and hT.  Under --use_crf 1 (crf_trans given) the call is
 farnn_decomp_ind1_crf_train_step: the CRF's negative log-likelihood, the Viterbi tags and the transitions' gradient as well.
 With the gates of --farnn 1 | 2 (gates=...) the call is farnn_decomp_ind1_gated_train_step, with or without crf_trans: the
-gates' gradients as well.
+gates' gradients as well; on a max context (--train_mode max) it is farnn_decomp_ind1_gated_max_train_step.
 """
 import torch
 
@@ -164,8 +164,8 @@ def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, le
     crf_trans [C,C] (C counts START and STOP): the loss is the CRF's negative log-likelihood, a sum over the sequences, the
     tags are the Viterbi path, and crf_trans gets a gradient (farnn_decomp_ind1_crf_train_step).
     gates: as decomp_ifst_train_step's -- Wss1, Wrs1, bs1 (farnn = 1) followed by Wss2, Wrs2, bs2 (farnn = 2); with them the
-    call is farnn_decomp_ind1_gated_train_step (with or without crf_trans), every gate gets a gradient, and sigmoid_exponent is
-    the gates' k."""
+    call is farnn_decomp_ind1_gated_train_step (with or without crf_trans; farnn_decomp_ind1_gated_max_train_step when the
+    context's semiring is 'max'), every gate gets a gradient, and sigmoid_exponent is the gates' k."""
     call = None
     if len(gates) not in (0, 3, 6):
         raise ValueError('gates: none, Wss1 Wrs1 bs1 (farnn 1) or those and Wss2 Wrs2 bs2 (farnn 2), not {} tensors'.format(len(gates)))
@@ -174,8 +174,9 @@ def decomp_ind1_train_step(tc, Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT, P, x, le
             if crf_trans is not None and tuple(crf_trans.shape) != (Cout.shape[0],) * 2:
                 raise ValueError('CRF transitions must be [C, C] = {}, not {}'.format((Cout.shape[0],) * 2, tuple(crf_trans.shape)))
             if gates:
-                tc.gated_step(weights, len(gates) // 3, sigmoid_exponent, *ptrs, *dims, outputs, stream,
-                              trans_ptr=weights.get('crf_trans'), dtrans_ptr=outputs.get('dtrans'))
+                step = tc.gated_max_step if tc.semiring == 'max' else tc.gated_step
+                step(weights, len(gates) // 3, sigmoid_exponent, *ptrs, *dims, outputs, stream,
+                     trans_ptr=weights.get('crf_trans'), dtrans_ptr=outputs.get('dtrans'))
             else:
                 tc.step_crf(weights, weights['crf_trans'], *ptrs, *dims, outputs, outputs['dtrans'], stream)
     spec = [(n, t, IF_REQUIRED if n in _D1_OPTIONAL else ALWAYS) for n, t in zip(_D1_NAMES, (Vgen, S1, S2, W, Cout, S1o, S2o, h0, hT))]

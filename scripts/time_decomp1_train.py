@@ -16,8 +16,9 @@ lengths, rotating through four batches of the same lengths.  Prints one JSON lin
 transitions are the reference's initial ones plus seeded noise in (-0.5, 0.5) where they are not -10000).
 --farnn 1 | 2: farnn_decomp_ind1_gated_train_step with seeded gates (Wss ~ N(0, 0.3^2 / S), Wrs ~ N(0, 0.3^2 / R), bs ~
 N(0, 0.2^2), sigmoid_exponent 5: the sigmoids stay off saturation), drawn after everything the plain step draws.
---parent_lib 1: the library named by FARNN_LIB is a build of an earlier commit without the CRF or the gated entry point (their
-bindings are dropped before the library is loaded); for the plain step only.
+--farnn 1 | 2 --train_mode max: farnn_decomp_ind1_gated_max_train_step on the same gates (train_step picks it on a max context).
+--parent_lib 1: the library named by FARNN_LIB is a build of the commit before the gated max entry point (its binding is
+dropped before the library is loaded); for the plain step in either semiring, the CRF step and the gated sum step.
 
 The line carries no rate: none was measured.  Each GPU step of a job script runs it under its own time limit
 (timeout -k 10 ...)."""
@@ -46,9 +47,8 @@ def main():
     import torch
     from re2nn_seq_amd import _lib, synth
     if a.parent_lib:
-        assert not a.use_crf and not a.farnn, 'an earlier build has no CRF step and no gated step'
-        _lib.SIGNATURES.pop('farnn_decomp_ind1_crf_train_step')
-        _lib.SIGNATURES.pop('farnn_decomp_ind1_gated_train_step')
+        assert not (a.farnn and a.train_mode == 'max'), 'the parent build has no gated max step'
+        _lib.SIGNATURES.pop('farnn_decomp_ind1_gated_max_train_step')
     from re2nn_seq_amd.farnn.train_step import decomp_ind1_train_step
     V, S, C, R, RO, B, L = 11000, 104, 73, 50, 70, 256, 64
     rng = np.random.RandomState(1234)
