@@ -95,7 +95,8 @@ __device__ __forceinline__ void dest_lane(const int lane, int &rj, int &rs, bool
 // one LDS-only barrier, as the first thing that knows (b, len): nothing in front of step 0 drains vmcnt with the ring in flight.
 template <int D, int LPR, bool H16>
 __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int dir, const int w, const int lane, const int nsteps,
-                                                const int len, const int b, DestRing<D, LPR, H16> &ring) {
+                                                const int len, const int b, DestRing<D, LPR, H16> &ring,
+                                                const long long *tokoff_lds = nullptr) {
     constexpr int NC = DestRing<D, LPR, H16>::NC;
     const int S = p.S, SP = p.SP, CPR = p.CPR;
     const int RW = (S + RG_NWC - 1) / RG_NWC;
@@ -115,7 +116,10 @@ __device__ __forceinline__ void regs_dest_prime(const RegsParams &p, const int d
             ring.voff[i] = ((unsigned)(my_valid ? my_row : 0) * (unsigned)SP + (unsigned)((my_valid && ci < CPR) ? ci : rs < CPR ? rs : 0) * 4u) * 4u;
     }
     (void)SP; (void)CPR;
-    {
+    if (tokoff_lds) {                                    // (FARNN_CHAIN_START 2: wavefront 0 left the first window's offsets in LDS)
+        const long long o_ = tokoff_lds[lane < nsteps ? lane : nsteps - 1];
+        ring.tkw_lo = (int)(unsigned)o_; ring.tkw_hi = (int)(unsigned)(o_ >> 32);
+    } else {
         const int t = lane < nsteps ? lane : nsteps - 1;
         const int idx = (dir == 0) ? t : (t < len ? len - 1 - t : t);
         const long long o_ = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);

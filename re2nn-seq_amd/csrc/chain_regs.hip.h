@@ -162,6 +162,8 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
     // HEAD (the destination split's recurrence-only launch, f16 and f32): the selection runs BESIDE the set-up, and ONE LDS-only
     // barrier stands in front of step 0.  The other forms keep the head below.
     constexpr bool HEAD = DEST && !SCORE && (FARNN_CHAIN_HEAD != 0);
+    constexpr int START = HEAD ? FARNN_CHAIN_START : 0;           // how it gets to step 0 (chain_regs_params.hip.h)
+    static_assert(START >= 0 && START <= 2, "FARNN_CHAIN_START is 0, 1 or 2");
     int b, len;
     const float *hinit = dir == 0 ? p.h0 : p.hT;
 #if defined(FARNN_PROBES)
@@ -171,21 +173,45 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
 #endif
     DestRing<RD_D, RD_LPR, H16> dring;
     if constexpr (HEAD) {
-        if (w == 0) {
-            // wavefront 0: the sequence and its length (launch_order.hip.h), in registers; two words of `misc` hand them on
+        // START 2 (the default): wavefront 0 selects, the others store the set-up; two words of `misc` hand (b, len) on, and wavefront 0
+        // leaves the first window's block offsets in LDS with them (below).
+        // START 1 (measured, not kept): every compute wavefront selects for itself -- a pure function of p.len, B, L and the slot, so all six get the same pair;
+        // the `len` lines are shared through L1 -- and asks for its tokens and its first blocks straight behind the selection: no LDS word
+        // and no barrier between the selection and the first block request.  The writer's and the eighth wavefront store the set-up
+        // meanwhile (none of it depends on the sequence).  Wavefront 0 still leaves (b, len) in `misc` for those two.
+        constexpr int NSEL = START == 1 ? RG_NWC : 1;                      // wavefronts that select
+        if (w < NSEL) {
             int bb = p.order ? p.order[slot] : slot, ll = -1;
-            if (p.sort) bb = select_by_length_rank_one_wave(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, lane, &ll);
+            if constexpr (START == 0) {
+                if (p.sort) bb = select_by_length_rank_one_wave(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, lane, &ll);
+            } else {
+                if (p.sort) bb = select_by_length_rank_top_one_wave(p.len, p.B, p.L, p.pair ? folded_rank(slot, p.B) : slot, lane, &ll);
+            }
             if (ll < 0) ll = clamp_len(p.len[bb], p.L);
-            if (lane == 0) { misc[RGM_SEL] = bb; misc[RGM_SEL + 1] = ll; }
-            FARNN_HD_STAMP(1);
+            if (w == 0 && lane == 0) { misc[RGM_SEL] = bb; misc[RGM_SEL + 1] = ll; }
+            if (w == 0) FARNN_HD_STAMP(1);
+            if constexpr (START == 1) {
+                b = __builtin_amdgcn_readfirstlane(bb);
+                len = __builtin_amdgcn_readfirstlane(ll);
+                const int ns = p.full ? p.L : len;
+                if (ns > 0) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, ns, len, b, dring);
+            } else if constexpr (START == 2) {
+                // wavefront 0 loads the row's first 64 token ids as soon as it has b, one lane per step in the direction's order, and
+                // leaves the block offsets in the LDS window in front of the barrier
+                const int ns = p.full ? p.L : ll;
+                if (lane < ns) {
+                    const int idx = (dir == 0) ? lane : (lane < ll ? ll - 1 - lane : lane);
+                    tokoff[lane] = (long long)clamp_tok(p.x[(long long)bb * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
+                }
+            }
         } else {
-            // wavefronts 1 .. 7 meanwhile: everything that depends on neither.  Every word has ONE store, from one wavefront.
+            // the other wavefronts meanwhile: everything that depends on neither.  Every word has ONE store, from one wavefront.
             // Of `hist` only what is read before it is written: row 0, and the pad columns S .. SP - 1 of rows 1 .. L (the compute
             // lanes write every column below S of a row they finish; the writer copies whole SP-wide rows, and the stash's readers
             // take the pads as exact zeros).  At most three words a row, at S not a multiple of four: nothing wider than a dword fits.
             // (ONE: rows of RD_XS floats, pads up to column RD_XS - 1 -- 80 - S words a row)
-            const int t = tid - 64;
-            constexpr int nt = nthreads - 64;
+            const int t = tid - 64 * NSEL;
+            constexpr int nt = nthreads - 64 * NSEL;
             // (rows of RD_XS floats: the pads reach column RD_XS - 1 -- the compute lanes of a one-store chain read whole rows as their
             //  state, chunks behind the row's columns included, and multiply them with whatever finite bytes the block holds there)
             for (int j = t; j < HS; j += nt) {
@@ -207,18 +233,25 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
             for (int j = t; j < 2 * RD_XS; j += nt)
                 smem[lds.xd + j] = j < S ? hinit[j] * ((dir == 1 && p.o) ? p.o[j] : 1.0f) : 0.0f;
         }
-        wg_barrier_lds();                                // the ONE barrier in front of step 0: LDS traffic only, nothing of the ring is in flight yet
-        b = __builtin_amdgcn_readfirstlane(misc[RGM_SEL]);
-        len = __builtin_amdgcn_readfirstlane(misc[RGM_SEL + 1]);
+        // the ONE barrier in front of step 0: LDS traffic only -- it drains no vmcnt (START 1: the compute wavefronts' rings are in flight
+        // across it; by the time they reach it the set-up's two wavefronts have passed)
+        wg_barrier_lds();
+        if (START != 1 || w >= RG_NWC) {
+            b = __builtin_amdgcn_readfirstlane(misc[RGM_SEL]);
+            len = __builtin_amdgcn_readfirstlane(misc[RGM_SEL + 1]);
+        }
         if (b_out) *b_out = b;
         // the block offsets in LDS feed the address windows BEHIND the first (chain_dest.hip.h, FARNN_RD_WINDOW): a sequence of at most
-        // 64 steps never reads them.  A longer one fills them as before, in front of a barrier of its own, before anything is primed.
+        // 64 steps never reads them.  A longer one fills them as before, in front of a barrier of its own.  (START 1: the ring is in
+        // flight by now, and a wavefront that loads token ids waits for them with vmcnt(0): the two wavefronts without a ring fill them.)
         if ((p.full ? p.L : len) > 64) {
             const int ns = p.full ? p.L : len;
-            for (int k = tid; k < ns; k += nthreads) {
-                const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
-                tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
-            }
+            constexpr int t0 = START == 1 ? 64 * RG_NWC : 0;
+            if (tid >= t0)
+                for (int k = tid - t0 + (START == 2 ? 64 : 0); k < ns; k += nthreads - t0) {
+                    const int idx = (dir == 0) ? k : (k < len ? len - 1 - k : k);
+                    tokoff[k] = (long long)clamp_tok(p.x[(long long)b * p.L + idx], p.V) * (H16 ? p.blk16 : p.blk * 4);
+                }
             wg_barrier_lds();
         }
     } else {
@@ -308,7 +341,8 @@ __device__ __forceinline__ void chain_regs_body(const RegsParams &p, float *smem
 #else
                 const bool probe_ = false;
 #endif
-                if constexpr (!PRIME_EARLY) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
+                if constexpr (START == 2) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring, tokoff);
+                else if constexpr (!PRIME_EARLY && START != 1) regs_dest_prime<RD_D, RD_LPR, H16>(p, dir, w, lane, nsteps, len, b, dring);
                 if (w == 0) FARNN_HD_STAMP(3);
                 regs_compute_dest<NLX, RD_D, RD_LPR, H16, ONE>(p, dir, w, lane, nsteps, tokoff, part + NP * PS, ol, hist, HS, smem + lds.xd, probe_, b, dring);
                 __builtin_amdgcn_s_setprio(0);

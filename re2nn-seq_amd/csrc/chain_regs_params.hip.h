@@ -10,6 +10,17 @@
 #ifndef FARNN_CHAIN_HEAD
 #define FARNN_CHAIN_HEAD 1      /* (chain_regs.hip.h) */
 #endif
+// How that head gets from the launch to step 0 (chain_regs.hip.h, HEAD):
+//   2 (default)  wavefront 0 selects (sequence, length) with the search that is short for the long rows (launch_order.hip.h), loads the
+//                row's first 64 token ids at once and leaves the block offsets in LDS in front of the barrier; the compute wavefronts
+//                fill their offset window from LDS behind it: no dependent global load between the barrier and the first block request;
+//   1            every compute wavefront selects for itself with that search and primes its ring straight behind it, the writer and
+//                the eighth wavefront store the set-up (measured and not kept: a later first step on the full-length rows);
+//   0            wavefront 0 selects with the plain bisection and hands (sequence, length) on through LDS, the compute wavefronts load
+//                their token ids behind the barrier: the head as it was, a variant build for A/B runs.
+#ifndef FARNN_CHAIN_START
+#define FARNN_CHAIN_START 2
+#endif
 // (Not in the profiling build: the build's ring-register check does not run there, and with the probes compiled in the compiler
 //  copied the one-store kernel's ring registers while their loads were in flight -- wrong tags.  It runs the two-store kernel.)
 #if defined(FARNN_PROBES) && !defined(FARNN_STEP_ONESTORE)

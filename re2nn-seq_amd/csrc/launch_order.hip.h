@@ -67,6 +67,67 @@ __device__ __forceinline__ int select_by_length_rank_one_wave(const int64_t *len
     return select_by_length_rank_wave<16>(len, B, L, rank, lane, len_out);          // B <= 1024
 }
 
+// The same selection with a search that is SHORT FOR THE LONG ROWS (the head of the recurrence-only destination-split launch,
+// chain_regs_body: a launch lasts as long as its longest rows, and whatever stands in front of their step 0 is paid by the whole
+// launch).  select_by_length_rank_wave bisects [0, L] whatever the rank: 6-7 rounds at L = 64.  Here
+//   1. ONE round tests the top class -- the rows of length L are done after it;
+//   2. a galloping descent (L - 1, L - 3, L - 7, ...) brackets the class in O(log(L - cls)) rounds;
+//   3. the bisection runs inside the bracket.
+// Invariant throughout: count_ge(lo) > rank >= count_ge(hi + 1) =: above.  At lo == hi that is the class and, in `above`, the count
+// of the classes over it -- the round the plain form spends on count_ge(cls + 1) is not run again.  Class, `rem` and the ballot pick
+// are the plain form's: the same (sequence, length) for every rank.
+template <int NV>
+__device__ __forceinline__ int select_by_length_rank_top_wave(const int64_t *len, int B, int L, int rank, int lane, int *len_out) {
+    int v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const int k = lane + 64 * i;
+        int x = k < B ? (int)len[k] : -1;                // (-1: no sequence; below every class)
+        if (k < B) x = x < 0 ? 0 : (x > L ? L : x);
+        v[i] = x;
+    }
+    auto count_ge = [&](int t) {
+        int c = 0;
+#pragma unroll
+        for (int i = 0; i < NV; i++) c += __popcll(__ballot(v[i] >= t));
+        return c;
+    };
+    int lo = 0, hi = L, above = 0;                       // count_ge(0) = B > rank; count_ge(L + 1) = 0
+    for (int gap = 0; lo < hi; gap = 2 * gap + 1) {      // probes L, L - 1, L - 3, L - 7, ...: each at most hi, above lo
+        const int t = L - gap;
+        if (t <= lo) break;                              // the descent ran past the bottom: [lo, hi] is the bracket
+        const int c = count_ge(t);
+        if (c > rank) { lo = t; break; }
+        hi = t - 1; above = c;
+    }
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const int c = count_ge(mid);
+        if (c > rank) lo = mid; else { hi = mid - 1; above = c; }
+    }
+    const int cls = lo;
+    *len_out = cls;
+    int rem = rank - above;                              // index inside the class (sequences in index order: register-major, then lane)
+    int res = 0;
+    bool found = false;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const unsigned long long m = __ballot(v[i] == cls);
+        const int c = __popcll(m);
+        if (!found && rem < c) {
+            const bool hit = ((m >> lane) & 1ull) && __popcll(m & ((1ull << lane) - 1ull)) == rem;
+            res = 64 * i + (int)__builtin_ctzll(__ballot(hit) | (1ull << 63));
+            found = true;
+        } else if (!found) rem -= c;
+    }
+    return res;
+}
+__device__ __forceinline__ int select_by_length_rank_top_one_wave(const int64_t *len, int B, int L, int rank, int lane, int *len_out) {
+    if (B <= 256) return select_by_length_rank_top_wave<4>(len, B, L, rank, lane, len_out);
+    if (B <= 512) return select_by_length_rank_top_wave<8>(len, B, L, rank, lane, len_out);
+    return select_by_length_rank_top_wave<16>(len, B, L, rank, lane, len_out);      // B <= 1024
+}
+
 // len_out (optional): the selected sequence's clamped length comes back with it -- the class the search found -- so the caller
 // need not load len[b] behind the selection (a dependent global round trip at the launch's start, when every workgroup loads).
 // LDS_ONLY: the two workgroup barriers order LDS traffic only (wg_barrier_lds) -- a __syncthreads() also drains the vector-memory
