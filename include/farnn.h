@@ -781,6 +781,57 @@ int  farnn_optim_set_lr(farnn_optim *opt, double lr);
 int  farnn_optim_steps(const farnn_optim *opt, int32_t i, int64_t *out);
 int  farnn_optim_set_steps(farnn_optim *opt, int32_t i, int64_t steps);
 
+/* ---- device-side scorer of an epoch's loss and tag metrics (metrics/metrics.py:17-28 eval_seq_token, :121-157
+ * get_ner_fmeasure of this package; reference src_seq/metrics/metrics.py:7-42, :96-129) ----------------------------------
+ * The reference scores ONE flat list per data set: the valid tokens of every sequence of every batch, in order.  A handle counts
+ * that list batch by batch, on the device: farnn_score_add takes one batch's padded tags, gold labels, lengths and (optionally)
+ * the step's loss scalar in ONE launch and waits for nothing; farnn_score_read is the only call that waits.  Every number is an
+ * integer count, or a double sum taken in stream order, so the host's ratios over them equal metrics.py's bit for bit.
+ *
+ * Per label id the caller's tables give kind (0 other, 1 B-, 2 I-), type (-1 or 0 .. n_types - 1) and canon (the first id with the
+ * same spelling).  With `prev` the previous valid token of the whole stream (across sequences, batches and adds; none before the
+ * first), link[j] = kind[j] == 2 && kind[prev] != 0 && type[j] == type[prev], for the tags and for the labels separately.  A
+ * position where tag and label are both B- of one type opens a candidate; the candidate is a match at the next position where
+ * both links are false (which may open the next candidate), dies at the next position where exactly one is false, and is a match
+ * if the stream ends first (both spans are then open-ended).  What an add leaves for the next lives in the handle: the last tag
+ * and label ids, the open candidate's type, the flat length.
+ * The adds (and resets) of one handle must be ordered on ONE stream: an add reads what the previous one left. */
+typedef struct farnn_score farnn_score;
+
+typedef struct {
+    int64_t n;                  /* valid tokens (the flat length)                                               */
+    int64_t same;               /* tag == label                                                                 */
+    int64_t canon_same;         /* canon[tag] == canon[label] (get_ner_fmeasure's accuracy)                     */
+    int64_t tp, fp, fn;         /* eval_seq_token's: same & tag != o; !same & tag != o; !same & label != o      */
+    int64_t pred_spans;         /* B- tags                                                                      */
+    int64_t gold_spans;         /* B- labels                                                                    */
+    int64_t matches;            /* spans equal in start, end and type; a candidate still open counts            */
+    int64_t errors;             /* valid positions whose tag or label lies outside [0, n_labels)                */
+    int64_t adds;               /* farnn_score_add calls since create / reset                                   */
+    double  loss_sum;           /* one double addition of the float32 loss per add that passed one              */
+    int64_t *per_type;          /* HOST, [5][n_types] or NULL: B- tags, B- labels, matches, then the flat index
+                                 * of the first B- tag and of the first B- label of the type (-1: none)         */
+} farnn_score_counts;
+
+/* kind, type, canon: HOST arrays [n_labels] (copied).  FARNN_EINVAL, before any device is touched: a null table or `out`,
+ * n_labels <= 0, n_types < 0, a kind outside 0..2, a type outside [-1, n_types), a canon outside [0, n_labels). */
+int  farnn_score_create(farnn_score **out, const int32_t *kind, const int32_t *type, const int32_t *canon, int32_t n_labels,
+                        int32_t n_types, int32_t o_idx, int device);
+void farnn_score_destroy(farnn_score *h);
+/* tags int32 [B][L], labels int64 [B][L], lengths int64 [B], loss float[1] or NULL: DEVICE pointers.  One launch on `stream`
+ * (hipStream_t as void*, NULL = the default stream), no host synchronisation and no allocation, except that the per-sequence
+ * work buffer grows (after a device synchronise) when B exceeds every earlier B.  Lengths are clamped to [0, L]; positions at
+ * or beyond a sequence's length are never read.  A valid position whose tag or label lies outside [0, n_labels) indexes no
+ * table: it counts as kind 0 (and as its raw id in same / canon_same / tp / fp / fn) and adds one to `errors`.
+ * FARNN_EINVAL: a null handle, tags, labels or lengths; B <= 0 or L <= 0. */
+int  farnn_score_add(farnn_score *h, const int32_t *tags, const int64_t *labels, const int64_t *lengths, int32_t B, int32_t L,
+                     const float *loss, void *stream);
+/* Copies the counts to the host behind everything enqueued on `stream` and waits for it: the only call that waits.  per_type may
+ * be NULL.  The handle keeps counting: a later add continues the same stream of tokens. */
+int  farnn_score_read(farnn_score *h, farnn_score_counts *counts, void *stream);
+/* Back to the state after create (enqueued on `stream`, not awaited). */
+int  farnn_score_reset(farnn_score *h, void *stream);
+
 /* ---- introspection / measurement ----------------------------------------------------- */
 int  farnn_abi_version(void);
 /* 1: the A/B (profiling) build of the library (csrc/build.py --probes): it also carries the forms the production build left behind --

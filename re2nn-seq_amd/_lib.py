@@ -189,10 +189,24 @@ class OptimDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double)]
 
 
+class ScoreCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ('n', 'same', 'canon_same', 'tp', 'fp', 'fn', 'pred_spans', 'gold_spans', 'matches',
+                                         'errors', 'adds')] + [('loss_sum', C.c_double), ('per_type', C.POINTER(C.c_int64))]
+
+
+SCORE_WAVES = 16                               # csrc/farnn_score.hip: sequences in flight (one per wavefront of the launch)
+SCORE_TYPE_ROWS = 5                            # per_type rows: B- tags, B- labels, matches, first B- tag, first B- label
+
 OPTIM_SGD, OPTIM_ADAM = 0, 1
 OPTIM_CHUNK, OPTIM_MAX_TENSORS = 2048, 32      # csrc/optim.hip.h: elements per workgroup, tensors per launch
 
 SIGNATURES = {
+    'farnn_score_create': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int]),
+    'farnn_score_destroy': (None, [C.c_void_p]),
+    'farnn_score_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'farnn_score_read': (C.c_int, [C.c_void_p, C.POINTER(ScoreCounts), C.c_void_p]),
+    'farnn_score_reset': (C.c_int, [C.c_void_p, C.c_void_p]),
     'farnn_optim_create': (C.c_int, [C.POINTER(OptimDesc), C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_optim_destroy': (None, [C.c_void_p]),
     'farnn_optim_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -832,3 +846,43 @@ class Optim:
 
     def set_steps(self, i, n):
         check(load().farnn_optim_set_steps(self._raw, int(i), int(n)), 'farnn_optim_set_steps')
+
+
+class Score:
+    """Owns one farnn_score* (the device-side scorer, include/farnn.h): the label tables, the counts and what one add leaves
+    for the next.  add() takes device pointers and waits for nothing; read() is the only call that waits."""
+
+    def __init__(self, kind, type_, canon, n_types, o_idx, device=0):
+        self._raw = None
+        self.n_labels, self.n_types = len(kind), int(n_types)
+        arrays = [None if a is None else (C.c_int32 * max(len(a), 1))(*[int(v) for v in a]) for a in (kind, type_, canon)]
+        out = C.c_void_p()
+        check(load().farnn_score_create(C.byref(out), arrays[0], arrays[1], arrays[2], self.n_labels, self.n_types, int(o_idx),
+                                        int(device)), 'farnn_score_create')
+        self._raw = out
+        self._per_type = (C.c_int64 * max(SCORE_TYPE_ROWS * self.n_types, 1))()
+
+    def close(self):
+        if self._raw:
+            load().farnn_score_destroy(self._raw)
+            self._raw = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, tags_ptr, labels_ptr, len_ptr, B, L, loss_ptr=None, stream=None):
+        check(load().farnn_score_add(self._raw, tags_ptr, labels_ptr, len_ptr, int(B), int(L), loss_ptr, stream), 'farnn_score_add')
+
+    def read(self, stream=None):
+        """(ScoreCounts, [SCORE_TYPE_ROWS][n_types] lists)"""
+        c = ScoreCounts()
+        c.per_type = C.cast(self._per_type, C.POINTER(C.c_int64))
+        check(load().farnn_score_read(self._raw, C.byref(c), stream), 'farnn_score_read')
+        nt = self.n_types
+        return c, [[int(self._per_type[r * nt + t]) for t in range(nt)] for r in range(SCORE_TYPE_ROWS)]
+
+    def reset(self, stream=None):
+        check(load().farnn_score_reset(self._raw, stream), 'farnn_score_reset')

@@ -36,6 +36,8 @@ def default_device():
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3
 #   DECOMP_TEACHER_MAX_TRAIN  those terms under --train_mode max, beside DECOMP_TEACHER_TRAIN                 f3
 #   NATIVE_OPTIM              the library's one-launch Adam / SGD in train_onehot.train_epochs                f6
+#   DEVICE_METRICS            an epoch's loss and TRAIN metrics counted on the device and read once, in
+#                             train_onehot.train_epochs (metrics/device.py; evaluation stays on the host path) f10
 def opted_in(name):
     """True only for RE2NN_<name>=1, read from the environment at call time."""
     return os.environ.get('RE2NN_' + name, '') == '1'

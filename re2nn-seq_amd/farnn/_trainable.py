@@ -85,3 +85,19 @@ class Trainable:
         pred = self._flatten(tags, lengths.to(tags.device)).to(torch.int64).to(input.device)
         true = self._flatten(label, lengths).to(input.device)
         return loss, pred, true
+
+    def forward_local_device(self, input, label, lengths, re_tags=None):
+        """forward_local(train=True) for a caller that scores on the device (metrics/device.py): the same
+        checks and the same step, but (loss, tags [B, Lmax] int32, labels [B, Lmax] int64, lengths [B] int64) as they lie on the
+        device -- no flatten and no copy to the host."""
+        self._check_step(re_tags)
+        self.enable_training()
+        on_host = lengths.device.type == 'cpu'
+        Lmax = int(lengths.max()) if on_host else int(lengths.max().item())
+        ntok = int(lengths.clamp(0, Lmax).sum()) if on_host else None
+        dev = self._dev()
+        lab = label[:, :Lmax].to(device=dev, dtype=torch.int64).contiguous()
+        ln = lengths.to(device=dev, dtype=torch.int64).contiguous()
+        loss, tags = self._train_call(input[:, :Lmax], ln, lab, ntok, re_tags)
+        self._dirty = True
+        return loss, tags, lab, ln

@@ -90,23 +90,40 @@ def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
     else:
         optimizer = optim.Adam(params, lr=args.lr, weight_decay=0)
     print('ALL TRAINABLE PARAMETERS: {}'.format(sum(p.numel() for p in params)))
+    score = None
+    if opted_in('DEVICE_METRICS'):                # opt-in: the loss and the tag metrics counted on the device
+        from .metrics.device import DeviceScore, entity_level, token_level
+        if DeviceScore.supported(i2s):
+            score = DeviceScore(i2s, s2i['o'], model._dev())
+    teacher = args.method == 'decompose' and getattr(args, 'marryup_type', 'none') in ('kd', 'pr')
     for epoch in range(1, args.epoch + 1):
         model.train()
         preds, trues, avg_loss, n_tok = [], [], 0.0, 0
         t0 = time.perf_counter()
+        if score is not None:
+            score.reset()
         for batch in iter_batches(splits['train'], args.bz):
             optimizer.zero_grad()
-            if args.method == 'decompose' and getattr(args, 'marryup_type', 'none') in ('kd', 'pr'):
-                # the RE teacher's scores of the batch (ref train_decompose.py:177-190; the step moves them to the device)
-                loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True, re_tags=batch['re'])
+            # under --marryup_type kd | pr the RE teacher's scores of the batch go with it (ref train_decompose.py:177-190; the
+            # step moves them to the device)
+            kw = {'re_tags': batch['re']} if teacher else {}
+            if score is not None:                 # nothing of the step comes back to the host: one read at the epoch's end
+                loss, tags, lab, ln = model.forward_local_device(batch['x'], batch['s'], batch['l'], **kw)
+                loss.backward()
+                optimizer.step()
+                score.add(tags, lab, ln, loss=loss.detach())
             else:
-                loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True)
-            loss.backward()
-            optimizer.step()
-            avg_loss += float(loss.detach())
-            preds.append(pred.cpu())
-            trues.append(true.cpu())
+                loss, pred, true = model.forward_local(batch['x'], batch['s'], batch['l'], train=True, **kw)
+                loss.backward()
+                optimizer.step()
+                avg_loss += float(loss.detach())
+                preds.append(pred.cpu())
+                trues.append(true.cpu())
             n_tok += int(batch['l'].sum())
+        counts = None
+        if score is not None:
+            counts = score.read()
+            avg_loss = counts.loss_sum
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         avg_loss /= max(len(splits['train']), 1)
@@ -117,9 +134,14 @@ def train_epochs(model, splits, args, s2i, i2s, logger, recorder, stats):
         print(info)
         logger.add(info)
         stats.setdefault('train_step', []).append({'tokens': n_tok, 'seconds': el, 'tokens_per_s': n_tok / el})
-        all_pred, all_true = torch.cat(preds), torch.cat(trues)
-        res_train = {'token-level': list(eval_seq_token(seq_label_pred=all_pred, seq_label_true=all_true, o_idx=s2i['o'])),
-                     'entity-level': list(get_ner_fmeasure(golden_lists=all_true, predict_lists=all_pred, i2s=i2s))}
+        if counts is not None:
+            if counts.errors:
+                raise ValueError('{} tags or labels outside the label map reached the device scorer'.format(counts.errors))
+            res_train = {'token-level': list(token_level(counts)), 'entity-level': list(entity_level(counts))}
+        else:
+            all_pred, all_true = torch.cat(preds), torch.cat(trues)
+            res_train = {'token-level': list(eval_seq_token(seq_label_pred=all_pred, seq_label_true=all_true, o_idx=s2i['o'])),
+                         'entity-level': list(get_ner_fmeasure(golden_lists=all_true, predict_lists=all_pred, i2s=i2s))}
         print_and_log_results(logger, res_train, epoch, 'TRAIN')
         res_dev = val_onehot(iter_batches(splits['dev'], args.bz), model, args, s2i['o'], i2s)
         print_and_log_results(logger, res_dev, epoch, 'DEV')
