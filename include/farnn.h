@@ -843,7 +843,8 @@ int  farnn_num_columns(const farnn_model *m);              /* K of the scores te
 /* algorithmic HBM bytes of one farnn_tag() call with `valid_tokens` tagged tokens
  * (SURVEY.md 8d / DESIGN.md: per-token figure x tokens), for the roofline line of bench.py */
 double farnn_algorithmic_bytes(const farnn_model *m, int64_t valid_tokens);
-/* the share of that figure read/written by kernel `which` (0 = recurrence chain, 1 = score+decode) */
+/* the share of that figure read/written by kernel `which` (0 = recurrence chain, 1 = score+decode), for the form the plan of the
+ * handle's last farnn_tag() call chose (before the first call: the model kind's default recurrence kernel) */
 double farnn_kernel_algorithmic_bytes(const farnn_model *m, int32_t which, int64_t valid_tokens);
 /* per-kernel timing with HIP events recorded on the launch stream.  enable=N>0 starts collecting
  * on every N-th farnn_tag() call (N=1: every call; event records cost a few microseconds of
@@ -852,6 +853,8 @@ double farnn_kernel_algorithmic_bytes(const farnn_model *m, int32_t which, int64
  * timed launches of kernel `which` (0 = recurrence chain, 1 = score+decode, 2 = prep). */
 int  farnn_set_profiling(farnn_model *m, int32_t enable);
 int  farnn_kernel_time(farnn_model *m, int32_t which, double *total_ms, int64_t *launches);
+/* the kernel behind slot `which`, read from the plan of the handle's last farnn_tag() call (before the first call, and after
+ * farnn_set_compact(): the model kind's default).  The score slot is named by the model's kind whatever that call launched. */
 const char *farnn_kernel_name(const farnn_model *m, int32_t which);
 
 #ifdef __cplusplus

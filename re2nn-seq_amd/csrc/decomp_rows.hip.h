@@ -1260,21 +1260,20 @@ inline int launch_rows_n(const DecompRowsParams &p, int wg_limit, size_t lds, hi
 }
 
 inline int launch_decomp_rows(const DecompRowsPack &k, const DecompWeights &w, const RowsPlan &pl,
-                              const int64_t *x, const int64_t *len, const int *order, int sort_in_kernel,
-                              float *A, float *Bk, int B, int L, int full, int n_cu, hipStream_t s) {
+                              const int64_t *x, const int64_t *len, const int *order, int sort,
+                              float *A, float *Bk, int B, int L, int full, int cu_limit, hipStream_t s) {
     DecompRowsParams p;
     p.P1 = k.P1; p.P2[0] = k.P2[0]; p.P2[1] = k.P2[1]; p.P3[0] = k.P3[0]; p.P3[1] = k.P3[1];
     p.n1 = k.n1; p.n2 = k.n2; p.n3 = k.n3; p.ld2 = k.ld2; p.ld3 = k.ld3; p.nch2 = k.nch2; p.nch3 = k.nch3;
     p.res1 = pl.res1; p.res2 = pl.res2; p.res3 = pl.res3;
     p.TVt = k.TVt; p.h0 = w.h0; p.hT = w.hT;
-    p.x = x; p.len = len; p.order = order; p.sort = sort_in_kernel; p.A = A; p.Bk = Bk;
+    p.x = x; p.len = len; p.order = order; p.sort = sort; p.A = A; p.Bk = Bk;
     p.B = B; p.L = L; p.S = w.S; p.SP = w.SP; p.R = w.R; p.Rp = w.Rp; p.farnn = w.farnn; p.nl = w.nl;
     p.full = full; p.V = w.V; p.sig_k = w.sig_k;
     p.dbg = tun(TUN_DBG);
     p.lds_floats = (int)(pl.lds / 4);
     const int groups = (B + pl.nseq - 1) / pl.nseq;
     p.groups = groups;
-    const int cu_limit = (pl.form && !tun(TUN_ROWS_NOROUNDS)) ? n_cu : 0;      // (launch_rows_n: the register forms walk their groups in rounds)
 #define FARNN_ROWS_LAUNCH(F_, A_, B_, C_, D_, E_) if (pl.form == F_) return launch_rows_n<1, A_, B_, C_, D_, E_, rows_form_mixed(F_), rows_form_lpr(F_)>(p, cu_limit, pl.lds, s);
     FARNN_ROWS_FORMS(FARNN_ROWS_LAUNCH)
 #undef FARNN_ROWS_LAUNCH

@@ -37,6 +37,7 @@ extern "C" int farnn_set_compact(farnn_model *m, int32_t enable) {
         return fail(FARNN_EINVAL, "set_compact: this model has no compact form (i-FST with 0/1 weights, sum semiring, at most 512 states)%s%s");
     if (!enable && !m->Mf) return fail(FARNN_EINVAL, "set_compact: this handle was created compact-only (no dense blocks)%s%s");
     m->compact_on = enable != 0;
+    m->plan = TagPlan();                    // (the handle's form changed: no call has been planned under it)
     return FARNN_OK;
 }
 
@@ -129,21 +130,259 @@ extern "C" int farnn_kernel_time(farnn_model *m, int32_t which, double *total_ms
     return FARNN_OK;
 }
 
+// ---- the plan of a call (tag_plan.hip.h) --------------------------------------------------------
+// Every decision about a farnn_tag call is made here, from host arithmetic alone and before anything is enqueued; the refusals
+// the dispatch can raise come from here too.  No FARNN_* switch that selects a form is read anywhere else on the call path.
+
+// the destination-split form of the narrow register-fed kernel (chain_dest.hip.h)
+static bool regs_dest(const farnn_model *m) {
+    return !m->rgeom.wide && m->semiring != FARNN_SEMIRING_MAX && !tun(TUN_NODEST);
+}
+
+// the Viterbi launch behind the scores; fused: it computes the scores itself (no score_tile launch goes before it)
+static int plan_viterbi(const farnn_model *m, TagPlan &p, bool fused) {
+    if (m->K > 256) return fail(FARNN_ERANGE, "Viterbi: more than 256 tags%s%s");
+    const size_t hlds = viterbi_hist_lds_bytes(m->K, m->Kp, m->SP, p.L, fused);
+    // (K >= 224 never takes this form: the transposed transition table alone is 196 KiB -- no IB4 = 7, 8 instantiations)
+    if (hlds <= 158 * 1024 && viterbi_hist_ib4(m->K) <= 6 && !tun(TUN_VITERBI_BP)) {
+        // partition history in LDS, back-pointers recomputed along the path
+        p.viterbi = VITERBI_HIST; p.ib4 = viterbi_hist_ib4(m->K); p.viterbi_lds = hlds;
+        return FARNN_OK;
+    }
+    if (fused) return fail(FARNN_EINVAL, "Viterbi: the fused form needs the history in LDS%s%s");
+    // long sequences: two partition rows + stored back-pointers
+    p.viterbi = VITERBI_BP; p.ib4 = viterbi_ib4(m->K); p.viterbi_lds = viterbi_lds_bytes(m->K, m->Kp, p.L);
+    return lds_fits(p.viterbi_lds);
+}
+
+// fused: the Viterbi kernel computes the scores itself (no score_tile launch goes before it)
+static bool viterbi_can_fuse(const farnn_model *m, int L, bool scores) {
+    return m->use_crf && !scores && !m->P && m->ws.A && m->OT && m->K <= 256 &&
+           viterbi_hist_lds_bytes(m->K, m->Kp, m->SP, L, true) <= 158 * 1024 && viterbi_hist_ib4(m->K) <= 6 &&
+           !tun(TUN_VITERBI_BP) && !tun(TUN_VITERBI_UNFUSED);
+}
+
+// the stand-alone scores + decode of the i-FST kinds, behind a recurrence that left the states in the stash
+static int plan_score_decode(const farnn_model *m, TagPlan &p, bool flat, bool scores, bool offs) {
+    if (viterbi_can_fuse(m, p.L, scores)) {          // stash -> scores -> Viterbi -> tags in one kernel
+        p.score = SCORE_VITERBI_FUSED;
+        return plan_viterbi(m, p, true);
+    }
+    if (m->lm.on && !m->P && !scores && !m->use_crf && m->S <= LM_MAXS * 2 && (p.B <= 1024 || !flat || offs)) {
+        // K2l: the output matrix is a label map and only tags are asked for -- S multiply-adds and a scan per token, one workgroup
+        // per sequence (score_decode.hip.h).  FARNN_NOLABELMAP=1 (no label map is built then) keeps the matrix form.
+        p.score = SCORE_LABEL_MAP;
+        return FARNN_OK;
+    }
+    p.score = SCORE_TILE; p.kch = m->Kc / 64;
+    return m->use_crf ? plan_viterbi(m, p, false) : FARNN_OK;
+}
+
+// The dense-block recurrence.  fuse: the decode is the threshold/argmax one, so the scores and the decode may run beside the
+// recurrence (ONE launch) where the geometry allows it; p.fused tells whether it does.
+static int plan_chain(const farnn_model *m, TagPlan &p, bool fuse, bool lm_tags, bool offs_ok) {
+    const ChainGeom &g = m->geom;
+    const int L = p.L;
+    // ---- the register-fed kernel (chain_regs.hip.h) where its geometry applies: S <= 72, two workgroups per compute unit, or
+    // its wide form (chain_wide.hip.h): 72 < S <= 128, one workgroup per compute unit.
+    if (m->rgeom.ok && !tun(TUN_NOREGS)) {
+        const RegsGeom &rg = m->rgeom;
+        const size_t lds_cap = rg.wide ? 158 * 1024 : 80 * 1024;
+        bool score = fuse && m->ws.hs && m->OTm && m->c16 >= 1 && m->c16 <= (rg.wide ? RGW_NG : RG_NG) && m->Kc <= 256 && L <= 31 * RG_TT &&
+                     offs_ok && !tun(TUN_NOFUSE);
+        // Which form is the faster one was measured, and the faster one is the default.  S <= 72 with a label-map output matrix (tags
+        // only): the recurrence-only kernel followed by the label-map score launch (K2l).  Round 5 kept ONE launch (the scores and
+        // the decode beside the recurrence: north_star's form) while 2 B <= compute units, on measurements at B = 64 / 256 / 1 024 and
+        // L = 64 only; round 6's grid (scripts/gpu_r06_dispatch_grid.py -> profiles/r06_dispatch_grid.txt: B = 16..128 x L = 16..100)
+        // has two launches ahead at 32 of its 35 points -- by 5-20 % at the reference's default --seq_max_len 30 and below, within
+        // 1 % either way at L = 64 -- so the rule no longer looks at the batch.  FARNN_FUSE=1 keeps the one launch (what a HIP graph
+        // replays as one node); tests/test_gpu_dispatch_ab.py holds the default to "not the slower form" at nine (B, L) points.
+        if (score && !rg.wide && lm_tags && !tun(TUN_FUSE)) score = false;
+        const bool lm_path = score && lm_tags;
+        const bool dest = regs_dest(m);
+        auto carve = [&](bool sc, bool lm, bool row80) {
+            return (size_t)regs_lds(L, m->SP, rg.NP, sc ? m->c16 : 0, sc ? m->Kc : 0, sc, rg.RQ, lm, dest, row80).total * sizeof(float);
+        };
+        size_t lds = carve(score, lm_path, false);
+        // the wide form PAIRED (two workgroups per compute unit, like S <= 72): a ring of two steps and the label-map path's LDS
+        const bool paired = rg.wide && lm_path && rg.RQ <= 9 && lds <= 80 * 1024 && !tun(TUN_WIDE_UNPAIRED);
+        if (score && lds > lds_cap) {               // the score tiles do not fit (beside a second workgroup): recurrence only
+            score = false;
+            lds = carve(false, false, false);
+        }
+        // the 16-bit image where the handle has one (an eligible model, build_half_image): the recurrence-only launch of the
+        // destination split reads half the bytes with half the load instructions; FARNN_NOHALF=1 keeps the f32 blocks
+        const bool half = dest && !score && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF);
+        // ... on a model whose o is absent or all ones it keeps `hist` in rows of RD_XS floats where that fits beside a second
+        // workgroup (chain_dest.hip.h: one store per step, chain_regs_one_kernel); where it does not -- the longest sequences this
+        // kernel takes -- rows of SP floats and two stores as before
+        bool row80 = false;
+        if (half && (!m->o || m->o_ones) && FARNN_STEP_ONESTORE && FARNN_CHAIN_HEAD) {
+            const size_t lds80 = carve(false, false, true);
+            if (lds80 <= lds_cap) { row80 = true; lds = lds80; }
+        }
+        if (lds <= lds_cap) {
+            p.rec = (paired && score) ? REC_CHAIN_WIDE_PAIRED : rg.wide ? REC_CHAIN_WIDE : REC_CHAIN_REGS;
+            p.fused = score; p.lm_path = lm_path; p.dest = dest; p.half = half; p.row80 = row80; p.lds = lds;
+            p.host_epoch = score && tun(TUN_HOST_EPOCH);       // diagnostic A/B: the epoch as a kernel argument (not graph-capturable)
+            return FARNN_OK;
+        }
+    }
+    p.rec = REC_CHAIN_KERNEL;
+    // ring shape: a whole step per phase when it fits, KS phases deep
+    int ks = 2, nqp = g.NQ;
+    if (!g.pick_ring(L, m->chain_ks, ks, nqp))
+        return fail(FARNN_ERANGE, "chain kernel: LDS ring does not fit (sequence too long for this S)%s%s");
+    p.KS = ks; p.NQP = nqp; p.PPS = (g.NQ + nqp - 1) / nqp;
+    p.lds = g.lds_bytes(L, ks, nqp);
+    p.block = (g.NW + g.NLD + 1) * 64;                          // compute + loader + writer wavefronts
+    if (tun(TUN_CHAIN_HELPER) && p.block < 512) p.block += 64;  // experiment: an idle eighth wavefront
+    const int fq_max = p.block <= 384 ? 6 : 3;
+    p.FQ = (g.NCH == 1 && p.PPS == 1 && g.NQ <= fq_max && !tun(TUN_NOFAST)) ? g.NQ : 0;
+    if (g.NCH > 4) return fail(FARNN_ERANGE, "unsupported state count%s%s");
+    p.NCH = g.NCH <= 2 ? g.NCH : 4;
+    return FARNN_OK;
+}
+
+// the dense-block recurrence followed by scores + decode: ONE launch (the decode is the chain kernel's epilogue) when
+// the decode is the threshold/argmax one and the geometry allows it, else the chain kernel + the score / Viterbi kernels
+static int plan_chain_and_decode(const farnn_model *m, TagPlan &p, bool flat, bool scores, bool offs, bool lm_tags, bool offs_ok) {
+    // CRF decode: recurrence + scores + Viterbi in ONE launch (chain_viterbi.hip) where the register-fed recurrence applies and
+    // the decode's LDS fits; else the recurrence kernel followed by the (fused score +) Viterbi kernel.
+    // The one launch (north_star: "decode fused into the same kernel") exists for S <= 108 and is parity-tested, but is NOT the
+    // default (round 5): a compute unit then holds BOTH chains of a sequence, which run 1 390 cycles per step there against
+    // 780-960 when a long chain shares its unit with a short one, and the decode waits behind them.  Measured at K = 130,
+    // 256 x 64: S = 71 77.7 us in one launch against 72.9 in two (round 4; round 5's recurrence kernel: 69), S = 104 113.8 against
+    // 95.7 (profiles/r04_*, r05_*).  FARNN_CV_ONE=1 selects it.
+    // The production library does not carry the form's 48 kernels: it lives in the A/B build (build.py --probes, -DFARNN_AB).
+#if defined(FARNN_AB)
+    if (tun(TUN_CV_ONE) && m->rgeom.ok && !tun(TUN_NOREGS) && !tun(TUN_NOFUSE) && viterbi_can_fuse(m, p.L, scores) && offs_ok &&
+        chain_viterbi_fits(p.L, m->SP, m->rgeom.NP, m->K, m->Kp, m->lm.on != 0, m->rgeom.RQ)) {
+        p.rec = REC_CHAIN_VITERBI; p.fused = true; p.dest = regs_dest(m);
+        return FARNN_OK;
+    }
+#endif
+    if (int rc = plan_chain(m, p, !m->use_crf, lm_tags, offs_ok)) return rc;
+    return p.fused ? FARNN_OK : plan_score_decode(m, p, flat, scores, offs);
+}
+
+// the recurrence of the three decomposed kinds: the register kernel or the rows kernel when packed, else the older kernel
+// fuse: ask for the one-launch form (scores + argmax decode beside the recurrence); p.fused tells whether the model's kernel
+// and geometry allow it
+static void plan_decomp_recurrence(const farnn_model *m, TagPlan &p, bool fuse, bool offs_ok) {
+    if (m->rows.ok && regs_plan(m->rows, m->dw, p.L, p.regs)) {      // farnn = 0, rank <= 64: four wavefronts per chain, the packed rows in registers
+        bool score = fuse && m->ws.hs && m->OTm && m->c16 >= 1 && m->c16 <= DG_NG && m->Kc <= 256 && p.L <= 31 * RG_TT &&
+                     offs_ok && !tun(TUN_NOFUSE);
+        if (score) {
+            p.regs.lds_score = regs_score_lds(p.regs, p.L, m->SP, m->c16, m->Kc);
+            if (p.regs.lds_score > 80 * 1024) score = false;
+        }
+        p.rec = REC_DECOMP_REGS; p.fused = score;
+    } else if (m->rows.ok && rows_plan(m->rows, m->dw, p.B, p.L, p.rows)) {
+        p.rec = REC_DECOMP_ROWS;
+        p.rows_cu = (p.rows.form && !tun(TUN_ROWS_NOROUNDS)) ? m->n_cu : 0;      // (launch_rows_n: the register forms walk their groups in rounds)
+    } else
+        p.rec = REC_DECOMP_CHAIN;
+}
+
+static int plan_tag(const farnn_model *m, int B, int L, int full, bool flat, bool scores, TagPlan &p) {
+    p = TagPlan();
+    p.planned = true; p.B = B; p.L = L; p.full = full;
+    // batch preparation: flat-output offsets and the length-sorted launch order (full mode runs
+    // every sequence for L steps, so there is nothing to balance)
+    p.want_order = !full && B > 2 && !tun(TUN_NOSORT);
+    // the plain i-FST path needs no prep launch up to B = 1024: the chain workgroups select their sequence
+    // by length rank themselves and the score workgroups sum the lengths in front of theirs
+    p.prep_in_kernel = (m->kind == KIND_IFST || (m->kind == KIND_DECOMP && m->rows.ok)) && B <= 1024 && L <= 1023 && !tun(TUN_PREP);
+    p.order_valid = p.want_order && !p.prep_in_kernel;
+    p.sort_in_kernel = p.want_order && p.prep_in_kernel;
+    // the decomposed independent=1 scoring kernel slices the batch by flat offsets even when no flat output is asked for
+    p.want_offs = flat || (m->kind == KIND_DECOMP1 && m->d1_BSSp && !full);
+    if ((p.want_offs || p.want_order) && !p.prep_in_kernel) {
+        p.prep = B <= 1024 ? PREP_SMALL : PREP_LARGE;
+        while (p.prep == PREP_SMALL && p.prep_G < 16 && B * p.prep_G * 2 <= 1024) p.prep_G *= 2;      // lanes per sequence
+    }
+    const bool offs = flat && !p.prep_in_kernel;            // the score stage is handed the prep launch's flat offsets
+    const bool offs_ok = B <= 1024 || !flat || offs;        // (beyond 1 024 sequences no workgroup sums the lengths in front of its own)
+    const bool lm_tags = m->lm.on && !m->P && !scores;      // bs_label_map_path of this call: the output matrix is a label map, tags only
+    switch (m->kind) {
+        case KIND_IFST:
+            if (!m->compact_on) return plan_chain_and_decode(m, p, flat, scores, offs, lm_tags, offs_ok);
+            if (L > 1024) return fail(FARNN_ERANGE, "compact recurrence: more than 1024 positions%s%s");
+            // ONE launch (compact_tag.hip.h: both chains of a sequence in LDS, label-map scores, argmax decode) where it
+            // applies; FARNN_NOFUSE=1: round 2's two launches
+            if (m->bmTok && lm_tags && !m->use_crf && !tun(TUN_NOFUSE) && compact_tag_fits(m->V, m->S, L) && offs_ok) {
+                p.rec = REC_COMPACT_TAG; p.fused = true;
+                p.lds = (size_t)compact_tag_lds(L, m->bmNS).total * 4;
+                p.nlk = m->nl == FARNN_NL_NONE ? 0 : m->nl == FARNN_NL_RELU ? 1 : 2;
+                p.NW = (m->S + 31) / 32;                         // 32-bit words of a bitmap row in use
+                return FARNN_OK;
+            }
+            p.rec = REC_COMPACT_CHAIN;
+            return plan_score_decode(m, p, flat, scores, offs);
+        case KIND_FST4:
+        case KIND_IND1:
+            p.score = m->kind == KIND_FST4 ? SCORE_FST4 : SCORE_IND1;
+            return plan_chain(m, p, false, lm_tags, offs_ok);
+        case KIND_DECOMP:
+            if (m->dense_decomp) return plan_chain_and_decode(m, p, flat, scores, offs, lm_tags, offs_ok);
+            plan_decomp_recurrence(m, p, !m->use_crf, offs_ok);
+            return p.fused ? FARNN_OK : plan_score_decode(m, p, flat, scores, offs);
+        case KIND_DECOMP0:
+            plan_decomp_recurrence(m, p, false, offs_ok);
+            p.score = SCORE_DECOMP0;
+            return m->use_crf ? plan_viterbi(m, p, false) : FARNN_OK;
+        case KIND_DECOMP1: {
+            p.score = SCORE_DECOMP1;
+            const int MT = (m->S + 15) / 16, NT = (m->RO + 15) / 16;
+            p.d1_mfma = m->d1_BSSp && m->ws.d1_br && decomp1_mfma_lds_bytes(MT, NT) <= 80 * 1024;
+            if (p.d1_mfma && NT > 5) return fail(FARNN_ERANGE, "decomp_ind1: output rank above 80 on the MFMA path%s%s");
+            // its label kernel: one 16-wavefront workgroup per CU when the weights fit in LDS beside the per-wavefront rows
+            p.d1_staged = p.d1_mfma && decomp1_label_lds_bytes(NT * 16, m->RO, m->K, m->Kc, true, 16) <= 150 * 1024;
+            if (m->dense_decomp) {
+                if (int rc = plan_chain(m, p, false, lm_tags, offs_ok)) return rc;
+            } else {
+                p.rec = REC_DECOMP_CHAIN;
+                p.order_valid = false;                           // (this kind's decomp_chain launch walks the batch in order)
+            }
+            return m->use_crf ? plan_viterbi(m, p, false) : FARNN_OK;
+        }
+        default:
+            return fail(FARNN_EINVAL, "tag: unknown model kind%s%s");
+    }
+}
+
+// What the reporting functions answer while no call has been planned (a new handle, or farnn_set_compact changed its form): the
+// recurrence kernel the model's kind defaults to, nothing fused.
+static TagPlan unplanned(const farnn_model *m) {
+    TagPlan p;
+    const bool decomp = !m->dense_decomp && (m->kind == KIND_DECOMP || m->kind == KIND_DECOMP1 || m->kind == KIND_DECOMP0);
+    p.rec = m->compact_on ? REC_COMPACT_CHAIN : !decomp ? REC_CHAIN_KERNEL : !m->rows.ok ? REC_DECOMP_CHAIN
+            : (m->dw.farnn == 0 && m->dw.R <= DG_ROWS && !tun(TUN_DECOMP_NOREGS)) ? REC_DECOMP_REGS : REC_DECOMP_ROWS;
+    return p;
+}
+
 extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
     if (!m) return "";
     TunScope tun_scope(&m->tun);
+    const TagPlan p = m->plan.planned ? m->plan : unplanned(m);
     switch (which) {
         case KERN_CHAIN:
-            if (m->compact_on) return m->last_fused ? "compact_tag_kernel<fused: both chains + label-map scores + decode>" : "compact_chain_kernel";
-            if (m->last_regs && m->last_fused && m->use_crf) return "chain_viterbi_kernel<fused: recurrence + scores + CRF decode>";
-            if (m->last_regs && m->rgeom.wide) return m->last_fused ? "chain_wide_kernel<fused: scores + decode beside the recurrence>" : "chain_wide_kernel";
-            if (m->last_regs) return m->last_fused ? "chain_regs_kernel<fused: scores + decode beside the recurrence>"
-                                                   : (m->last_half ? "chain_regs_kernel<f16 blocks>" : "chain_regs_kernel");
-            if (m->dense_decomp) return "chain_kernel";
-            if (m->kind == KIND_DECOMP && m->last_fused && m->last_wave) return "decomp_regs_kernel<fused: scores + decode beside the recurrence>";
-            if (m->kind == KIND_DECOMP || m->kind == KIND_DECOMP1 || m->kind == KIND_DECOMP0)
-                return m->rows.ok ? ((m->last_wave || (m->calls == 0 && m->dw.farnn == 0 && m->dw.R <= DG_ROWS && !tun(TUN_DECOMP_NOREGS))) ? "decomp_regs_kernel" : "decomp_rows_kernel") : "decomp_chain_kernel";
-            return "chain_kernel";
+            switch (p.rec) {
+                case REC_COMPACT_TAG: return "compact_tag_kernel<fused: both chains + label-map scores + decode>";
+                case REC_COMPACT_CHAIN: return "compact_chain_kernel";
+                case REC_CHAIN_VITERBI: return "chain_viterbi_kernel<fused: recurrence + scores + CRF decode>";
+                case REC_CHAIN_WIDE:
+                case REC_CHAIN_WIDE_PAIRED: return p.fused ? "chain_wide_kernel<fused: scores + decode beside the recurrence>" : "chain_wide_kernel";
+                case REC_CHAIN_REGS: return p.fused ? "chain_regs_kernel<fused: scores + decode beside the recurrence>"
+                                                    : (p.half ? "chain_regs_kernel<f16 blocks>" : "chain_regs_kernel");
+                case REC_DECOMP_REGS: return p.fused ? "decomp_regs_kernel<fused: scores + decode beside the recurrence>" : "decomp_regs_kernel";
+                case REC_DECOMP_ROWS: return "decomp_rows_kernel";
+                case REC_DECOMP_CHAIN: return "decomp_chain_kernel";
+                default: return "chain_kernel";
+            }
+        // the score slot is named by the model's kind, whatever the last call launched; m->last_lm_score (tag_host.hip.h) is the one
+        // remembered field beside the plan
         case KERN_SCORE: return m->kind == KIND_FST4 ? "fst4_score_kernel"
                               : (m->kind == KIND_IND1 ? "ind1_score_kernel"
                               : (m->kind == KIND_DECOMP1 ? (m->d1_BSSp ? "decomp1_br_mfma_kernel+decomp1_label_kernel" : "decomp1_score_kernel")
@@ -154,255 +393,220 @@ extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
     }
 }
 
-// ---- the hot path ----------------------------------------------------------------------------
+// ---- the hot path: launch from the plan -----------------------------------------------------------
+// The helpers below fill parameter structs from the model and the plan, and launch; none of them decides anything.
 
-// the register-fed recurrence's view of a call (chain_regs_params.hip.h); the hand-off words are filled in by the callers that use them
-static RegsParams make_regs_params(farnn_model *m, const int64_t *x, const int64_t *len, int B, int full) {
+// template selection, in the style of with_chain_slots (train_host.hip.h)
+template <typename F>
+static int with_chain_form(int nch, int fq, F &&go) {          // chain_kernel<NCH, _, FQ>: the fast-path widths exist for NCH = 1 only
+    if (nch == 2) return go(int_c<2>(), int_c<0>());
+    if (nch == 4) return go(int_c<4>(), int_c<0>());
+    return fq == 1 ? go(int_c<1>(), int_c<1>()) : fq == 2 ? go(int_c<1>(), int_c<2>()) : fq == 3 ? go(int_c<1>(), int_c<3>())
+         : fq == 4 ? go(int_c<1>(), int_c<4>()) : fq == 5 ? go(int_c<1>(), int_c<5>()) : fq == 6 ? go(int_c<1>(), int_c<6>())
+         : go(int_c<1>(), int_c<0>());
+}
+template <typename F>
+static int with_hist_ib4(int ib4, F &&go) {                    // viterbi_hist_kernel<IB4, _>: K / 32 = 0 .. 6
+    return ib4 == 0 ? go(int_c<0>()) : ib4 == 1 ? go(int_c<1>()) : ib4 == 2 ? go(int_c<2>()) : ib4 == 3 ? go(int_c<3>())
+         : ib4 == 4 ? go(int_c<4>()) : ib4 == 5 ? go(int_c<5>()) : go(int_c<6>());
+}
+template <typename F>
+static int with_score_columns(int kch, F &&go) {               // score_tile_kernel<KCH>: 64-column chunks of the scores, 1 .. 4
+    return kch == 1 ? go(int_c<1>()) : kch == 2 ? go(int_c<2>()) : kch == 3 ? go(int_c<3>()) : go(int_c<4>());
+}
+template <typename F>
+static int with_bitmap_words(int nw, F &&go) {                 // compact_tag_kernel<NW, _>: 32-bit words of a bitmap row, 1 .. 4
+    return nw <= 1 ? go(int_c<1>()) : nw == 2 ? go(int_c<2>()) : nw == 3 ? go(int_c<3>()) : go(int_c<4>());
+}
+
+static ScoreParams make_score_params(farnn_model *m, const TagPlan &pl, const int64_t *len, int32_t *tags, int64_t *flat, float *scores) {
+    ScoreParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = m->ws.A; p.Bk = m->ws.Bk; p.OT = m->OT; p.OTm = m->OTm; p.c16 = m->c16; p.P = m->P; p.trT = m->tr; p.len = len;
+    p.offs = (flat && !pl.prep_in_kernel) ? m->ws.offs : nullptr; p.tags = tags; p.flat = flat; p.scores = scores;
+    p.crf_scores = m->ws.crf_scores;
+    p.B = pl.B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.K = m->K; p.Kp = m->Kp; p.Kc = m->Kc;
+    p.kch = m->Kc / 64;
+    p.full = pl.full; p.use_crf = m->use_crf; p.o_idx = m->o_idx; p.threshold = m->threshold;
+    p.dbg = tun(TUN_DBG);
+    p.kz = (m->kind == KIND_IFST && m->use_crf && !tun(TUN_NOKZ)) ? m->C : 0;      // the library appended the two zero rows itself
+    p.lm = m->lm;
+    return p;
+}
+
+// The register-fed recurrence (chain_regs_params.hip.h), with the scores + decode beside it when the plan fused them.
+// The hand-off words of the one-launch forms (chain_regs.hip.h / decomp_regs.hip.h + beside.hip.h) and their launch counter:
+// a launch's epoch is (the counter >> BS_EPOCH_SHIFT) + 1, read from device memory by the kernel; every launch adds exactly
+// BS_EPOCH_SPAN to the counter whatever its batch size (beside.hip.h, bs_launch_epoch).  Nothing per launch comes from the host and
+// nothing is ever reset: the step replays from a HIP graph as the very same launch, and graphs captured at different batch sizes
+// and eager calls may interleave on a handle (stream-ordered).  The words are zeroed once, when the workspace is allocated.
+static void handoff_words(farnn_model *m, unsigned long long **prog, unsigned long long **arr, unsigned long long **done) {
+    *prog = m->ws.hs; *arr = m->ws.hs + (size_t)2 * m->ws.B; *done = m->ws.hs + (size_t)3 * m->ws.B + 16;      // (the counter on a 128-byte line of its own)
+}
+
+static int launch_chain_regs_form(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
     const RegsGeom &rg = m->rgeom;
+    const bool mx = m->semiring == FARNN_SEMIRING_MAX;
     RegsParams rp;
     memset(&rp, 0, sizeof(rp));
     rp.Mf = m->Mf; rp.Mb = m->Mb; rp.blk = (long long)m->geom.SR * m->SP;
     rp.o = m->o; rp.h0 = m->h0; rp.hT = m->hT; rp.x = x; rp.len = len;
-    rp.order = m->order_valid ? m->ws.order : nullptr; rp.sort = m->sort_in_kernel ? 1 : 0;
-    rp.A = m->ws.A; rp.Bk = m->ws.Bk; rp.B = B; rp.L = m->curL; rp.S = m->S; rp.SP = m->SP; rp.CPR = rg.CPR; rp.V = m->V;
+    rp.order = pl.order_valid ? m->ws.order : nullptr; rp.sort = pl.sort_in_kernel ? 1 : 0;
+    rp.A = m->ws.A; rp.Bk = m->ws.Bk; rp.B = pl.B; rp.L = pl.L; rp.S = m->S; rp.SP = m->SP; rp.CPR = rg.CPR; rp.V = m->V;
     rp.G = rg.G; rp.RPG = rg.RPG; rp.RQ = rg.RQ; rp.D = rg.D; rp.PS = rg.PS; rp.pair = rg.wide ? 0 : 1;
-    rp.nl = m->nl; rp.full = full; rp.dbg = tun(TUN_DBG);
-    rp.dest = (!rg.wide && m->semiring != FARNN_SEMIRING_MAX && !tun(TUN_NODEST)) ? 1 : 0;     // chain_dest.hip.h
+    rp.nl = m->nl; rp.full = pl.full; rp.dbg = tun(TUN_DBG);
+    rp.dest = pl.dest ? 1 : 0; rp.half = pl.half ? 1 : 0; rp.row80 = pl.row80 ? 1 : 0;          // chain_dest.hip.h
     rp.Mf16 = m->Mf16; rp.Mb16 = m->Mb16; rp.blk16 = (long long)m->SP * RD_XS * 2;              // (null: no image, build_half_image)
     rp.o_ones = (!m->o || m->o_ones) ? 1 : 0;                                                    // (build_output_matrix)
-    return rp;
-}
-
-// The hand-off words of the one-launch forms (chain_regs.hip.h / decomp_regs.hip.h + beside.hip.h) and their launch counter.
-// A launch's epoch is (the counter >> BS_EPOCH_SHIFT) + 1, read from device memory by the kernel; every launch adds exactly
-// BS_EPOCH_SPAN to the counter whatever its batch size (beside.hip.h, bs_launch_epoch).  Nothing per launch comes from the host and
-// nothing is ever reset: the step replays from a HIP graph as the very same launch, and graphs captured at different batch sizes
-// and eager calls may interleave on a handle (stream-ordered).  The words are zeroed once, when the workspace is allocated.
-static int handoff_words(farnn_model *m, unsigned long long **prog, unsigned long long **arr, unsigned long long **done) {
-    *prog = m->ws.hs; *arr = m->ws.hs + (size_t)2 * m->ws.B; *done = m->ws.hs + (size_t)3 * m->ws.B + 16;      // (the counter on a 128-byte line of its own)
-    return FARNN_OK;
-}
-
-// fuse_sp != nullptr: ask for the fused launch (scores + argmax decode as the chain kernel's epilogue); *fused tells
-// whether the geometry allowed it (else the caller launches the score kernel itself)
-static int launch_chain(farnn_model *m, const int64_t *x, const int64_t *len, int B, int L, int full,
-                        hipStream_t s, const ScoreParams *fuse_sp = nullptr, bool *fused = nullptr) {
-    const ChainGeom &g = m->geom;
-    if (fused) *fused = false;
-    m->last_regs = false;
-    m->last_half = false;
-    // ---- the register-fed kernel (chain_regs.hip.h) where its geometry applies: S <= 72, two workgroups per compute unit, or
-    // its wide form (chain_wide.hip.h): 72 < S <= 128, one workgroup per compute unit.
-    // With fuse_sp (threshold/argmax decode, K <= 256) the scores and the decode run beside the recurrence: ONE launch.
-    if (m->rgeom.ok && !tun(TUN_NOREGS)) {
-        const RegsGeom &rg = m->rgeom;
-        const size_t lds_cap = rg.wide ? 158 * 1024 : 80 * 1024;
-        bool score = fuse_sp && m->ws.hs && m->OTm && m->c16 >= 1 && m->c16 <= (rg.wide ? RGW_NG : RG_NG) && m->Kc <= 256 && m->curL <= 31 * RG_TT &&
-                     (B <= 1024 || !fuse_sp->flat || fuse_sp->offs) && !tun(TUN_NOFUSE);
-        // Which form is the faster one was measured, and the faster one is the default.  S <= 72 with a label-map output matrix (tags
-        // only): the recurrence-only kernel followed by the label-map score launch (K2l).  Round 5 kept ONE launch (the scores and
-        // the decode beside the recurrence: north_star's form) while 2 B <= compute units, on measurements at B = 64 / 256 / 1 024 and
-        // L = 64 only; round 6's grid (scripts/gpu_r06_dispatch_grid.py -> profiles/r06_dispatch_grid.txt: B = 16..128 x L = 16..100)
-        // has two launches ahead at 32 of its 35 points -- by 5-20 % at the reference's default --seq_max_len 30 and below, within
-        // 1 % either way at L = 64 -- so the rule no longer looks at the batch.  FARNN_FUSE=1 keeps the one launch (what a HIP graph
-        // replays as one node); tests/test_gpu_dispatch_ab.py holds the default to "not the slower form" at nine (B, L) points.
-        if (score && !rg.wide && bs_label_map_path(*fuse_sp) && !tun(TUN_FUSE)) score = false;
-        const bool lm_path = score && bs_label_map_path(*fuse_sp);
-        const bool dest = !rg.wide && m->semiring != FARNN_SEMIRING_MAX && !tun(TUN_NODEST);
-        size_t lds = (size_t)regs_lds(m->curL, m->SP, rg.NP, score ? m->c16 : 0, score ? m->Kc : 0, score, rg.RQ, lm_path, dest).total * sizeof(float);
-        // the wide form PAIRED (two workgroups per compute unit, like S <= 72): a ring of two steps and the label-map path's LDS
-        const bool paired = rg.wide && lm_path && rg.RQ <= 9 && lds <= 80 * 1024 && !tun(TUN_WIDE_UNPAIRED);
-        if (score && lds > lds_cap) {               // the score tiles do not fit (beside a second workgroup): recurrence only
-            score = false;
-            lds = (size_t)regs_lds(m->curL, m->SP, rg.NP, 0, 0, false, rg.RQ, false, dest).total * sizeof(float);
+    if (pl.fused && pl.rec != REC_CHAIN_VITERBI) {
+        handoff_words(m, &rp.prog, &rp.arr, &rp.done);
+        if (pl.host_epoch) {
+            if (++m->epoch_u == 0) { FARNN_HIP_TRY(hipMemsetAsync(m->ws.hs, 0, m->ws.hs_bytes, s)); m->epoch_u = 1; }
+            rp.done = nullptr; rp.epoch_host = m->epoch_u + 0x40000000u;
         }
-        // the destination split's recurrence-only launch on the 16-bit image of a model whose o is absent or all ones keeps `hist` in rows of RD_XS floats
-        // where that fits beside a second workgroup (chain_dest.hip.h: one store per step, chain_regs_one_kernel); where it does not --
-        // the longest sequences this kernel takes -- rows of SP floats and two stores as before
-        bool row80 = false;
-        if (dest && !score && (!m->o || m->o_ones) && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF) && FARNN_STEP_ONESTORE && FARNN_CHAIN_HEAD) {
-            const size_t lds80 = (size_t)regs_lds(m->curL, m->SP, rg.NP, 0, 0, false, rg.RQ, false, dest, true).total * sizeof(float);
-            if (lds80 <= lds_cap) { row80 = true; lds = lds80; }
-        }
-        if (lds <= lds_cap) {
-            RegsParams rp = make_regs_params(m, x, len, B, full);
-            if (score) {
-                int hrc = handoff_words(m, &rp.prog, &rp.arr, &rp.done);
-                if (hrc) return hrc;
-                if (tun(TUN_HOST_EPOCH)) {       // diagnostic A/B: the epoch as a kernel argument (not graph-capturable)
-                    if (++m->epoch_u == 0) { FARNN_HIP_TRY(hipMemsetAsync(m->ws.hs, 0, m->ws.hs_bytes, s)); m->epoch_u = 1; }
-                    rp.done = nullptr; rp.epoch_host = m->epoch_u + 0x40000000u;
-                }
-                rp.spin = tun(TUN_FUSE_SPIN);
-                rp.solo_margin = tun(TUN_SOLO_MARGIN);
-                rp.sp = *fuse_sp;
-                if (fused) *fused = true;
-            }
-            // the 16-bit image where the handle has one (an eligible model, build_half_image): the recurrence-only launch of the
-            // destination split reads half the bytes with half the load instructions; FARNN_NOHALF=1 keeps the f32 blocks
-            rp.half = (rp.dest && !score && m->Mf16 && m->Mb16 && !tun(TUN_NOHALF)) ? 1 : 0;
-            rp.row80 = row80 ? 1 : 0;
-            KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
-            if (paired && score) { rp.D = 2; rp.pair = 1; }
-            const int rc = (paired && score) ? launch_chain_wide_paired(rp, m->semiring == FARNN_SEMIRING_MAX, s, kt.e0, kt.e1)
-                           : rg.wide ? launch_chain_wide(rp, m->semiring == FARNN_SEMIRING_MAX, score, s, kt.e0, kt.e1)
-                                     : launch_chain_regs(rp, m->semiring == FARNN_SEMIRING_MAX, score, s, kt.e0, kt.e1);
-            if (rc) return rc;
-            m->last_regs = true;
-            m->last_half = rp.half != 0;
-            return FARNN_OK;
-        }
+        rp.spin = tun(TUN_FUSE_SPIN);
+        rp.solo_margin = tun(TUN_SOLO_MARGIN);
+        rp.sp = sp;
     }
-    (void)fuse_sp;
+    KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
+#if defined(FARNN_AB)
+    if (pl.rec == REC_CHAIN_VITERBI) return launch_chain_viterbi(rp, sp, mx, s, kt.e0, kt.e1);
+#endif
+    if (pl.rec == REC_CHAIN_WIDE_PAIRED) {
+        rp.D = 2; rp.pair = 1;
+        return launch_chain_wide_paired(rp, mx, s, kt.e0, kt.e1);
+    }
+    return pl.rec == REC_CHAIN_WIDE ? launch_chain_wide(rp, mx, pl.fused, s, kt.e0, kt.e1) : launch_chain_regs(rp, mx, pl.fused, s, kt.e0, kt.e1);
+}
+
+static int launch_chain_kernel(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, hipStream_t s) {
+    const ChainGeom &g = m->geom;
     ChainParams p;
     p.Mf = m->Mf; p.Mb = m->Mb; p.blk = (long long)m->geom.SR * m->SP;
     p.o = m->o; p.h0 = m->h0; p.hT = m->hT; p.x = x; p.len = len; p.A = m->ws.A; p.Bk = m->ws.Bk;
-    p.order = m->order_valid ? m->ws.order : nullptr;
-    p.sort = m->sort_in_kernel ? 1 : 0;
-    p.B = B; p.L = m->curL; p.S = m->S; p.SP = m->SP; p.CPR = g.CPR; p.V = m->V;
+    p.order = pl.order_valid ? m->ws.order : nullptr;
+    p.sort = pl.sort_in_kernel ? 1 : 0;
+    p.B = pl.B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.CPR = g.CPR; p.V = m->V;
     p.NW = g.NW; p.NLD = g.NLD; p.G = g.G; p.LPR = g.LPR; p.RPG = g.RPG; p.RPGp = g.RPGp; p.NQ = g.NQ;
-    p.nl = m->nl; p.full = full; p.dbg = tun(TUN_DBG);
-    // ring shape: a whole step per phase when it fits, KS phases deep
-    int ks = 2, nqp = g.NQ;
-    if (!g.pick_ring(m->curL, m->chain_ks, ks, nqp))
-        return fail(FARNN_ERANGE, "chain kernel: LDS ring does not fit (sequence too long for this S)%s%s");
-    p.KS = ks; p.NQP = nqp; p.PPS = (g.NQ + nqp - 1) / nqp;
-    const size_t lds = g.lds_bytes(m->curL, ks, nqp);
-    dim3 grid(2 * B), block((g.NW + g.NLD + 1) * 64);         // compute + loader + writer wavefronts
+    p.nl = m->nl; p.full = pl.full; p.dbg = tun(TUN_DBG);
+    p.KS = pl.KS; p.NQP = pl.NQP; p.PPS = pl.PPS;
+    const dim3 grid(2 * pl.B), block(pl.block);
     const bool mx = m->semiring == FARNN_SEMIRING_MAX;
-    int rc = FARNN_OK;
-    if (tun(TUN_CHAIN_HELPER) && block.x < 512) block = dim3(block.x + 64);     // experiment: an idle eighth wavefront
     KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
-    const int fq_max = block.x <= 384 ? 6 : 3;
-    const int fq = (g.NCH == 1 && p.PPS == 1 && g.NQ <= fq_max && !tun(TUN_NOFAST)) ? g.NQ : 0;
-    auto go = [&](auto NCH, auto FQ) {
-        return mx ? launch_timed(chain_kernel<NCH(), true, FQ()>, grid, block, lds, s, kt.e0, kt.e1, p)
-                  : launch_timed(chain_kernel<NCH(), false, FQ()>, grid, block, lds, s, kt.e0, kt.e1, p);
-    };
-    if (g.NCH == 1) {
-        if (fq == 1) rc = go(int_c<1>(), int_c<1>());
-        else if (fq == 2) rc = go(int_c<1>(), int_c<2>());
-        else if (fq == 3) rc = go(int_c<1>(), int_c<3>());
-        else if (fq == 4) rc = go(int_c<1>(), int_c<4>());
-        else if (fq == 5) rc = go(int_c<1>(), int_c<5>());
-        else if (fq == 6) rc = go(int_c<1>(), int_c<6>());
-        else rc = go(int_c<1>(), int_c<0>());
-    } else if (g.NCH == 2) rc = go(int_c<2>(), int_c<0>());
-    else if (g.NCH <= 4) rc = go(int_c<4>(), int_c<0>());
-    else return fail(FARNN_ERANGE, "unsupported state count%s%s");
+    const int rc = with_chain_form(pl.NCH, pl.FQ, [&](auto NCH, auto FQ) {
+        return mx ? launch_timed(chain_kernel<NCH(), true, FQ()>, grid, block, pl.lds, s, kt.e0, kt.e1, p)
+                  : launch_timed(chain_kernel<NCH(), false, FQ()>, grid, block, pl.lds, s, kt.e0, kt.e1, p);
+    });
     if (rc) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     return FARNN_OK;
 }
 
-// the recurrence of the three decomposed kinds: rows kernel when packed, else the older kernels
-// fuse_sp != nullptr: ask for the one-launch form (scores + argmax decode beside the recurrence); *fused tells whether the
-// model's kernel and geometry allowed it (else the caller launches the score kernel itself)
-static int launch_decomp_recurrence(farnn_model *m, const int64_t *x, const int64_t *lengths, int B, int full,
-                                    hipStream_t s, const ScoreParams *fuse_sp = nullptr, bool *fused = nullptr) {
-    if (fused) *fused = false;
-    const int *order = m->order_valid ? m->ws.order : nullptr;
-    if (m->n_cu <= 0) m->n_cu = device_cus(m->device);
-    RegsPlan rp;
-    m->last_wave = m->rows.ok && regs_plan(m->rows, m->dw, m->curL, rp);
-    if (m->last_wave) {      // farnn = 0, rank <= 64: four wavefronts per chain, the packed rows in registers
-        BesideParams bs;
-        const BesideParams *use = nullptr;
-        bool score = fuse_sp && m->ws.hs && m->OTm && m->c16 >= 1 && m->c16 <= DG_NG && m->Kc <= 256 && m->curL <= 31 * RG_TT &&
-                     (B <= 1024 || !fuse_sp->flat || fuse_sp->offs) && !tun(TUN_NOFUSE);
-        if (score) {
-            rp.lds_score = regs_score_lds(rp, m->curL, m->SP, m->c16, m->Kc);
-            if (rp.lds_score > 80 * 1024) score = false;
-        }
-        if (score) {
-            memset(&bs, 0, sizeof(bs));
-            bs.A = m->ws.A; bs.Bk = m->ws.Bk; bs.B = B; bs.L = m->curL; bs.SP = m->SP; bs.CPR = m->SP / 4;
-            int hrc = handoff_words(m, &bs.prog, &bs.arr, &bs.done);
-            if (hrc) return hrc;
-            bs.spin = tun(TUN_FUSE_SPIN); bs.dbg = tun(TUN_DBG); bs.sp = *fuse_sp;
-            use = &bs;
-            if (fused) *fused = true;
-        }
-        return launch_decomp_regs(m->rows, m->dw, rp, x, lengths, order, m->sort_in_kernel ? 1 : 0, m->ws.A, m->ws.Bk, B, m->curL,
-                                  full, s, use);
+// the compact handle's recurrence: compact_tag_kernel (the call's one launch) or compact_chain_kernel
+static int launch_compact(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
+    CompactParams cp;
+    cp.bitsF = m->bmF; cp.bitsB = m->bmB; cp.wF = m->bmWF; cp.wB = m->bmWB; cp.o = m->o; cp.h0 = m->h0; cp.hT = m->hT;
+    cp.mF = m->bmMF; cp.mB = m->bmMB; cp.xF = m->bmXF; cp.xB = m->bmXB; cp.tokoff = m->bmTok;
+    cp.x = x; cp.len = len; cp.order = pl.order_valid ? m->ws.order : nullptr; cp.A = m->ws.A; cp.Bk = m->ws.Bk;
+    cp.B = pl.B; cp.L = pl.L; cp.S = m->S; cp.SP = m->SP; cp.V = m->V; cp.nl = m->nl; cp.full = pl.full; cp.dbg = tun(TUN_DBG);
+    KernelTimer kt(m, KERN_CHAIN, s);
+    if (pl.rec == REC_COMPACT_CHAIN) return launch_compact_chain(cp, m->bmNS, s);
+    const int rc = with_bitmap_words(pl.NW, [&](auto NW) {
+        const dim3 grid(pl.B), block(CT_WAVES * 64);
+        if (pl.nlk == 0) return launch(compact_tag_kernel<NW(), 0>, grid, block, pl.lds, s, cp, sp);
+        if (pl.nlk == 1) return launch(compact_tag_kernel<NW(), 1>, grid, block, pl.lds, s, cp, sp);
+        return launch(compact_tag_kernel<NW(), 2>, grid, block, pl.lds, s, cp, sp);
+    });
+    if (rc) return rc;
+    FARNN_HIP_TRY(hipGetLastError());
+    return FARNN_OK;
+}
+
+// the recurrence of the decomposed kinds
+static int launch_decomp_recurrence(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
+    const int *order = pl.order_valid ? m->ws.order : nullptr;
+    const int sort = pl.sort_in_kernel ? 1 : 0;
+    KernelTimer kt(m, KERN_CHAIN, s);
+    if (pl.rec == REC_DECOMP_ROWS)
+        return launch_decomp_rows(m->rows, m->dw, pl.rows, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, pl.rows_cu, s);
+    if (pl.rec == REC_DECOMP_CHAIN) return launch_decomp_chain(m->dw, x, len, order, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s);
+    BesideParams bs;
+    if (pl.fused) {
+        memset(&bs, 0, sizeof(bs));
+        bs.A = m->ws.A; bs.Bk = m->ws.Bk; bs.B = pl.B; bs.L = pl.L; bs.SP = m->SP; bs.CPR = m->SP / 4;
+        handoff_words(m, &bs.prog, &bs.arr, &bs.done);
+        bs.spin = tun(TUN_FUSE_SPIN); bs.dbg = tun(TUN_DBG); bs.sp = sp;
     }
-    RowsPlan pl;
-    if (m->rows.ok && rows_plan(m->rows, m->dw, B, m->curL, pl))
-        return launch_decomp_rows(m->rows, m->dw, pl, x, lengths, order, m->sort_in_kernel ? 1 : 0, m->ws.A, m->ws.Bk, B,
-                                  m->curL, full, m->n_cu, s);
-    return launch_decomp_chain(m->dw, x, lengths, order, m->ws.A, m->ws.Bk, B, m->curL, full, s);
+    return launch_decomp_regs(m->rows, m->dw, pl.regs, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s, pl.fused ? &bs : nullptr);
 }
 
-// fused: the Viterbi kernel computes the scores itself (no score_tile launch went before it)
-static bool viterbi_can_fuse(const farnn_model *m, const ScoreParams &p) {
-    return m->use_crf && !p.scores && !p.P && p.A && p.OT && m->K <= 256 &&
-           viterbi_hist_lds_bytes(m->K, m->Kp, p.SP, p.L, true) <= 158 * 1024 && viterbi_hist_ib4(m->K) <= 6 &&
-           !tun(TUN_VITERBI_BP) && !tun(TUN_VITERBI_UNFUSED);
+static int launch_recurrence(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
+    switch (pl.rec) {
+        case REC_COMPACT_TAG:
+        case REC_COMPACT_CHAIN: return launch_compact(m, pl, x, len, sp, s);
+        case REC_CHAIN_KERNEL: return launch_chain_kernel(m, pl, x, len, s);
+        case REC_DECOMP_REGS:
+        case REC_DECOMP_ROWS:
+        case REC_DECOMP_CHAIN: return launch_decomp_recurrence(m, pl, x, len, sp, s);
+        default: return launch_chain_regs_form(m, pl, x, len, sp, s);
+    }
 }
 
-static int launch_viterbi(farnn_model *m, const ScoreParams &p, int B, hipStream_t s, bool fused = false) {
+static int launch_viterbi(farnn_model *m, const TagPlan &pl, const ScoreParams &p, hipStream_t s) {
     int rc;
-    if (m->K > 256) return fail(FARNN_ERANGE, "Viterbi: more than 256 tags%s%s");
-    const size_t hlds = viterbi_hist_lds_bytes(m->K, m->Kp, p.SP, p.L, fused);
-    // (K >= 224 never takes this form: the transposed transition table alone is 196 KiB -- no IB4 = 7, 8 instantiations)
-    if (hlds <= 158 * 1024 && viterbi_hist_ib4(m->K) <= 6 && !tun(TUN_VITERBI_BP)) {
-        // partition history in LDS, back-pointers recomputed along the path
+    const int B = pl.B;
+    if (pl.viterbi == VITERBI_HIST) {
+        const bool fused = pl.score == SCORE_VITERBI_FUSED;
         const int threads = viterbi_hist_score_threads(m->K, fused);
-        auto go = [&](auto N) {
-            return fused ? launch(viterbi_hist_kernel<N(), true>, dim3(B), dim3(threads), hlds, s, p)
-                         : launch(viterbi_hist_kernel<N(), false>, dim3(B), dim3(threads), hlds, s, p);
-        };
-        rc = FARNN_OK;
-        switch (viterbi_hist_ib4(m->K)) {
-            case 0: rc = go(int_c<0>()); break;
-            case 1: rc = go(int_c<1>()); break;
-            case 2: rc = go(int_c<2>()); break;
-            case 3: rc = go(int_c<3>()); break;
-            case 4: rc = go(int_c<4>()); break;
-            case 5: rc = go(int_c<5>()); break;
-            case 6: rc = go(int_c<6>()); break;
-        }
-        if (rc) return rc;
-        FARNN_HIP_TRY(hipGetLastError());
-        return FARNN_OK;
+        rc = with_hist_ib4(pl.ib4, [&](auto N) {
+            return fused ? launch(viterbi_hist_kernel<N(), true>, dim3(B), dim3(threads), pl.viterbi_lds, s, p)
+                         : launch(viterbi_hist_kernel<N(), false>, dim3(B), dim3(threads), pl.viterbi_lds, s, p);
+        });
+    } else {
+        const int threads = round_up(4 * m->K, 64);
+        auto go = [&](auto N) { return launch(viterbi_kernel<N()>, dim3(B), dim3(threads), pl.viterbi_lds, s, p); };
+        if (pl.ib4 == 2) rc = go(int_c<2>());            // K <= 32
+        else if (pl.ib4 == 4) rc = go(int_c<4>());       // K <= 64
+        else if (pl.ib4 == 9) rc = go(int_c<9>());       // K <= 144
+        else if (pl.ib4 == 13) rc = go(int_c<13>());     // K <= 208
+        else rc = go(int_c<16>());                       // K <= 256
     }
-    if (fused) return fail(FARNN_EINVAL, "Viterbi: the fused form needs the history in LDS%s%s");
-    // long sequences: two partition rows + stored back-pointers
-    const size_t vlds = viterbi_lds_bytes(m->K, m->Kp, p.L);
-    const int threads = round_up(4 * m->K, 64);
-    auto go = [&](auto N) { return launch(viterbi_kernel<N()>, dim3(B), dim3(threads), vlds, s, p); };
-    const int ib4 = viterbi_ib4(m->K);
-    if (ib4 == 2) rc = go(int_c<2>());            // K <= 32
-    else if (ib4 == 4) rc = go(int_c<4>());       // K <= 64
-    else if (ib4 == 9) rc = go(int_c<9>());       // K <= 144
-    else if (ib4 == 13) rc = go(int_c<13>());     // K <= 208
-    else rc = go(int_c<16>());                    // K <= 256
     if (rc) return rc;
     FARNN_HIP_TRY(hipGetLastError());
     return FARNN_OK;
 }
 
-static int launch_decomp1_score(farnn_model *m, const int64_t *x, const int64_t *len, int B, int full,
+// the Viterbi launch behind the score kernels of the decomposed independent=0 / independent=1 models (they left the emissions in crf_scores)
+static int launch_viterbi_tail(farnn_model *m, const TagPlan &pl, const int64_t *len, int32_t *tags, int64_t *flat, hipStream_t s) {
+    ScoreParams v;
+    memset(&v, 0, sizeof(v));
+    v.trT = m->tr; v.len = len; v.offs = flat ? m->ws.offs : nullptr; v.tags = tags; v.flat = flat;
+    v.crf_scores = m->ws.crf_scores; v.B = pl.B; v.L = pl.L; v.K = m->K; v.Kp = m->Kp;
+    v.full = pl.full; v.use_crf = 1; v.o_idx = m->o_idx; v.threshold = m->threshold;
+    return launch_viterbi(m, pl, v, s);
+}
+
+static int launch_decomp1_score(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len,
                                 int32_t *tags, int64_t *flat, float *scores, hipStream_t s) {
+    const int B = pl.B, full = pl.full;
     Decomp1ScoreParams p;
     p.A = m->ws.A; p.Bk = m->ws.Bk; p.Vgen = m->dw.Vgen; p.S1 = m->dw.S1; p.S2 = m->dw.S2; p.W = m->dw.W;
     p.S1o = m->d1_S1o; p.S2o = m->d1_S2o; p.CoutT = m->d1_CoutT; p.P = m->P;
     p.x = x; p.len = len; p.offs = flat ? m->ws.offs : nullptr;
     p.tags = tags; p.flat = flat; p.scores = scores; p.crf_scores = m->ws.crf_scores;
-    p.B = B; p.L = m->curL; p.S = m->S; p.SP = m->SP; p.R = m->R; p.Rp = m->Rp; p.RO = m->RO; p.ROp = m->ROp;
+    p.B = B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.R = m->R; p.Rp = m->Rp; p.RO = m->RO; p.ROp = m->ROp;
     p.V = m->V;
     p.K = m->K; p.Kp = m->Kp; p.Kc = m->Kc;
     p.full = full; p.use_crf = m->use_crf; p.o_idx = m->o_idx; p.threshold = m->threshold;
     int rc;
     KernelTimer kt(m, KERN_SCORE, s);
-    Decomp1MfmaParams qm;
-    qm.base = p; qm.BSSp = m->d1_BSSp; qm.S1oP = m->d1_S1oP; qm.S2oP = m->d1_S2oP; qm.br = m->ws.d1_br;
-    if (!full) qm.base.offs = m->ws.offs;       // farnn_tag computes the flat offsets for this path even without flat output
-    qm.MT = (m->S + 15) / 16; qm.NT = (m->RO + 15) / 16; qm.KQ4 = (m->S + 15) / 16;
-    const size_t mlds = decomp1_mfma_lds_bytes(qm.MT, qm.NT);
-    if (m->d1_BSSp && m->ws.d1_br && mlds <= 80 * 1024) {
+    if (pl.d1_mfma) {
+        Decomp1MfmaParams qm;
+        qm.base = p; qm.BSSp = m->d1_BSSp; qm.S1oP = m->d1_S1oP; qm.S2oP = m->d1_S2oP; qm.br = m->ws.d1_br;
+        if (!full) qm.base.offs = m->ws.offs;       // farnn_tag computes the flat offsets for this path even without flat output
+        qm.MT = (m->S + 15) / 16; qm.NT = (m->RO + 15) / 16; qm.KQ4 = (m->S + 15) / 16;
+        const size_t mlds = decomp1_mfma_lds_bytes(qm.MT, qm.NT);
         // persistent: two workgroups per CU, every wavefront owns a contiguous slice of the live tokens
-        if (m->n_cu <= 0) m->n_cu = device_cus(m->device);
         const int nwg = std::min(2 * m->n_cu, (B * p.L + 3) / 4);
         auto go = [&](auto N) { return launch(decomp1_br_mfma_kernel<N()>, dim3(nwg), dim3(256), mlds, s, qm); };
         switch (qm.NT) {
@@ -410,14 +614,12 @@ static int launch_decomp1_score(farnn_model *m, const int64_t *x, const int64_t 
             case 2: rc = go(int_c<2>()); break;
             case 3: rc = go(int_c<3>()); break;
             case 4: rc = go(int_c<4>()); break;
-            case 5: rc = go(int_c<5>()); break;
-            default: return fail(FARNN_ERANGE, "decomp_ind1: output rank above 80 on the MFMA path%s%s");
+            default: rc = go(int_c<5>()); break;
         }
         if (rc) return rc;
         FARNN_HIP_TRY(hipGetLastError());
         const int NC = qm.NT * 16;
-        // one 16-wavefront workgroup per CU when the weights fit in LDS beside the per-wavefront rows
-        const bool staged = decomp1_label_lds_bytes(NC, m->RO, m->K, m->Kc, true, 16) <= 150 * 1024;
+        const bool staged = pl.d1_staged;
         const int lthreads = staged ? 1024 : 256;
         const size_t llds = decomp1_label_lds_bytes(NC, m->RO, m->K, m->Kc, staged, lthreads / 64);
         const int lgrid = std::min((staged ? 1 : 4) * m->n_cu, (B * p.L + lthreads / 64 - 1) / (lthreads / 64));
@@ -433,130 +635,57 @@ static int launch_decomp1_score(farnn_model *m, const int64_t *x, const int64_t 
         decomp1_score_kernel<<<dim3(p.L, B), dim3(256), lds, s>>>(p);
     }
     FARNN_HIP_TRY(hipGetLastError());
-    if (m->use_crf) {
-        ScoreParams v;
-        memset(&v, 0, sizeof(v));
-        v.trT = m->tr; v.len = len; v.offs = flat ? m->ws.offs : nullptr; v.tags = tags; v.flat = flat;
-        v.crf_scores = m->ws.crf_scores; v.B = B; v.L = m->curL; v.K = m->K; v.Kp = m->Kp;
-        v.full = full; v.use_crf = 1; v.o_idx = m->o_idx; v.threshold = m->threshold;
-        if ((rc = launch_viterbi(m, v, B, s))) return rc;
-    }
-    return FARNN_OK;
+    return pl.viterbi ? launch_viterbi_tail(m, pl, len, tags, flat, s) : FARNN_OK;
 }
 
-static int launch_decomp0_score(farnn_model *m, const int64_t *x, const int64_t *len, int B, int full,
+static int launch_decomp0_score(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len,
                                 int32_t *tags, int64_t *flat, float *scores, hipStream_t s) {
     Decomp0ScoreParams p;
     p.A = m->ws.A; p.Bk = m->ws.Bk; p.Vgen = m->d0_Vgen; p.S1 = m->dw.S1; p.S2 = m->dw.S2; p.CT = m->d0_CT;
     p.S1w = m->d0_S1w; p.S2w = m->d0_S2w; p.CwT = m->d0_CwT; p.P = m->P;
     p.x = x; p.len = len; p.offs = flat ? m->ws.offs : nullptr;
     p.tags = tags; p.flat = flat; p.scores = scores; p.crf_scores = m->ws.crf_scores;
-    p.B = B; p.L = m->curL; p.S = m->S; p.SP = m->SP; p.R = m->R; p.Rp = m->Rp; p.RW = m->RW; p.RWp = m->RWp;
+    p.B = pl.B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.R = m->R; p.Rp = m->Rp; p.RW = m->RW; p.RWp = m->RWp;
     p.V = m->V;
     p.K = m->K; p.Kp = m->Kp; p.Kc = m->Kc;
-    p.full = full; p.use_crf = m->use_crf; p.o_idx = m->o_idx; p.threshold = m->threshold;
+    p.full = pl.full; p.use_crf = m->use_crf; p.o_idx = m->o_idx; p.threshold = m->threshold;
     const size_t lds = decomp0_score_lds_bytes(m->SP, m->Rp, m->RWp, m->Kc);
-    int rc;
-    if ((rc = raise_lds_limit(decomp0_score_kernel, lds))) return rc;
+    if (int rc = raise_lds_limit(decomp0_score_kernel, lds)) return rc;
     KernelTimer kt(m, KERN_SCORE, s);
-    decomp0_score_kernel<<<dim3((p.L + D0_TOK - 1) / D0_TOK, B), dim3(256), lds, s>>>(p);
+    decomp0_score_kernel<<<dim3((p.L + D0_TOK - 1) / D0_TOK, pl.B), dim3(256), lds, s>>>(p);
     FARNN_HIP_TRY(hipGetLastError());
-    if (m->use_crf) {
-        ScoreParams v;
-        memset(&v, 0, sizeof(v));
-        v.trT = m->tr; v.len = len; v.offs = flat ? m->ws.offs : nullptr; v.tags = tags; v.flat = flat;
-        v.crf_scores = m->ws.crf_scores; v.B = B; v.L = m->curL; v.K = m->K; v.Kp = m->Kp;
-        v.full = full; v.use_crf = 1; v.o_idx = m->o_idx; v.threshold = m->threshold;
-        if ((rc = launch_viterbi(m, v, B, s))) return rc;
-    }
-    return FARNN_OK;
+    return pl.viterbi ? launch_viterbi_tail(m, pl, len, tags, flat, s) : FARNN_OK;
 }
 
-static ScoreParams make_score_params(farnn_model *m, const int64_t *len, int B, int full, int32_t *tags,
-                                     int64_t *flat, float *scores) {
-    ScoreParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = m->ws.A; p.Bk = m->ws.Bk; p.OT = m->OT; p.OTm = m->OTm; p.c16 = m->c16; p.P = m->P; p.trT = m->tr; p.len = len;
-    p.offs = (flat && !m->prep_in_kernel) ? m->ws.offs : nullptr; p.tags = tags; p.flat = flat; p.scores = scores;
-    p.crf_scores = m->ws.crf_scores;
-    p.B = B; p.L = m->curL; p.S = m->S; p.SP = m->SP; p.K = m->K; p.Kp = m->Kp; p.Kc = m->Kc;
-    p.kch = m->Kc / 64;
-    p.full = full; p.use_crf = m->use_crf; p.o_idx = m->o_idx; p.threshold = m->threshold;
-    p.dbg = tun(TUN_DBG);
-    p.kz = (m->kind == KIND_IFST && m->use_crf && !tun(TUN_NOKZ)) ? m->C : 0;      // the library appended the two zero rows itself
-    p.lm = m->lm;
-    return p;
-}
-
-static int launch_score_decode(farnn_model *m, const int64_t *len, int B, int full, int32_t *tags,
-                               int64_t *flat, float *scores, hipStream_t s) {
-    ScoreParams p = make_score_params(m, len, B, full, tags, flat, scores);
-    if (viterbi_can_fuse(m, p)) {          // stash -> scores -> Viterbi -> tags in one kernel
-        KernelTimer kt(m, KERN_SCORE, s);
-        return launch_viterbi(m, p, B, s, true);
+// the score / decode launch(es) behind the recurrence; one KERN_SCORE timer around whatever runs here
+static int launch_score(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &p,
+                        int32_t *tags, int64_t *flat, float *scores, hipStream_t s) {
+    switch (pl.score) {
+        case SCORE_NONE: return FARNN_OK;
+        case SCORE_DECOMP1: return launch_decomp1_score(m, pl, x, len, tags, flat, scores, s);
+        case SCORE_DECOMP0: return launch_decomp0_score(m, pl, x, len, tags, flat, scores, s);
+        default: break;
     }
-    int rc;
-    if (p.lm.on && !p.P && !scores && !m->use_crf && m->S <= LM_MAXS * 2 && (B <= 1024 || !flat || p.offs)) {
-        // K2l: the output matrix is a label map and only tags are asked for -- S multiply-adds and a scan per token, one workgroup
-        // per sequence (score_decode.hip.h).  FARNN_NOLABELMAP=1 (no label map is built then) keeps the matrix form.
-        KernelTimer kt(m, KERN_SCORE, s);
-        label_map_score_kernel<LMS_WAVES><<<B, LMS_WAVES * 64, 0, s>>>(p);
-        FARNN_HIP_TRY(hipGetLastError());
-        m->last_lm_score = true;
-        return FARNN_OK;
-    }
-    m->last_lm_score = false;
-    const size_t lds = score_lds_bytes(m->S, m->Kc);
-    const dim3 grid((p.L + SCORE_TT - 1) / SCORE_TT, B), block(SCORE_WAVES * 64);
     KernelTimer kt(m, KERN_SCORE, s);
-    auto go = [&](auto KCH) { return launch(score_tile_kernel<KCH()>, grid, block, lds, s, p); };
-    switch (p.kch) {
-        case 1: rc = go(int_c<1>()); break;
-        case 2: rc = go(int_c<2>()); break;
-        case 3: rc = go(int_c<3>()); break;
-        default: rc = go(int_c<4>()); break;
+    switch (pl.score) {
+        case SCORE_VITERBI_FUSED: return launch_viterbi(m, pl, p, s);
+        case SCORE_LABEL_MAP:
+            label_map_score_kernel<LMS_WAVES><<<pl.B, LMS_WAVES * 64, 0, s>>>(p);
+            FARNN_HIP_TRY(hipGetLastError());
+            return FARNN_OK;
+        case SCORE_FST4:
+        case SCORE_IND1:
+            return launch_fst4_score(pl.score == SCORE_FST4 ? m->A4 : m->Ms, m->ws.A, m->ws.Bk, m->P, x, len, flat ? m->ws.offs : nullptr,
+                                     tags, flat, scores, pl.B, pl.L, m->S, m->SP, m->C, m->Kc, pl.full,
+                                     m->o_idx, m->threshold, pl.score == SCORE_FST4 ? nullptr : m->Oten, m->V, s);
+        default: break;
     }
+    const size_t lds = score_lds_bytes(m->S, m->Kc);
+    const dim3 grid((p.L + SCORE_TT - 1) / SCORE_TT, pl.B), block(SCORE_WAVES * 64);
+    const int rc = with_score_columns(pl.kch, [&](auto KCH) { return launch(score_tile_kernel<KCH()>, grid, block, lds, s, p); });
     if (rc) return rc;
     FARNN_HIP_TRY(hipGetLastError());
-    if (m->use_crf && (rc = launch_viterbi(m, p, B, s))) return rc;
-    return FARNN_OK;
-}
-
-// the dense-block recurrence followed by scores + decode: ONE launch (the decode is the chain kernel's epilogue) when
-// the decode is the threshold/argmax one and the geometry allows it, else the chain kernel + the score / Viterbi kernels
-static int launch_chain_and_decode(farnn_model *m, const int64_t *x, const int64_t *len, int B, int L, int full,
-                                   int32_t *tags, int64_t *flat, float *scores, hipStream_t s) {
-    int rc;
-    if (!m->use_crf) {
-        const ScoreParams sp = make_score_params(m, len, B, full, tags, flat, scores);
-        bool fused = false;
-        if ((rc = launch_chain(m, x, len, B, L, full, s, &sp, &fused))) return rc;
-        m->last_fused = fused;
-        if (fused) return FARNN_OK;
-    } else {
-        // CRF decode: recurrence + scores + Viterbi in ONE launch (chain_viterbi.hip) where the register-fed recurrence applies and
-        // the decode's LDS fits; else the recurrence kernel followed by the (fused score +) Viterbi kernel
-        m->last_fused = false;
-        const ScoreParams sp = make_score_params(m, len, B, full, tags, flat, scores);
-        // The one launch (north_star: "decode fused into the same kernel") exists for S <= 108 and is parity-tested, but is NOT the
-        // default (round 5): a compute unit then holds BOTH chains of a sequence, which run 1 390 cycles per step there against
-        // 780-960 when a long chain shares its unit with a short one, and the decode waits behind them.  Measured at K = 130,
-        // 256 x 64: S = 71 77.7 us in one launch against 72.9 in two (round 4; round 5's recurrence kernel: 69), S = 104 113.8 against
-        // 95.7 (profiles/r04_*, r05_*).  FARNN_CV_ONE=1 selects it.
-        // The production library does not carry the form's 48 kernels: it lives in the A/B build (build.py --probes, -DFARNN_AB).
-#if defined(FARNN_AB)
-        if (tun(TUN_CV_ONE) && m->rgeom.ok && !tun(TUN_NOREGS) && !tun(TUN_NOFUSE) && viterbi_can_fuse(m, sp) &&
-            (B <= 1024 || !flat || sp.offs) && chain_viterbi_fits(m->curL, m->SP, m->rgeom.NP, m->K, m->Kp, m->lm.on != 0, m->rgeom.RQ)) {
-            const RegsParams rp = make_regs_params(m, x, len, B, full);
-            KernelTimer kt(m, KERN_CHAIN, s, /*ext=*/true);
-            if ((rc = launch_chain_viterbi(rp, sp, m->semiring == FARNN_SEMIRING_MAX, s, kt.e0, kt.e1))) return rc;
-            m->last_regs = true; m->last_fused = true;
-            return FARNN_OK;
-        }
-#endif
-        if ((rc = launch_chain(m, x, len, B, L, full, s))) return rc;
-    }
-    return launch_score_decode(m, len, B, full, tags, flat, scores, s);
+    return pl.viterbi ? launch_viterbi(m, pl, p, s) : FARNN_OK;
 }
 
 // forward_RE's view of the scores (model_onehot.py:153-154): the `oo` column (the last one) capped at the threshold
@@ -568,6 +697,7 @@ __global__ void clamp_oo_column_kernel(float *scores, long long rows, int K, int
     }
 }
 
+// order the streams, reserve, plan, then launch from the plan: prep, recurrence, scores + decode
 static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, int32_t B, int32_t L,
                     int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream) {
     TunScope tun_scope(&m->tun);
@@ -598,123 +728,23 @@ static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, in
     // included), so (B, L) only have to fit the capacity: a loop whose batches vary in size or length allocates once
     if (B > m->ws.B || L > m->ws.L)
         if ((rc = farnn_reserve(m, B, L))) return rc;
-    m->curL = L;
-    const int full = mode == FARNN_MODE_FULL;
     m->prof_this_call = m->profiling > 0 && (m->calls++ % m->profiling) == 0;
-    // batch preparation: flat-output offsets and the length-sorted launch order (full mode runs
-    // every sequence for L steps, so there is nothing to balance)
-    const bool want_order = !full && B > 2 && !tun(TUN_NOSORT);
-    // the plain i-FST path needs no prep launch up to B = 1024: the chain workgroups select their sequence
-    // by length rank themselves and the score workgroups sum the lengths in front of theirs
-    m->prep_in_kernel = (m->kind == KIND_IFST || (m->kind == KIND_DECOMP && m->rows.ok)) && B <= 1024 && L <= 1023 &&
-                        !tun(TUN_PREP);
-    m->order_valid = want_order && !m->prep_in_kernel;
-    m->sort_in_kernel = want_order && m->prep_in_kernel;
-    // the decomposed independent=1 scoring kernel slices the batch by flat offsets even when no flat output is asked for
-    const bool want_offs = flat_tags || (m->kind == KIND_DECOMP1 && m->d1_BSSp && !full);
-    if ((want_offs || want_order) && !m->prep_in_kernel) {
+    if (m->n_cu <= 0) m->n_cu = device_cus(m->device);
+    TagPlan pl;
+    if ((rc = plan_tag(m, B, L, mode == FARNN_MODE_FULL, flat_tags != nullptr, scores != nullptr, pl))) return rc;
+    m->plan = pl;
+    if (pl.score == SCORE_LABEL_MAP || pl.score == SCORE_TILE) m->last_lm_score = pl.score == SCORE_LABEL_MAP;
+    if (pl.prep != PREP_NONE) {
         KernelTimer kt(m, KERN_PREP, s);
-        if (B <= 1024) {
-            int G = 1;
-            while (G < 16 && B * G * 2 <= 1024) G *= 2;               // lanes per sequence
-            batch_prep_small_kernel<<<1, round_up(B * G, 64), 0, s>>>(
-                lengths, want_offs ? m->ws.offs : nullptr, want_order ? m->ws.order : nullptr, B, L, G);
-        }
-        else
-            batch_prep_kernel<<<1, 1024, (size_t)(L + 2) * sizeof(int), s>>>(
-                lengths, want_offs ? m->ws.offs : nullptr, want_order ? m->ws.order : nullptr, B, L);
+        int64_t *offs = pl.want_offs ? m->ws.offs : nullptr;
+        int *order = pl.want_order ? m->ws.order : nullptr;
+        if (pl.prep == PREP_SMALL) batch_prep_small_kernel<<<1, round_up(B * pl.prep_G, 64), 0, s>>>(lengths, offs, order, B, L, pl.prep_G);
+        else batch_prep_kernel<<<1, 1024, (size_t)(L + 2) * sizeof(int), s>>>(lengths, offs, order, B, L);
         FARNN_HIP_TRY(hipGetLastError());
     }
-    switch (m->kind) {
-        case KIND_IFST:
-            if (m->compact_on) {
-                if (L > 1024) return fail(FARNN_ERANGE, "compact recurrence: more than 1024 positions%s%s");
-                CompactParams cp;
-                cp.bitsF = m->bmF; cp.bitsB = m->bmB; cp.wF = m->bmWF; cp.wB = m->bmWB; cp.o = m->o; cp.h0 = m->h0; cp.hT = m->hT;
-                cp.mF = m->bmMF; cp.mB = m->bmMB; cp.xF = m->bmXF; cp.xB = m->bmXB; cp.tokoff = m->bmTok;
-                cp.x = x; cp.len = lengths; cp.order = m->order_valid ? m->ws.order : nullptr; cp.A = m->ws.A; cp.Bk = m->ws.Bk;
-                cp.B = B; cp.L = L; cp.S = m->S; cp.SP = m->SP; cp.V = m->V; cp.nl = m->nl; cp.full = full; cp.dbg = tun(TUN_DBG);
-                m->last_fused = false;
-                {
-                    // ONE launch (compact_tag.hip.h: both chains of a sequence in LDS, label-map scores, argmax decode) where it
-                    // applies; FARNN_NOFUSE=1: round 2's two launches
-                    const ScoreParams sp = make_score_params(m, lengths, B, full, tags, flat_tags, scores);
-                    if (m->bmTok && sp.lm.on && !sp.P && !scores && !m->use_crf && !tun(TUN_NOFUSE) &&
-                        compact_tag_fits(m->V, m->S, L) && (B <= 1024 || !flat_tags || sp.offs)) {
-                        const size_t lds = (size_t)compact_tag_lds(L, m->bmNS).total * 4;
-                        const int nlk = m->nl == FARNN_NL_NONE ? 0 : m->nl == FARNN_NL_RELU ? 1 : 2;
-                        const int nw = (m->S + 31) / 32;                       // 32-bit words of a bitmap row in use
-                        KernelTimer kt(m, KERN_CHAIN, s);
-                        auto go = [&](auto NW) {
-                            const dim3 grid(B), block(CT_WAVES * 64);
-                            if (nlk == 0) return launch(compact_tag_kernel<NW(), 0>, grid, block, lds, s, cp, sp);
-                            if (nlk == 1) return launch(compact_tag_kernel<NW(), 1>, grid, block, lds, s, cp, sp);
-                            return launch(compact_tag_kernel<NW(), 2>, grid, block, lds, s, cp, sp);
-                        };
-                        if (nw <= 1) rc = go(int_c<1>()); else if (nw == 2) rc = go(int_c<2>());
-                        else if (nw == 3) rc = go(int_c<3>()); else rc = go(int_c<4>());
-                        if (rc) return rc;
-                        FARNN_HIP_TRY(hipGetLastError());
-                        m->last_fused = true;
-                        return FARNN_OK;
-                    }
-                }
-                {
-                    KernelTimer kt(m, KERN_CHAIN, s);
-                    if ((rc = launch_compact_chain(cp, m->bmNS, s))) return rc;
-                }
-                return launch_score_decode(m, lengths, B, full, tags, flat_tags, scores, s);
-            }
-            return launch_chain_and_decode(m, x, lengths, B, L, full, tags, flat_tags, scores, s);
-        case KIND_FST4:
-            if ((rc = launch_chain(m, x, lengths, B, L, full, s))) return rc;
-            {
-                KernelTimer kt(m, KERN_SCORE, s);
-                return launch_fst4_score(m->A4, m->ws.A, m->ws.Bk, m->P, x, lengths, flat_tags ? m->ws.offs : nullptr,
-                                         tags, flat_tags, scores, B, m->curL, m->S, m->SP, m->C, m->Kc, full,
-                                         m->o_idx, m->threshold, /*Oten*/ nullptr, m->V, s);
-            }
-        case KIND_IND1:
-            if ((rc = launch_chain(m, x, lengths, B, L, full, s))) return rc;
-            {
-                KernelTimer kt(m, KERN_SCORE, s);
-                return launch_fst4_score(m->Ms, m->ws.A, m->ws.Bk, m->P, x, lengths, flat_tags ? m->ws.offs : nullptr,
-                                         tags, flat_tags, scores, B, m->curL, m->S, m->SP, m->C, m->Kc, full,
-                                         m->o_idx, m->threshold, m->Oten, m->V, s);
-            }
-        case KIND_DECOMP: {
-            if (m->dense_decomp) return launch_chain_and_decode(m, x, lengths, B, L, full, tags, flat_tags, scores, s);
-            bool fused = false;
-            {
-                KernelTimer kt(m, KERN_CHAIN, s);
-                if (!m->use_crf) {
-                    const ScoreParams sp = make_score_params(m, lengths, B, full, tags, flat_tags, scores);
-                    if ((rc = launch_decomp_recurrence(m, x, lengths, B, full, s, &sp, &fused))) return rc;
-                } else if ((rc = launch_decomp_recurrence(m, x, lengths, B, full, s))) return rc;
-            }
-            m->last_fused = fused;
-            if (fused) return FARNN_OK;
-            return launch_score_decode(m, lengths, B, full, tags, flat_tags, scores, s);
-        }
-        case KIND_DECOMP0: {
-            {
-                KernelTimer kt(m, KERN_CHAIN, s);
-                if ((rc = launch_decomp_recurrence(m, x, lengths, B, full, s))) return rc;
-            }
-            return launch_decomp0_score(m, x, lengths, B, full, tags, flat_tags, scores, s);
-        }
-        case KIND_DECOMP1: {
-            if (m->dense_decomp) {
-                if ((rc = launch_chain(m, x, lengths, B, L, full, s))) return rc;
-            } else {
-                KernelTimer kt(m, KERN_CHAIN, s);
-                if ((rc = launch_decomp_chain(m->dw, x, lengths, nullptr, m->ws.A, m->ws.Bk, B, m->curL, full, s))) return rc;
-            }
-            return launch_decomp1_score(m, x, lengths, B, full, tags, flat_tags, scores, s);
-        }
-        default:
-            return fail(FARNN_EINVAL, "tag: unknown model kind%s%s");
-    }
+    const ScoreParams sp = make_score_params(m, pl, lengths, tags, flat_tags, scores);
+    if ((rc = launch_recurrence(m, pl, x, lengths, sp, s))) return rc;
+    return launch_score(m, pl, x, lengths, sp, tags, flat_tags, scores, s);
 }
 
 extern "C" int farnn_tag(farnn_model *m, const int64_t *x, const int64_t *lengths, int32_t B, int32_t L,
@@ -883,15 +913,22 @@ extern "C" double farnn_algorithmic_bytes(const farnn_model *m, int64_t valid_to
 
 extern "C" double farnn_kernel_algorithmic_bytes(const farnn_model *m, int32_t which, int64_t valid_tokens) {
     if (!m) return 0.0;
+    TunScope tun_scope(&m->tun);
+    const TagPlan p = m->plan.planned ? m->plan : unplanned(m);
     const double S = m->S, C = m->C, R = m->R, K = m->K, n = (double)valid_tokens;
     if (which == KERN_CHAIN) {
-        if (m->compact_on) return (2.0 * S * m->bmNS * 8 + 8) * n;      // one bit-packed block per direction + the token id
-        if (!m->dense_decomp && (m->kind == KIND_DECOMP || m->kind == KIND_DECOMP1 || m->kind == KIND_DECOMP0))
-            return (R * 4 + 8) * n + (2.0 * S * R + S * S) * 4;
+        switch (p.rec) {
+            case REC_COMPACT_TAG:
+            case REC_COMPACT_CHAIN: return (2.0 * S * m->bmNS * 8 + 8) * n;      // one bit-packed block per direction + the token id
+            case REC_DECOMP_REGS:
+            case REC_DECOMP_ROWS:
+            case REC_DECOMP_CHAIN: return (R * 4 + 8) * n + (2.0 * S * R + S * S) * 4;
+            default: break;
+        }
         // one block per direction + the token id (+ the tag when the decode is this kernel's epilogue); the 16-bit image: what the
         // launched form requests
-        if (m->last_regs && m->last_half) return (2.0 * S * S * 2 + 8) * n;
-        return (2.0 * S * S * 4 + 8 + (m->last_fused ? 4 : 0)) * n + (m->last_fused ? K * S * 4 : 0);
+        if (p.half) return (2.0 * S * S * 2 + 8) * n;
+        return (2.0 * S * S * 4 + 8 + (p.fused ? 4 : 0)) * n + (p.fused ? K * S * 4 : 0);
     }
     if (which == KERN_SCORE) {
         switch (m->kind) {

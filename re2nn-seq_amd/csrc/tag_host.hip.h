@@ -13,6 +13,7 @@
 #include "decomp_chain.hip.h"
 #include "decomp_rows.hip.h"
 #include "chain_regs_params.hip.h"
+#include "tag_plan.hip.h"
 
 using namespace farnn;
 
@@ -57,7 +58,6 @@ struct farnn_model {
     // device-resident, library-owned weights
     float *Mf = nullptr, *Mb = nullptr;     // chain blocks [V][S][SP] (+ transposed)
     unsigned short *Mf16 = nullptr, *Mb16 = nullptr;   // their 16-bit image [V][SP][80] f16, when every entry is an f16 exactly (build_half_image)
-    bool last_half = false;                 // the last recurrence read the 16-bit image
     u64 *bmF = nullptr, *bmB = nullptr, *bmWF = nullptr, *bmWB = nullptr;   // compact form: bit-packed blocks (compact.hip.h)
     int bmNS = 0;                           // 64-bit words per bitmap row; 0: no compact form
     u64 *bmMF = nullptr, *bmMB = nullptr, *bmXF = nullptr, *bmXB = nullptr;   // K1t's planes: T | W, T & W (merge_planes_kernel; S <= 128)
@@ -82,18 +82,15 @@ struct farnn_model {
     int RW = 0, RWp = 0;                    // decomposed independent=0: wildcard factors + label factor
     float *d0_Vgen = nullptr, *d0_CT = nullptr, *d0_S1w = nullptr, *d0_S2w = nullptr, *d0_CwT = nullptr;
     Workspace ws;
-    int curL = 0;                           // the current call's L: every stride of the workspace arrays
     ChainGeom geom;
     RegsGeom rgeom;                         // geometry of the register-fed recurrence kernel (chain_regs.hip.h); rgeom.ok: usable
     unsigned epoch_u = 0;                   // diagnostic FARNN_HOST_EPOCH=1: the round-3 host-side epoch
-    bool last_regs = false;                 // the last recurrence ran on chain_regs_kernel
-    bool last_lm_score = false;             // the last stand-alone score launch was label_map_score_kernel (K2l)
+    TagPlan plan;                           // the plan of the last farnn_tag call (tag_plan.hip.h); plan.planned false: none yet
+    // the one field remembered beside the plan: the last STAND-ALONE score launch was label_map_score_kernel (K2l).  A call that
+    // launches no score kernel leaves it as it was, and farnn_kernel_name(KERN_SCORE) goes on reporting the older call's answer
+    bool last_lm_score = false;
     int chain_ks = 3;
-    bool prep_in_kernel = false, sort_in_kernel = false;
     bool dense_decomp = false;              // decomposed model served by dense per-word blocks + chain_kernel
-    bool order_valid = false;
-    bool last_wave = false;                 // the last decomposed recurrence ran on decomp_regs_kernel
-    bool last_fused = false;                // the last farnn_tag ran the single-launch form (chain + score/decode epilogue)
     int profiling = 0;          // 0 off, N>0: time every N-th farnn_tag call
     long long calls = 0;
     int prof_this_call = 0;
