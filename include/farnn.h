@@ -453,6 +453,70 @@ int  farnn_train_time(farnn_train_ctx *ctx, double *total_ms, int64_t *steps);
  * (three S x S blocks per distinct word of the batch) is allocated by its first step. */
 int  farnn_train_set_semiring(farnn_train_ctx *ctx, int32_t semiring);
 
+/* ---- training step of the decomposed FST (FARNN_S_D_W, --method decompose --independent 0) ----------
+ * Replaces FARNN_S_D_W.forward_local(train=True) + loss.backward() (model_decompose.py:243-456) for farnn = 0/1/2, every
+ * update_nonlinear, the priority layer, and the CE1 loss or (use_crf) the CRF negative log-likelihood, in the SUM semiring.  The max
+ * semiring of this model (--train_mode max) is not built: there is no set_semiring entry.  With csum = C_embed.sum(0) and cwsum =
+ * C_wildcard.sum(0) the two chains are the decomposed i-FST's recurrence on the word table Vgen * csum and the matrix
+ * S1_wildcard diag(cwsum) S2_wildcard^T + wildcard_wildcard (:253, :327-332), and
+ *   score[c] = sum_r Vgen[w,r] C_embed[c,r] (alpha S1)[r] (beta S2)[r] + sum_q C_wildcard[c,q] (alpha S1w)[q] (beta S2w)[q]  (:310-325)
+ * with alpha the forward state before the token and beta the backward state behind it.  Vgen (model_decompose.py:222-241) is an
+ * input; the caller differentiates it from dVgen.  All pointers are DEVICE pointers; matrices are row-major and unpadded.
+ * No sum of the step depends on the order in which workgroups finish: two steps on the same inputs are bit-identical. */
+typedef struct farnn_decomp_fst_train_ctx farnn_decomp_fst_train_ctx;
+
+typedef struct {
+    int32_t V, S, R, Q, K;      /* vocabulary rows, states, rank of the language factors, rank of the wildcard factors, score columns */
+    int32_t nl;                 /* FARNN_NL_* (update_nonlinear)                                               */
+    float   threshold;          /* decode clamp of column K-1 (:365) / K-3 with the CRF (:353)                 */
+    int32_t o_idx;              /* label written for that column (:356, :367)                                  */
+    int32_t farnn;              /* 0 plain recurrence, 1 update gate, 2 update + reset gate (:255-266,:301-306) */
+    float   sigmoid_exponent;   /* k of the gate activation sigmoid(k x) (:97-103)                             */
+    int32_t use_crf;            /* 1: the CRF loss on the scores, K = labels + 2 (START, STOP); decode = Viterbi */
+} farnn_decomp_fst_train_dims;
+
+typedef struct {
+    const float *Vgen;          /* [V][R]   */
+    const float *Ce;            /* [K][R] C_embed       */
+    const float *S1, *S2;       /* [S][R]   */
+    const float *Cw;            /* [K][Q] C_wildcard    */
+    const float *S1w, *S2w;     /* [S][Q] S1_wildcard, S2_wildcard */
+    const float *WW;            /* [S][S] wildcard_wildcard */
+    const float *h0, *hT;       /* [S]      */
+    const float *P;             /* [K][K] priority matrix or NULL */
+    const float *crf_trans;     /* [K][K] crf.transitions (use_crf = 1), else NULL */
+    const float *Wss1, *Wrs1, *bs1;   /* [S][S], [R][S], [S] update gate (farnn >= 1), else NULL */
+    const float *Wss2, *Wrs2, *bs2;   /* reset gate (farnn = 2), else NULL                       */
+} farnn_decomp_fst_train_weights;
+
+typedef struct {
+    float *loss;                /* [1]                                                  */
+    float *dVgen;               /* [V][R]  (rows of words that do not occur are zero)   */
+    float *dCe;                 /* [K][R]  */
+    float *dS1, *dS2;           /* [S][R]  */
+    float *dCw;                 /* [K][Q]  */
+    float *dS1w, *dS2w;         /* [S][Q]  */
+    float *dWW;                 /* [S][S]  */
+    float *dh0, *dhT;           /* [S]     */
+    int32_t *tags;              /* [B][L] decoded labels of this forward pass, -1 at pad positions */
+    float *dtrans;              /* [K][K] gradient of crf.transitions (use_crf = 1), else NULL     */
+    float *dWss1, *dWrs1, *dbs1;      /* gate gradients (farnn >= 1), else NULL */
+    float *dWss2, *dWrs2, *dbs2;      /* (farnn = 2), else NULL                 */
+} farnn_decomp_fst_train_outputs;
+
+int  farnn_decomp_fst_train_create(const farnn_decomp_fst_train_dims *dims, int device, farnn_decomp_fst_train_ctx **out);
+void farnn_decomp_fst_train_destroy(farnn_decomp_fst_train_ctx *ctx);
+/* One step on the given stream; x, lengths, labels as farnn_decomp_ifst_train_step's.  Every FARNN_ERANGE (the CRF limit, more
+ * than 512 states or either rank above 512, the 2^30 element bound with Q counted like R, a launch above 160 KiB of LDS -- the
+ * score head keeps 16 positions' rows of 2 S + 3 R + 3 Q + 2 K floats there) is returned before anything is enqueued: a
+ * refused step leaves the output buffers untouched. */
+int  farnn_decomp_fst_train_step(farnn_decomp_fst_train_ctx *ctx, const farnn_decomp_fst_train_weights *w, const int64_t *x,
+                                 const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                 int64_t valid_tokens, const farnn_decomp_fst_train_outputs *out, void *stream);
+/* as farnn_train_set_profiling / farnn_train_time */
+int  farnn_decomp_fst_train_set_profiling(farnn_decomp_fst_train_ctx *ctx, int32_t enable);
+int  farnn_decomp_fst_train_time(farnn_decomp_fst_train_ctx *ctx, double *total_ms, int64_t *steps);
+
 /* ---- training step of the onehot i-FST (FARNN_S_O_I_S, --method onehot --independent 2) -----------------
  * Replaces FARNN_S_O_I_S.forward_local(train=True) + loss.backward() (model_onehot.py:131-146,351-428,
  * train_onehot.py:156-206) for the sum or the max semiring (farnn_onehot_train_set_semiring) and the CE1 loss: cross-entropy (mean over the valid tokens) of

@@ -118,6 +118,22 @@ class TrainOutputs(C.Structure):
                                           'dWss1', 'dWrs1', 'dbs1', 'dWss2', 'dWrs2', 'dbs2')]
 
 
+class DecompFstTrainDims(C.Structure):
+    _fields_ = [('V', C.c_int32), ('S', C.c_int32), ('R', C.c_int32), ('Q', C.c_int32), ('K', C.c_int32), ('nl', C.c_int32),
+                ('threshold', C.c_float), ('o_idx', C.c_int32), ('farnn', C.c_int32), ('sigmoid_exponent', C.c_float),
+                ('use_crf', C.c_int32)]
+
+
+class DecompFstTrainWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('Vgen', 'Ce', 'S1', 'S2', 'Cw', 'S1w', 'S2w', 'WW', 'h0', 'hT', 'P', 'crf_trans',
+                                          'Wss1', 'Wrs1', 'bs1', 'Wss2', 'Wrs2', 'bs2')]
+
+
+class DecompFstTrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('loss', 'dVgen', 'dCe', 'dS1', 'dS2', 'dCw', 'dS1w', 'dS2w', 'dWW', 'dh0', 'dhT', 'tags',
+                                          'dtrans', 'dWss1', 'dWrs1', 'dbs1', 'dWss2', 'dWrs2', 'dbs2')]
+
+
 class Teacher(C.Structure):
     _fields_ = [('mode', C.c_int32), ('c1', C.c_float), ('pi', C.c_float)]
 
@@ -257,6 +273,13 @@ SIGNATURES = {
     'farnn_decomp_ind1_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_decomp_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_decomp_fst_train_create': (C.c_int, [C.POINTER(DecompFstTrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_decomp_fst_train_destroy': (None, [C.c_void_p]),
+    'farnn_decomp_fst_train_step': (C.c_int, [C.c_void_p, C.POINTER(DecompFstTrainWeights), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                              C.POINTER(DecompFstTrainOutputs), C.c_void_p]),
+    'farnn_decomp_fst_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_decomp_fst_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_ifst_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
@@ -719,6 +742,23 @@ class TrainContext(_TrainContextBase):
         entry = 'farnn_decomp_ifst_teacher_max_train_step' if max_entry else 'farnn_decomp_ifst_teacher_train_step'
         check(getattr(load(), entry)(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, re_ptr, C.byref(t),
                                      int(B), int(L), int(valid_tokens), C.byref(o), stream), entry)
+
+
+class DecompFstTrainContext(_TrainContextBase):
+    """Owns one farnn_decomp_fst_train_ctx* (training step of the decomposed FST, FARNN_S_D_W; include/farnn.h).  Sum semiring
+    only: the entry has no set_semiring."""
+    _create, _destroy, _step = 'farnn_decomp_fst_train_create', 'farnn_decomp_fst_train_destroy', 'farnn_decomp_fst_train_step'
+    _set_profiling, _time = 'farnn_decomp_fst_train_set_profiling', 'farnn_decomp_fst_train_time'
+    _weights, _outputs = DecompFstTrainWeights, DecompFstTrainOutputs
+
+    def __init__(self, V, S, R, Q, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0, sigmoid_exponent=5.0):
+        self._open(DecompFstTrainDims(int(V), int(S), int(R), int(Q), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
+                                      float(sigmoid_exponent), int(bool(use_crf))), device)
+        self.dims = (int(V), int(S), int(R), int(Q), int(K))
+
+    def set_semiring(self, semiring):
+        if semiring != 'sum':
+            raise NotImplementedError('the decomposed FST trains in the sum semiring only (DESIGN.md, row f11)')
 
 
 class OnehotTrainContext(_TrainContextBase):

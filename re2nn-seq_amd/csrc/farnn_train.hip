@@ -1,4 +1,5 @@
-// libfarnn_hip.so -- the five training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the onehot
+// libfarnn_hip.so -- the six training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the decomposed
+// FST on the same chains (farnn_decomp_fst_train_*), the onehot
 // i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*), the onehot independent=1 model (farnn_ind1_train_*) and the
 // decomposed independent=1 model (farnn_decomp_ind1_train_*), and the optimizer step that follows any of them (farnn_optim_*, at
 // the end).  Their own translation unit: the training kernels (train.hip.h: the scores and the loss, shared by the first two
@@ -21,6 +22,7 @@
 #include "fst4_train.hip.h"
 #include "ind1_train.hip.h"
 #include "decomp1_train.hip.h"
+#include "decomp0_train.hip.h"
 #include "decomp1_gated_train.hip.h"
 #include "decomp1_gated_max_train.hip.h"
 #include "train_bucketed_crf.hip.h"
@@ -184,7 +186,8 @@ static int train_validate(const farnn_train_ctx *c, const farnn_train_weights *w
 // Stage 2: host arithmetic only, no HIP call -- the workspace sizes, the kernel forms and the LDS bytes of every launch, from the
 // dimensions, the semiring, B, L, the device's CU count and the FARNN_TRAIN_* switches.  Every size the step refuses is refused
 // here, the launches above 160 KiB of LDS included: a refused step has enqueued nothing and has not touched the caller's outputs.
-static int train_plan(const farnn_train_ctx *c, int B, int L, bool teacher, TrainPlan &pl) {
+template <typename Ctx>      // (farnn_train_ctx, and the decomposed FST's context: the same chains)
+static int train_plan(const Ctx *c, int B, int L, bool teacher, TrainPlan &pl) {
     const size_t S = c->d.S, R = c->d.R, K = c->d.K, V = c->d.V, SR = S > R ? S : R;
     const int farnn = c->d.farnn;
     const bool crf = c->d.use_crf != 0;
@@ -511,6 +514,293 @@ extern "C" int farnn_decomp_ifst_teacher_max_train_step(farnn_train_ctx *c, cons
     if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_max_train_step: null teacher argument%s%s");
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
                                      [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; t.tch_max = true; });
+}
+
+// ---- training step of the decomposed FST (FARNN_S_D_W; decomp0_train.hip.h) ------------------------------
+struct farnn_decomp_fst_train_ctx : TrainCtxBase {
+    Tunables tun;
+    farnn_decomp_fst_train_dims d;
+    int n_cu = 256;
+    int semiring = FARNN_SEMIRING_SUM;  // (train_plan reads it: this step has the sum semiring only)
+    DevBuf<float> fixed;          // create's block: what depends on the dimensions only (Decomp0Step::carve_fixed)
+    DevBuf<float> ws;             // per-batch workspace (zeroed every step)
+    DevBuf<int> iws;              // the bucketing of the positions by word
+    DevBuf<float> part;           // partial products of the parameter-gradient reductions
+    DevBuf<float> ones;           // 1.0f each: the chains' output mask and the bias gradients' column of ones
+    size_t ones_filled = 0;       // how many of them a step has written (the buffer grows with the batch)
+};
+// what create's block holds
+struct D0Fixed {
+    float *S1T, *S2T, *Wm, *WT, *S1wT, *S2wT, *csum, *cwsum, *dOsum, *Rtab, *dRt, *dVs, *dS1s, *dS2s, *X1, *X2;
+    float *Wss1T, *Wss2T, *GV1, *GV2, *dGV1, *dGV2, *dRg1, *dRg2;      // farnn > 0
+};
+static size_t carve_d0_fixed(float *base, D0Fixed &f, const farnn_decomp_fst_train_dims &d) {
+    Carver<float> a(base);
+    const size_t S = d.S, R = d.R, Q = d.Q, V = d.V;
+    f.S1T = a.take(S * R); f.S2T = a.take(S * R); f.Wm = a.take(S * S); f.WT = a.take(S * S);
+    f.S1wT = a.take(S * Q); f.S2wT = a.take(S * Q); f.csum = a.take(R); f.cwsum = a.take(Q); f.dOsum = a.take(S);
+    f.Rtab = a.take(V * R); f.dRt = a.take(V * R); f.dVs = a.take(V * R); f.dS1s = a.take(S * R); f.dS2s = a.take(S * R);
+    f.X1 = a.take(S * Q); f.X2 = a.take(S * Q);
+    if (d.farnn) {
+        f.Wss1T = a.take(S * S); f.Wss2T = a.take(S * S);
+        f.GV1 = a.take(V * S); f.GV2 = a.take(V * S); f.dGV1 = a.take(V * S); f.dGV2 = a.take(V * S);
+        f.dRg1 = a.take(V * R); f.dRg2 = a.take(V * R);
+    }
+    return a.off;
+}
+
+extern "C" int farnn_decomp_fst_train_create(const farnn_decomp_fst_train_dims *d, int device, farnn_decomp_fst_train_ctx **out) {
+    if (!d || !out) return fail(FARNN_EINVAL, "decomp_fst_train_create: null argument%s%s");
+    *out = nullptr;
+    if (d->V <= 0 || d->S <= 0 || d->R <= 0 || d->Q <= 0 || d->K <= 0) return fail(FARNN_EINVAL, "decomp_fst_train_create: bad dimensions%s%s");
+    if (d->nl < FARNN_NL_NONE || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "decomp_fst_train_create: bad nonlinearity%s%s");
+    if (d->use_crf && (d->K < 4 || train_crf_lds_bytes(d->K, 4, true) > 160 * 1024))
+        return fail(FARNN_ERANGE, "decomp_fst_train_create: CRF needs 4..190 score columns%s%s");
+    if (d->farnn < 0 || d->farnn > 2) return fail(FARNN_EINVAL, "decomp_fst_train_create: farnn must be 0, 1 or 2%s%s");
+    int rc;
+    if ((rc = train_ctx_create("decomp_fst_train", d, device, out))) return rc;
+    farnn_decomp_fst_train_ctx *c = *out;
+    c->n_cu = device_cus(device);
+    D0Fixed f;
+    if ((rc = c->fixed.ensure(carve_d0_fixed(nullptr, f, *d), "decomp_fst_train_create: out of device memory%s%s"))) {
+        train_ctx_destroy(c);
+        *out = nullptr;
+        return rc;
+    }
+    return FARNN_OK;
+}
+extern "C" void farnn_decomp_fst_train_destroy(farnn_decomp_fst_train_ctx *c) { train_ctx_destroy(c); }
+extern "C" int farnn_decomp_fst_train_set_profiling(farnn_decomp_fst_train_ctx *c, int32_t enable) { return train_ctx_set_profiling("decomp_fst_train", c, enable); }
+extern "C" int farnn_decomp_fst_train_time(farnn_decomp_fst_train_ctx *c, double *total_ms, int64_t *steps) { return train_ctx_time("decomp_fst_train", c, total_ms, steps); }
+
+// C = A B, k ascending, every element one owner (decomp1_gemm_kernel): A element (m, k) at A[m am + k ak], B (k, n) at B[k bk + n bn]
+static void d0_gemm(hipStream_t s, const float *A, size_t am, size_t ak, const float *Bm, size_t bk, size_t bn, float *Cm, int M, int N, int K) {
+    const D1Gemm g = {A, Bm, nullptr, nullptr, Cm, M, N, K, am, ak, bk, bn, (size_t)N};
+    decomp1_gemm_kernel<<<dim3((unsigned)((M + 63) / 64), (unsigned)((N + 63) / 64)), 256, 0, s>>>(g);
+}
+
+// One step.  The chains and their back-propagation are the decomposed i-FST's (TrainPlan, with_chain_form) on the word table
+// Rtab, the matrix W and a mask of ones; the stages are the member functions, in the order they run.
+struct Decomp0Step : TrainPlan {
+    static constexpr const char *name = "decomp_fst_train", *label_range = "K";
+    farnn_decomp_fst_train_ctx *c; const farnn_decomp_fst_train_weights *w; const farnn_decomp_fst_train_outputs *o; hipStream_t s;
+    TrainParams p; D0Params q; D0Fixed f; PrepJobs prep; AtbJobs jobs; Buckets bk; BucketedCrf crfst;
+    D0Lds lds0; unsigned grid0; size_t Q, need0, ineed;
+    float *DVS, *U, *UW, *DP, *DQ, *DPW, *DQW, *loss_part;
+
+    int validate() {
+        if (!w->Vgen || !w->Ce || !w->S1 || !w->S2 || !w->Cw || !w->S1w || !w->S2w || !w->WW || !w->h0 || !w->hT)
+            return fail(FARNN_EINVAL, "decomp_fst_train_step: null weight%s%s");
+        if (!o->loss || !o->dVgen || !o->dCe || !o->dS1 || !o->dS2 || !o->dCw || !o->dS1w || !o->dS2w || !o->dWW || !o->dh0 || !o->dhT || !o->tags)
+            return fail(FARNN_EINVAL, "decomp_fst_train_step: null output%s%s");
+        if (c->d.use_crf && (!w->crf_trans || !o->dtrans)) return fail(FARNN_EINVAL, "decomp_fst_train_step: CRF transitions / their gradient missing%s%s");
+        if (c->d.farnn >= 1 && (!w->Wss1 || !w->Wrs1 || !w->bs1 || !o->dWss1 || !o->dWrs1 || !o->dbs1))
+            return fail(FARNN_EINVAL, "decomp_fst_train_step: update-gate weights / gradients missing%s%s");
+        if (c->d.farnn == 2 && (!w->Wss2 || !w->Wrs2 || !w->bs2 || !o->dWss2 || !o->dWrs2 || !o->dbs2))
+            return fail(FARNN_EINVAL, "decomp_fst_train_step: reset-gate weights / gradients missing%s%s");
+        return FARNN_OK;
+    }
+    // the step's own arrays, behind everything the chains lay out (carve_train_ws)
+    size_t carve_ws(float *base) {
+        const size_t off0 = carve_train_ws(base, p, *this);
+        Carver<float> a(base ? base + off0 : nullptr);
+        p.DVf = a.take(N1 * R); p.DVb = a.take(N1 * R); p.HP = a.take((size_t)B * 2 * S);
+        U = a.take(N0 * R); UW = a.take(N0 * Q); DVS = a.take(N0 * R);
+        DP = a.take(N1 * R); DQ = a.take(N1 * R); DPW = a.take(N1 * Q); DQW = a.take(N1 * Q);
+        loss_part = a.take((size_t)grid0 * D0_WAVES);
+        if (crf) crfst.carve(a, (size_t)B, (size_t)L, K, false);
+        return off0 + a.off;
+    }
+    // every size the step refuses, before anything is enqueued
+    int plan(int B_, int L_) {
+        Q = (size_t)c->d.Q;
+        if (Q > (size_t)TR_VPT * TR_THREADS / TR_NSEQ) return fail(FARNN_ERANGE, "decomp_fst_train_step: wildcard rank above 512%s%s");
+        if ((unsigned long long)B_ * (L_ + 1) * Q >= (1ull << 30))
+            return fail(FARNN_ERANGE, "decomp_fst_train_step: B (L+1) Q must stay below 2^30 elements%s%s");
+        if (int rc = train_plan(c, B_, L_, false, *this)) return rc;
+        lds0 = decomp0_loss_lds(S, R, Q, K);
+        if (int rc = lds_fits(lds0.bytes())) return rc;
+        grid0 = (unsigned)std::min<size_t>(c->n_cu, (N0 + D0_TP - 1) / D0_TP);
+        need0 = carve_ws(nullptr);
+        ineed = carve_bucket_ints(nullptr, bk, V, N0);
+        return FARNN_OK;
+    }
+    int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
+    int prepare(); int forward(); int loss(); int backward(); int gradients();
+    int stages() {
+        int rc;
+        if ((rc = prepare()) || (rc = forward()) || (rc = loss())) return rc;
+        return (rc = backward()) ? rc : gradients();
+    }
+    template <int PHASE>
+    int launch_loss() {
+        return lds0.clds() ? launch(decomp0_loss_kernel<true, PHASE>, grid0, D0_THREADS, lds0.bytes(), s, q)
+                           : launch(decomp0_loss_kernel<false, PHASE>, grid0, D0_THREADS, lds0.bytes(), s, q);
+    }
+};
+
+// Stage 3: grow the buffers, lay the workspaces out, fill the kernels' parameters and the job lists.  Nothing is enqueued yet.
+int Decomp0Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens) {
+    int rc;
+    if ((rc = c->ws.ensure(need0, "decomp_fst_train_step: out of device memory for the workspace%s%s")) ||
+        (rc = c->iws.ensure(ineed, "decomp_fst_train_step: out of device memory for the index workspace%s%s"))) return rc;
+    const size_t nones = std::max(N1, S);
+    if (c->ones.n < nones) {                                   // (filled on the step's stream, in prepare())
+        if ((rc = c->ones.ensure(nones, "decomp_fst_train_step: out of device memory for the column of ones%s%s"))) return rc;
+        c->ones_filled = 0;
+    }
+    [[maybe_unused]] const size_t carved = carve_ws(c->ws.p), icarved = carve_bucket_ints(c->iws.p, bk, V, N0);
+    assert(carved == need0 && icarved == ineed);
+    carve_d0_fixed(c->fixed.p, f, c->d);
+    // the chains: the i-FST's kernels on (Rtab, S1, S2, W, gates), no output mask
+    p.Vgen = f.Rtab; p.S1 = w->S1; p.S2 = w->S2; p.W = f.Wm; p.C = nullptr; p.h0 = w->h0; p.hT = w->hT; p.P = w->P;
+    p.S1T = f.S1T; p.S2T = f.S2T; p.WT = f.WT; p.Osum = c->ones.p;
+    p.x = x; p.len = lengths; p.labels = labels; p.err = c->err.dev;
+    p.farnn = farnn; p.sig_k = c->d.sigmoid_exponent;
+    if (farnn) {
+        p.Wss1 = w->Wss1; p.Wrs1 = w->Wrs1; p.bs1 = w->bs1; p.Wss2 = w->Wss2; p.Wrs2 = w->Wrs2; p.bs2 = w->bs2;
+        p.Wss1T = f.Wss1T; p.Wss2T = f.Wss2T;
+        p.GV1 = f.GV1; p.GV2 = f.GV2; p.dGV1 = f.dGV1; p.dGV2 = f.dGV2;
+    }
+    p.nss_f = nss_f; p.nss_b = nss_b;
+    p.dOsum = f.dOsum; p.loss = o->loss; p.tags = o->tags;
+    p.B = B; p.L = L; p.V = (int)V; p.S = (int)S; p.R = (int)R; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
+    p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
+    // the score head
+    q.Vgen = w->Vgen; q.Ce = w->Ce; q.Cw = w->Cw; q.S1 = w->S1; q.S2 = w->S2; q.S1w = w->S1w; q.S2w = w->S2w; q.P = w->P;
+    q.S1T = f.S1T; q.S2T = f.S2T; q.S1wT = f.S1wT; q.S2wT = f.S2wT;
+    q.A = p.A; q.Bk = p.Bk; q.GA = p.GA; q.GB = p.GB; q.x = x; q.len = lengths; q.labels = labels;
+    q.SC = p.SC; q.DS = p.DS; q.U = U; q.UW = UW; q.DVS = DVS; q.DP = DP; q.DQ = DQ; q.DPW = DPW; q.DQW = DQW;
+    q.loss_part = loss_part; q.tags = o->tags; q.err = c->err.dev;
+    q.B = B; q.L = L; q.V = (int)V; q.S = (int)S; q.R = (int)R; q.Q = (int)Q; q.K = (int)K; q.o_idx = c->d.o_idx;
+    q.threshold = c->d.threshold; q.inv_tokens = p.inv_tokens;
+    if (crf) crfst.fill(w->crf_trans, nullptr, p.SC, p.DS, lengths, labels, o->tags, c->err.dev, B, L, K, c->d.o_idx, c->d.threshold);
+    // the preparation jobs: the outputs the products add into and the score's shares to zero, the transposes, the column sums
+    PrepJobs &pj = prep;
+    prep_add(pj, 0, nullptr, o->loss, 1, 1); prep_add(pj, 0, nullptr, o->dS1, S, R); prep_add(pj, 0, nullptr, o->dS2, S, R);
+    prep_add(pj, 0, nullptr, o->dWW, S, S); prep_add(pj, 0, nullptr, o->dCe, K, R); prep_add(pj, 0, nullptr, o->dCw, K, Q);
+    prep_add(pj, 0, nullptr, o->dS1w, S, Q); prep_add(pj, 0, nullptr, o->dS2w, S, Q);
+    prep_add(pj, 0, nullptr, f.dS1s, S, R); prep_add(pj, 0, nullptr, f.dS2s, S, R);
+    prep_add(pj, 1, w->S1, f.S1T, S, R); prep_add(pj, 1, w->S2, f.S2T, S, R);
+    prep_add(pj, 1, w->S1w, f.S1wT, S, Q); prep_add(pj, 1, w->S2w, f.S2wT, S, Q);
+    prep_add(pj, 2, w->Ce, f.csum, K, R); prep_add(pj, 2, w->Cw, f.cwsum, K, Q);
+    if (farnn) {
+        prep_add(pj, 0, nullptr, o->dWss1, S, S); prep_add(pj, 0, nullptr, o->dbs1, 1, S); prep_add(pj, 1, w->Wss1, f.Wss1T, S, S);
+        if (farnn == 2) { prep_add(pj, 0, nullptr, o->dWss2, S, S); prep_add(pj, 0, nullptr, o->dbs2, 1, S); prep_add(pj, 1, w->Wss2, f.Wss2T, S, S); }
+    }
+    if (pj.total < 0) return fail(FARNN_ERANGE, "decomp_fst_train_step: too many preparation jobs%s%s");
+    // the products over the per-token rows.  Every output has at most two addends: the two chains' shares (a + b = b + a in
+    // floating point, whichever atomic lands first); the score's shares of dS1 / dS2 go to a buffer of their own
+    const int iS = (int)S, iR = (int)R, iQ = (int)Q, iK = (int)K;
+    const long long n1 = (long long)N1, n0 = (long long)N0;
+    jobs.chunk = 128;
+    atb_add(jobs, p.Zf, p.Tf, o->dS2, n1, iS, iR);
+    if (!farnn) {
+        atb_add(jobs, p.A, p.D1f + R, o->dS1, n1 - 1, iS, iR);
+        atb_add(jobs, p.A, p.Zf + S, o->dWW, n1 - 1, iS, iS);
+    } else {
+        atb_add(jobs, p.HBARf, p.D1f, o->dS1, n1, iS, iR);
+        atb_add(jobs, p.HBARf, p.Zf, o->dWW, n1, iS, iS);
+    }
+    atb_add(jobs, p.Zb, p.Tb, o->dS1, n1, iS, iR);
+    atb_add(jobs, p.BBAR, p.D1b, o->dS2, n1, iS, iR);
+    atb_add(jobs, p.Zb, p.BBAR, o->dWW, n1, iS, iS);
+    atb_add(jobs, p.DS, U, o->dCe, n0, iK, iR);                      // dC_embed += ds x u
+    atb_add(jobs, p.DS, UW, o->dCw, n0, iK, iQ);                     // dC_wildcard += ds x uw
+    atb_add(jobs, p.A, DP, f.dS1s, n1, iS, iR);                      // alpha x dp
+    atb_add(jobs, p.Bk, DQ, f.dS2s, n1, iS, iR);                     // beta x dq
+    atb_add(jobs, p.A, DPW, o->dS1w, n1, iS, iQ);                    // alpha x dpw
+    atb_add(jobs, p.Bk, DQW, o->dS2w, n1, iS, iQ);                   // beta x dqw
+    if (farnn) {
+        atb_add(jobs, p.A, p.DAZf + S, o->dWss1, n1 - 1, iS, iS);
+        atb_add(jobs, p.Bk, p.DAZb + S, o->dWss1, n1 - 1, iS, iS);
+        atb_add(jobs, c->ones.p, p.DAZf, o->dbs1, n1, 1, iS);
+        atb_add(jobs, c->ones.p, p.DAZb, o->dbs1, n1, 1, iS);
+        if (farnn == 2) {
+            atb_add(jobs, p.A, p.DARf + S, o->dWss2, n1 - 1, iS, iS);
+            atb_add(jobs, p.Bk, p.DARb + S, o->dWss2, n1 - 1, iS, iS);
+            atb_add(jobs, c->ones.p, p.DARf, o->dbs2, n1, 1, iS);
+            atb_add(jobs, c->ones.p, p.DARb, o->dbs2, n1, 1, iS);
+        }
+    }
+    if (jobs.total_wgs < 0) return fail(FARNN_ERANGE, "decomp_fst_train_step: too many gradient products for one launch%s%s");
+    if ((rc = c->part.ensure(atb_partial_floats(jobs), "decomp_fst_train_step: out of device memory for the partial products%s%s"))) return rc;
+    jobs.partial = c->part.p;
+    return FARNN_OK;
+}
+// Stage 4 (prep): zero the workspace and the outputs, transpose, the column sums; Rtab, W, W^T; the gates' input halves; the buckets
+int Decomp0Step::prepare() {
+    int rc;
+    FARNN_HIP_TRY(hipMemsetAsync(c->ws.p, 0, need0 * sizeof(float), s));
+    if ((rc = clear_bucket_counts(bk, V, N0, s))) return rc;
+    if (c->ones_filled < c->ones.n) {
+        decomp0_fill_kernel<<<(unsigned)((c->ones.n + 255) / 256), 256, 0, s>>>(c->ones.p, c->ones.n, 1.0f);
+        c->ones_filled = c->ones.n;
+    }
+    train_prep_kernel<<<(prep.total + 255) / 256, 256, 0, s>>>(prep);
+    const size_t ne = std::max(V * R, S * S);
+    decomp0_prep_kernel<<<(unsigned)((ne + 255) / 256), 256, 0, s>>>(w->Vgen, f.csum, f.Rtab, V * R, (int)R, w->S1w, w->S2w, f.cwsum, w->WW,
+                                                                    f.Wm, f.WT, (int)S, (int)Q);
+    if (farnn) {                                               // GV = Rtab Wrs (:259-262: the gates read _R, not V_vec)
+        d0_gemm(s, f.Rtab, R, 1, w->Wrs1, S, 1, f.GV1, (int)V, (int)S, (int)R);
+        if (farnn == 2) d0_gemm(s, f.Rtab, R, 1, w->Wrs2, S, 1, f.GV2, (int)V, (int)S, (int)R);
+    }
+    return launch_bucketing(p.x, p.len, B, L, (int)V, bk, c->err.dev, s);
+}
+// Stage 5: both chains with the state stash (the i-FST's kernels)
+int Decomp0Step::forward() {
+    return with_chain_form(*this, ldsw_f, ns_f, [&](auto LDSW, auto GATED, auto VPS, auto VPR, auto NS) {
+        return launch(train_forward_kernel<LDSW(), GATED(), VPS(), VPR(), NS()>, dim3((B + NS() - 1) / NS(), 2), TR_THREADS, lds_f, s, p);
+    });
+}
+// Stage 6: the score head, the loss (cross-entropy, or the CRF between the emissions and the adjoints), the decode
+int Decomp0Step::loss() {
+    int rc;
+    if (!crf) {
+        if ((rc = launch_loss<0>())) return rc;
+        onehot_loss_sum_kernel<<<1, 64, 0, s>>>(loss_part, (int)grid0 * D0_WAVES, o->loss);
+        return FARNN_OK;
+    }
+    if ((rc = launch_loss<1>()) || (rc = crfst.run(p.SC, grid0, o->dtrans, o->loss, s))) return rc;
+    return launch_loss<2>();
+}
+// Stage 7: back-propagation through time, the i-FST's kernel in its DET form
+int Decomp0Step::backward() {
+    return with_chain_form(*this, ldsw_b, ns_b, [&](auto LDSW, auto GATED, auto VPS, auto VPR, auto NS) {
+        return launch(train_backward_kernel<LDSW(), GATED(), VPS(), VPR(), NS(), true>, dim3((B + NS() - 1) / NS(), 2), TR_THREADS, lds_b, s, p);
+    });
+}
+// Stage 8: the reductions, all in a fixed order
+int Decomp0Step::gradients() {
+    const int iV = (int)V, iS = (int)S, iR = (int)R, iQ = (int)Q;
+    const D0WordSum ws = {bk.list, bk.wstart, bk.wcount, p.len, DVS, p.DVf, p.DVb, p.DAZf, p.DAZb, p.DARf, p.DARb,
+                          f.dVs, f.dRt, f.dGV1, f.dGV2, L, iS, iR, farnn};
+    decomp0_word_sum_kernel<<<(unsigned)V, 256, 0, s>>>(ws);
+    if (farnn) {                                               // dRtab += dGV Wrs^T, dWrs = Rtab^T dGV
+        d0_gemm(s, f.dGV1, S, 1, w->Wrs1, 1, S, f.dRg1, iV, iR, iS);
+        d0_gemm(s, f.Rtab, 1, R, f.dGV1, S, 1, o->dWrs1, iR, iS, iV);
+        if (farnn == 2) {
+            d0_gemm(s, f.dGV2, S, 1, w->Wrs2, 1, S, f.dRg2, iV, iR, iS);
+            d0_gemm(s, f.Rtab, 1, R, f.dGV2, S, 1, o->dWrs2, iR, iS, iV);
+        }
+    }
+    atb_launch(jobs, s);
+    d0_gemm(s, o->dWW, S, 1, w->S2w, Q, 1, f.X1, iS, iQ, iS);      // X1 = dW S2w
+    d0_gemm(s, o->dWW, 1, S, w->S1w, Q, 1, f.X2, iS, iQ, iS);      // X2 = dW^T S1w
+    const D0Fold fo = {f.dVs, farnn ? f.dRg1 : nullptr, farnn == 2 ? f.dRg2 : nullptr, f.csum, f.cwsum, f.dS1s, f.dS2s, f.X1, f.X2,
+                       f.dRt, o->dVgen, o->dS1, o->dS2, o->dS1w, o->dS2w, V * R, S * R, S * Q, iR, iQ};
+    const size_t ne = std::max(V * R, std::max(S * R, S * Q));
+    decomp0_fold_kernel<<<(unsigned)((ne + 255) / 256), 256, 0, s>>>(fo);
+    const D0SumAdj sa = {f.dRt, w->Vgen, w->S1w, f.X1, p.HP, o->dCe, o->dCw, o->dh0, o->dhT, iV, iR, iQ, iS, (int)K, B};
+    decomp0_sum_adj_kernel<<<(unsigned)((R + Q + 2 * S + 255) / 256), 256, 0, s>>>(sa);
+    return FARNN_OK;
+}
+
+extern "C" int farnn_decomp_fst_train_step(farnn_decomp_fst_train_ctx *c, const farnn_decomp_fst_train_weights *w, const int64_t *x,
+                                           const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
+                                           int64_t valid_tokens, const farnn_decomp_fst_train_outputs *o, void *stream) {
+    TunScope tun_scope(c ? &c->tun : nullptr);
+    return run_train_step<Decomp0Step>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
 // ---- training step of the onehot i-FST (FARNN_S_O_I_S; onehot_train.hip.h) -------------------------------

@@ -61,6 +61,9 @@ struct TrainParams {
     const float *re;          // [B][L][K] the teacher's scores, zero columns already appended
     int t_mode;               // FARNN_TEACHER_KD / FARNN_TEACHER_PR
     float t_c1, t_pi, t_inv_n;   // temperature (KD) or rule strength (PR); weight of the original loss; 1 / (B L K)
+    // train_backward_kernel's DET form (decomp0_train.hip.h; NULL in every other step): what the plain form adds with atomics is stored
+    float *DVf, *DVb;         // [B][L+1][R] d v_t of every step, beside D1f / D1b
+    float *HP;                // [B][2][S] the sequence's share of dh0, dhT
 };
 
 __device__ __forceinline__ float nl_grad_from_output(float y, int nl) {
@@ -826,7 +829,10 @@ __global__ void crf_reduce_kernel(const float *__restrict__ part, float *dtrans,
 // grid (ceil(B/2), 2), TR_NSEQ sequences per workgroup.  LDSW: the four matrices of this direction
 // (3 S R + S S floats) live in LDS.  The forward chain's pre-activation is read from the stash (PRE), not recomputed.
 // LDS: [Ma | Mb | Mc | Md] z fp [2][mv_pad(S)], d1 [2][mv_pad(R)], pa pb [8][2][max(S,R)], pc [8][2][S], toks [2][L]
-template <bool LDSW, bool GATED, int VPS, int VPR, int NS>
+// DET (the decomposed FST's step): no float atomics -- d v_t goes to its row of DVf / DVb, the gates' input adjoints stay in
+// their rows DAZ / DAR, the sequence's dh0 / dhT go to HP, and dOsum (a mask of ones there) is dropped; the caller sums them in a
+// fixed order.  The plain form is what it was.
+template <bool LDSW, bool GATED, int VPS, int VPR, int NS, bool DET = false>
 __global__ void __launch_bounds__(TR_THREADS)
 train_backward_kernel(const TrainParams p) {
     constexpr int VPT = VPS > VPR ? VPS : VPR;       // slots per thread: VPS cover 2 S states, VPR cover 2 R ranks
@@ -947,7 +953,7 @@ train_backward_kernel(const TrainParams p) {
                         const float daz = gt * (cc[k] - hp) * p.sig_k * zc[k] * (1.0f - zc[k]);
                         dazv[li] = daz;
                         DAZ[row] = daz;
-                        atomicAdd(p.dGV1 + (unsigned)(toks[sq[k] * p.L + t - 1] * S + ss[k]), daz);   // az = h Wss1 + GV1[token] + bs1
+                        if constexpr (!DET) atomicAdd(p.dGV1 + (unsigned)(toks[sq[k] * p.L + t - 1] * S + ss[k]), daz);   // az = h Wss1 + GV1[token] + bs1
                         if (farnn == 2) hp = (1.0f - rc[k]) * hin[k] + rc[k] * hp;          // hbar (:150-151)
                     } else {
                         yy = gt * nl_grad_from_output(hcur[k], p.nl);
@@ -987,7 +993,8 @@ train_backward_kernel(const TrainParams p) {
                     dd = uv * vv;
                     D1o[row] = dd;
                     To[row] = vv * rvv;
-                    atomicAdd(p.dVgen + (unsigned)(toks[rq[k] * p.L + t - 1] * R + rr_[k]), uv * rvv);   // d v_t = u * rr
+                    if constexpr (DET) (dir == 0 ? p.DVf : p.DVb)[row] = uv * rvv;
+                    else atomicAdd(p.dVgen + (unsigned)(toks[rq[k] * p.L + t - 1] * R + rr_[k]), uv * rvv);   // d v_t = u * rr
                 }
                 d1[rq[k] * RP + rr_[k]] = dd;
             }
@@ -1010,7 +1017,7 @@ train_backward_kernel(const TrainParams p) {
                         dhin[k] = fmaf(dhb, 1.0f - rc[k], dhin[k]);
                         dhk[k] = fmaf(dhb, rc[k], dhk[k]);
                         DAR[srow[k] + (unsigned)(t * S)] = dar;
-                        atomicAdd(p.dGV2 + (unsigned)(toks[sq[k] * p.L + t - 1] * S + ss[k]), dar);
+                        if constexpr (!DET) atomicAdd(p.dGV2 + (unsigned)(toks[sq[k] * p.L + t - 1] * S + ss[k]), dar);
                     } else {
                         dhk[k] += dhb;
                     }
@@ -1050,8 +1057,11 @@ train_backward_kernel(const TrainParams p) {
     for (int k = 0; k < VPT; k++) {
         if (sv[k]) {
             const float g0 = gacc[k] + G_base[srow[k]] + dhin[k];
-            if (g0 != 0.0f) atomicAdd((dir == 0 ? p.dh0 : p.dhT) + ss[k], g0);
-            if (dOacc[k] != 0.0f) atomicAdd(p.dOsum + ss[k], dOacc[k]);
+            if constexpr (DET) p.HP[((size_t)(b0 + sq[k]) * 2 + dir) * S + ss[k]] = g0;
+            else {
+                if (g0 != 0.0f) atomicAdd((dir == 0 ? p.dh0 : p.dhT) + ss[k], g0);
+                if (dOacc[k] != 0.0f) atomicAdd(p.dOsum + ss[k], dOacc[k]);
+            }
         }
     }
 }

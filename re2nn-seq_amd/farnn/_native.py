@@ -3,7 +3,7 @@
 PyTorch-ROCm tensors are used only as device-memory containers; every number is produced by
 libfarnn_hip.so.  The method contract mirrors what the reference's callers consume
 (SURVEY.md 8b): ``val.val_onehot`` calls ``forward_local(x, label, lengths, train=False)`` and
-``RE.get_RE_prediction`` calls ``forward_RE(x, label, lengths, train=False)``.  The training surface of the five trainable
+``RE.get_RE_prediction`` calls ``forward_RE(x, label, lengths, train=False)``.  The training surface of all six trainable
 mirrors is farnn/_trainable.py; the reader of their opt-in switches (opted_in) and the semiring's name (_semiring) live here.
 """
 import os
@@ -31,6 +31,7 @@ def default_device():
 #   DECOMP_IND1_GATED_TRAIN   that step for the gated model (--farnn 1 | 2, sum semiring), beside DECOMP_IND1_TRAIN f9
 #   DECOMP_IND1_GATED_MAX_TRAIN  the gated model under --train_mode max, beside DECOMP_IND1_TRAIN, DECOMP_IND1_GATED_TRAIN and
 #                             BUCKETED_MAX_TRAIN (and DECOMP_IND1_CRF_TRAIN under --use_crf 1)                f9
+#   DECOMP_FST_TRAIN          the decomposed FST's training step (FARNN_S_D_W; sum semiring)                  f11
 #   BUCKETED_MAX_TRAIN        --train_mode max for the three steps over bucketed per-word blocks (the onehot
 #                             FST, the onehot and the decomposed independent=1 model), beside each model's own f7 - f9
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3

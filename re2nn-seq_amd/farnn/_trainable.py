@@ -1,5 +1,5 @@
-"""The training surface the five trainable mirrors share (FARNN_S_O_I_S, FARNN_S_O, FARNN_S_O_I, FARNN_S_D_W_I_S,
-FARNN_S_D_W_I): device-resident leaf tensors for the optimizer, the library context, the step inside forward_local(train=True)
+"""The training surface all six trainable mirrors share (FARNN_S_O_I_S, FARNN_S_O, FARNN_S_O_I, FARNN_S_D_W_I_S,
+FARNN_S_D_W_I, FARNN_S_D_W): device-resident leaf tensors for the optimizer, the library context, the step inside forward_local(train=True)
 and the copy back into the host attributes the tagging handle is built from.
 
 A class lists ``Trainable`` before its NativeTagger base and keeps what is its own:

@@ -12,7 +12,8 @@ import torch
 
 from .. import _lib
 from .model_decompose_single import FARNN_S_D_W_I_S, crf_default_transitions, _GATE_KEYS
-from ._native import NativeTagger
+from . import train_step
+from ._native import NativeTagger, opted_in
 from .priority import expand_priority
 
 _PARAM_KEYS = ('S1', 'S2', 'V_embed', 'embed_r_generalized', 'C_embed', 'C_wildcard', 'S1_wildcard',
@@ -83,6 +84,58 @@ class FARNN_S_D_W(FARNN_S_D_W_I_S):
                 torch.nn.init.xavier_normal_(getattr(self, name))
             torch.nn.init.normal_(self.h0)
             torch.nn.init.normal_(self.hT)
+
+    # ---- training step (reference :373-456 with train=True; opt-in: RE2NN_DECOMP_FST_TRAIN=1) ----
+    # which tensors get a gradient: the reference's requires_grad flags (:52-63, :104-165); the gates and crf.transitions follow
+    # in FARNN_S_D_W_I_S._train_decl, always trainable
+    _TRAIN_FLAGS = {'S1': None, 'S2': None, 'embed_r_generalized': None, 'V_embed': 'train_V_embed', 'C_embed': None,
+                    'C_wildcard': 'train_wildcard', 'S1_wildcard': 'train_wildcard', 'S2_wildcard': 'train_wildcard',
+                    'wildcard_wildcard': 'train_wildcard_wildcard', 'h0': 'train_h0', 'hT': 'train_hT',
+                    'beta_vec': 'train_beta', 'embedding.weight': 'train_word_embed'}
+
+    _check_needs_re_tags = False     # every refusal is known without a batch
+
+    def _check_trainable(self, re_tags=None):
+        """The cases the HIP training step does not cover, refused before any device work."""
+        if not opted_in('DECOMP_FST_TRAIN'):           # before self.args is touched: the refusal needs the type only
+            from ..train_onehot import no_training_step
+            raise no_training_step(self)
+        a = self.args
+        why = None
+        if a.farnn not in (0, 1, 2):
+            why = '--farnn {}'.format(a.farnn)
+        elif a.train_mode != 'sum':
+            why = 'the max semiring (--train_mode {})'.format(a.train_mode)
+        elif a.local_loss_func != 'CE1':
+            why = 'a loss other than CE1 (--local_loss_func {})'.format(a.local_loss_func)
+        elif re_tags is not None or getattr(a, 'marryup_type', 'none') not in ('none', None):
+            why = 'the KD / PR teacher terms (--marryup_type {}; the reference class never reads it)'.format(
+                getattr(a, 'marryup_type', 'none'))
+        else:
+            from ..dist import world
+            if world()[1] > 1:
+                why = 'multi-GPU data-parallel training'
+        if why is not None:
+            raise NotImplementedError('training the decomposed FST covers farnn 0 / 1 / 2, the sum semiring and the CE1 loss '
+                                      '(with or without the CRF) on one GPU; {} is not built (DESIGN.md, row f11)'.format(why))
+
+    def _check_step(self, re_tags):
+        self._check_trainable(re_tags)
+
+    def _train_context(self):
+        tp, a = self._tp, self.args
+        S, R = tp['S1'].shape
+        K, Q = tp['C_wildcard'].shape
+        return _lib.DecompFstTrainContext(tp['V_embed'].shape[0], S, R, Q, K, nl=a.update_nonlinear, threshold=a.threshold,
+                                          o_idx=self.o_idx, device=self.device_index, use_crf=self.use_crf, farnn=int(a.farnn),
+                                          sigmoid_exponent=float(a.sigmoid_exponent))
+
+    def _train_call(self, x, lengths, lab, ntok, re_tags):
+        tp = self._tp                  # the Vgen fold stays in torch, as for the decomposed i-FST
+        return train_step.decomp_fst_train_step(self._tc, self._train_vgen(), tp['C_embed'], tp['S1'], tp['S2'], tp['C_wildcard'],
+                                                tp['S1_wildcard'], tp['S2_wildcard'], tp['wildcard_wildcard'], tp['h0'], tp['hT'],
+                                                self._tpP, x, lengths, lab, crf_trans=tp.get('crf.transitions'),
+                                                gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]), valid_tokens=ntok)
 
     # ---- device handle ------------------------------------------------------------------------
     def _build_handle(self):

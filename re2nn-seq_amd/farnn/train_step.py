@@ -123,6 +123,23 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
     return _step(tc, valid_tokens, x, lengths, labels, spec, call)
 
 
+_D0_NAMES = ('Vgen', 'Ce', 'S1', 'S2', 'Cw', 'S1w', 'S2w', 'WW', 'h0', 'hT')
+
+
+def decomp_fst_train_step(tc, Vgen, Ce, S1, S2, Cw, S1w, S2w, WW, h0, hT, P, x, lengths, labels, crf_trans=None, gates=(),
+                          valid_tokens=None):
+    """The decomposed FST (FARNN_S_D_W, model_decompose.py:243-456), sum semiring: returns (loss scalar tensor
+    with grad, tags int32 [B,L] with -1 at pads).  One library call (farnn_decomp_fst_train_step) computes the loss (CE1, or the
+    CRF's negative log-likelihood when crf_trans is given), the tags and the gradients of Vgen [V,R] (which flows on through
+    torch's autograd as for f3), C_embed, S1, S2, C_wildcard, S1_wildcard, S2_wildcard, wildcard_wildcard, h0, hT, the gates
+    (as decomp_ifst_train_step's) and crf_trans.  P is read only."""
+    if len(gates) not in (0, 3, 6):
+        raise ValueError('gates: none, Wss1 Wrs1 bs1 (farnn 1) or those and Wss2 Wrs2 bs2 (farnn 2), not {} tensors'.format(len(gates)))
+    spec = [(n, t, ALWAYS) for n, t in zip(_D0_NAMES, (Vgen, Ce, S1, S2, Cw, S1w, S2w, WW, h0, hT))]
+    spec += [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)] + [(n, g, ALWAYS) for n, g in zip(GATE_NAMES, gates)]
+    return _step(tc, valid_tokens, x, lengths, labels, spec)
+
+
 def _onehot_t_step(tc, T, W, O, h0, hT, P, x, lengths, labels, valid_tokens):
     """The onehot i-FST and the onehot independent=1 step: the same weights T, W, O, h0, hT and the one gradient dT; which
     library step runs is the context's (OnehotTrainContext or Ind1TrainContext)."""
