@@ -529,6 +529,7 @@ struct Decomp0ScoreParams {
 // entry read from L2 feeds four FMAs (r02a: one workgroup per token re-read all four S x R factors -- 83 KB at the
 // config-2 size -- for every token: 730 MB of L2 traffic per launch, 88 us).
 constexpr int D0_TOK = 8;
+constexpr size_t D0_STATIC_LDS = D0_TOK * sizeof(int);      // tokid[]: static LDS beside the dynamic tile, inside the same 160 KiB
 
 __global__ void __launch_bounds__(256)
 decomp0_score_kernel(const Decomp0ScoreParams p) {

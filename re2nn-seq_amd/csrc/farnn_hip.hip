@@ -329,6 +329,9 @@ static int plan_tag(const farnn_model *m, int B, int L, int full, bool flat, boo
             plan_decomp_recurrence(m, p, !m->use_crf, offs_ok);
             return p.fused ? FARNN_OK : plan_score_decode(m, p, flat, scores, offs);
         case KIND_DECOMP0:
+            // the score kernel's tile and its static tokid[] share the workgroup's 160 KiB: refused here, before anything is launched
+            // (at exactly 160 KiB of tile the launcher's hipFuncSetAttribute failed behind the recurrence, with a HIP error)
+            if (int rc = lds_fits(decomp0_score_lds_bytes(m->SP, m->Rp, m->RWp, m->Kc) + D0_STATIC_LDS)) return rc;
             plan_decomp_recurrence(m, p, false, offs_ok);
             p.score = SCORE_DECOMP0;
             return m->use_crf ? plan_viterbi(m, p, false) : FARNN_OK;
