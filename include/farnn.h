@@ -455,8 +455,8 @@ int  farnn_train_set_semiring(farnn_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the decomposed FST (FARNN_S_D_W, --method decompose --independent 0) ----------
  * Replaces FARNN_S_D_W.forward_local(train=True) + loss.backward() (model_decompose.py:243-456) for farnn = 0/1/2, every
- * update_nonlinear, the priority layer, and the CE1 loss or (use_crf) the CRF negative log-likelihood, in the SUM semiring.  The max
- * semiring of this model (--train_mode max) is not built: there is no set_semiring entry.  With csum = C_embed.sum(0) and cwsum =
+ * update_nonlinear, the priority layer, and the CE1 loss or (use_crf) the CRF negative log-likelihood, in the sum semiring or
+ * (farnn_decomp_fst_train_set_semiring) the max semiring.  With csum = C_embed.sum(0) and cwsum =
  * C_wildcard.sum(0) the two chains are the decomposed i-FST's recurrence on the word table Vgen * csum and the matrix
  * S1_wildcard diag(cwsum) S2_wildcard^T + wildcard_wildcard (:253, :327-332), and
  *   score[c] = sum_r Vgen[w,r] C_embed[c,r] (alpha S1)[r] (beta S2)[r] + sum_q C_wildcard[c,q] (alpha S1w)[q] (beta S2w)[q]  (:310-325)
@@ -516,6 +516,13 @@ int  farnn_decomp_fst_train_step(farnn_decomp_fst_train_ctx *ctx, const farnn_de
 /* as farnn_train_set_profiling / farnn_train_time */
 int  farnn_decomp_fst_train_set_profiling(farnn_decomp_fst_train_ctx *ctx, int32_t enable);
 int  farnn_decomp_fst_train_time(farnn_decomp_fst_train_ctx *ctx, double *total_ms, int64_t *steps);
+/* The semiring of the two recurrences (the reference's --train_mode, model_decompose.py:269-276): FARNN_SEMIRING_SUM (the
+ * default) or FARNN_SEMIRING_MAX, where a step is n[s] = max_j hbar[j] Tr_w[j,s] (the backward chain: Tr_w[s,j]) with
+ * Tr_w = S1 diag(Vgen[w] * csum) S2^T + W (utils._maxmul, utils.py:192-195: the first maximal j takes the whole adjoint).
+ * The score head, the priority layer, the loss and the decode stay sum-times; two max steps on the same inputs are
+ * bit-identical too.  Returns FARNN_EINVAL for any other value and FARNN_ERANGE for FARNN_SEMIRING_MAX above 192 states.  The
+ * max step's workspace (three S x S blocks per distinct word of the batch) is allocated by its first step. */
+int  farnn_decomp_fst_train_set_semiring(farnn_decomp_fst_train_ctx *ctx, int32_t semiring);
 
 /* ---- training step of the onehot i-FST (FARNN_S_O_I_S, --method onehot --independent 2) -----------------
  * Replaces FARNN_S_O_I_S.forward_local(train=True) + loss.backward() (model_onehot.py:131-146,351-428,

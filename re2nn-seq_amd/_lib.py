@@ -274,6 +274,7 @@ SIGNATURES = {
     'farnn_decomp_ind1_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_decomp_ind1_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_fst_train_create': (C.c_int, [C.POINTER(DecompFstTrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_decomp_fst_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_decomp_fst_train_destroy': (None, [C.c_void_p]),
     'farnn_decomp_fst_train_step': (C.c_int, [C.c_void_p, C.POINTER(DecompFstTrainWeights), C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
@@ -745,20 +746,17 @@ class TrainContext(_TrainContextBase):
 
 
 class DecompFstTrainContext(_TrainContextBase):
-    """Owns one farnn_decomp_fst_train_ctx* (training step of the decomposed FST, FARNN_S_D_W; include/farnn.h).  Sum semiring
-    only: the entry has no set_semiring."""
+    """Owns one farnn_decomp_fst_train_ctx* (training step of the decomposed FST, FARNN_S_D_W; include/farnn.h)."""
     _create, _destroy, _step = 'farnn_decomp_fst_train_create', 'farnn_decomp_fst_train_destroy', 'farnn_decomp_fst_train_step'
     _set_profiling, _time = 'farnn_decomp_fst_train_set_profiling', 'farnn_decomp_fst_train_time'
+    _set_semiring = 'farnn_decomp_fst_train_set_semiring'
     _weights, _outputs = DecompFstTrainWeights, DecompFstTrainOutputs
 
-    def __init__(self, V, S, R, Q, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0, sigmoid_exponent=5.0):
+    def __init__(self, V, S, R, Q, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0, sigmoid_exponent=5.0,
+                 semiring='sum'):
         self._open(DecompFstTrainDims(int(V), int(S), int(R), int(Q), int(K), NL[nl], float(threshold), int(o_idx), int(farnn),
-                                      float(sigmoid_exponent), int(bool(use_crf))), device)
+                                      float(sigmoid_exponent), int(bool(use_crf))), device, semiring)
         self.dims = (int(V), int(S), int(R), int(Q), int(K))
-
-    def set_semiring(self, semiring):
-        if semiring != 'sum':
-            raise NotImplementedError('the decomposed FST trains in the sum semiring only (DESIGN.md, row f11)')
 
 
 class OnehotTrainContext(_TrainContextBase):

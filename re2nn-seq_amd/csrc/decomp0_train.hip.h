@@ -1,7 +1,6 @@
 // Training step of the decomposed FST tagger (FARNN_S_D_W, --method decompose --independent 0): the CE1 loss
 // or the CRF negative log-likelihood, and the gradients of Vgen, C_embed, S1, S2, C_wildcard, S1_wildcard, S2_wildcard,
-// wildcard_wildcard, h0, hT, the gates and the CRF's transitions.  Sum semiring only: the max semiring of this model
-// (--train_mode max) is a follow-up and has no entry here.
+// wildcard_wildcard, h0, hT, the gates and the CRF's transitions.
 //
 // Reference: FARNN_S_D_W.forward_local(train=True) (model_decompose.py:373-456) followed by loss.backward().  With v = Vgen[w]:
 //   csum = C_embed.sum(0), cwsum = C_wildcard.sum(0)                                                           (:328, :394)
@@ -11,7 +10,8 @@
 //                alpha_i = the forward state BEFORE token i, beta_i = the backward state behind it              (:310-325, :426-427)
 // The chains with their stash and the back-propagation through time are train.hip.h's kernels, unchanged for the i-FST; this
 // step launches train_backward_kernel's DET form, which stores what the plain form adds with float atomics (the word table's
-// and the gates' per-step adjoints, the sequences' dh0 / dhT).  This header adds
+// and the gates' per-step adjoints, the sequences' dh0 / dhT).  The max semiring's chains and their weight gradients are
+// decomp0_train_max.hip.h's; the rest of that step is this header's, unchanged.  This header adds
 //   decomp0_prep_kernel      Rtab, W and W^T from the column sums
 //   decomp0_loss_kernel      the score head and its adjoint: a tile of 16 positions per workgroup round, the four state-by-rank
 //                            products, the two label-by-rank products and all their transposes on the f32 matrix cores
@@ -316,6 +316,7 @@ decomp0_loss_kernel(const D0Params p) {
 // ---- per word, in bucket order: the rows the loss kernel and the back-propagation left per position ------------------------------
 // dVs[w] = sum DVS[pos]; dRt[w] = sum DVf[row of the forward step that read pos] + DVb[row of the backward step];
 // dGV1[w] / dGV2[w] likewise from DAZ / DAR (farnn >= 1 / 2).  Zero rows for a word that does not occur.  grid (V).
+// MX (the max semiring, decomp0_train_max.hip.h): dRt of the batch's words comes from dM_w and is left alone; the other rows are zeroed.
 struct D0WordSum {
     const int *list, *wstart, *wcount;
     const int64_t *len;
@@ -323,6 +324,7 @@ struct D0WordSum {
     float *dVs, *dRt, *dGV1, *dGV2;
     int L, S, R, farnn;
 };
+template <bool MX = false>
 __global__ void __launch_bounds__(256)
 decomp0_word_sum_kernel(const D0WordSum p) {
     const int w = blockIdx.x, n = p.wcount[w], first = p.wstart[w], L = p.L;
@@ -332,10 +334,10 @@ decomp0_word_sum_kernel(const D0WordSum p) {
             const int pos = p.list[first + k], b = pos / L, i = pos - b * L, len = clamp_len(p.len[b], L);
             const size_t row0 = (size_t)b * (L + 1);
             a += p.DVS[(size_t)pos * p.R + r];
-            c += p.DVf[(row0 + i + 1) * p.R + r] + p.DVb[(row0 + len - i) * p.R + r];
+            if constexpr (!MX) c += p.DVf[(row0 + i + 1) * p.R + r] + p.DVb[(row0 + len - i) * p.R + r];
         }
         p.dVs[(size_t)w * p.R + r] = a;
-        p.dRt[(size_t)w * p.R + r] = c;
+        if (!MX || n == 0) p.dRt[(size_t)w * p.R + r] = c;
     }
     if (!p.farnn) return;
     for (int s = threadIdx.x; s < p.S; s += 256) {

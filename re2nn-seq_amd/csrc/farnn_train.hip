@@ -23,6 +23,7 @@
 #include "ind1_train.hip.h"
 #include "decomp1_train.hip.h"
 #include "decomp0_train.hip.h"
+#include "decomp0_train_max.hip.h"
 #include "decomp1_gated_train.hip.h"
 #include "decomp1_gated_max_train.hip.h"
 #include "train_bucketed_crf.hip.h"
@@ -267,7 +268,7 @@ struct TrainStep : TrainPlan {
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
     int prep_jobs(); int product_jobs();
     int prepare(); int forward(); int max_forward(); int loss(); int backward(); int max_weight_gradients(); int gradients();
-    int max_backward() { return launch(tmax_backward_kernel, dim3(B, 2), TM_THREADS, lds_tok, s, p, m.mp); }
+    int max_backward() { return launch(tmax_backward_kernel<>, dim3(B, 2), TM_THREADS, lds_tok, s, p, m.mp); }
     int stages() {
         int rc;
         if ((rc = prepare()) || (rc = mx ? max_forward() : forward()) || (rc = loss())) return rc;
@@ -521,13 +522,15 @@ struct farnn_decomp_fst_train_ctx : TrainCtxBase {
     Tunables tun;
     farnn_decomp_fst_train_dims d;
     int n_cu = 256;
-    int semiring = FARNN_SEMIRING_SUM;  // (train_plan reads it: this step has the sum semiring only)
+    int semiring = FARNN_SEMIRING_SUM;  // farnn_decomp_fst_train_set_semiring
     DevBuf<float> fixed;          // create's block: what depends on the dimensions only (Decomp0Step::carve_fixed)
     DevBuf<float> ws;             // per-batch workspace (zeroed every step)
     DevBuf<int> iws;              // the bucketing of the positions by word
     DevBuf<float> part;           // partial products of the parameter-gradient reductions
     DevBuf<float> ones;           // 1.0f each: the chains' output mask and the bias gradients' column of ones
     size_t ones_filled = 0;       // how many of them a step has written (the buffer grows with the batch)
+    DevBuf<float> mws;            // max semiring only (Decomp0Step::carve_max_floats): M, MT, dM, IN, GM, the chunks' partial sums;
+    DevBuf<int> miws;             // IDX, the word slots -- allocated on first use
 };
 // what create's block holds
 struct D0Fixed {
@@ -573,6 +576,16 @@ extern "C" void farnn_decomp_fst_train_destroy(farnn_decomp_fst_train_ctx *c) { 
 extern "C" int farnn_decomp_fst_train_set_profiling(farnn_decomp_fst_train_ctx *c, int32_t enable) { return train_ctx_set_profiling("decomp_fst_train", c, enable); }
 extern "C" int farnn_decomp_fst_train_time(farnn_decomp_fst_train_ctx *c, double *total_ms, int64_t *steps) { return train_ctx_time("decomp_fst_train", c, total_ms, steps); }
 
+extern "C" int farnn_decomp_fst_train_set_semiring(farnn_decomp_fst_train_ctx *c, int32_t semiring) {
+    if (!c) return fail(FARNN_EINVAL, "decomp_fst_train_set_semiring: null context%s%s");
+    if (semiring != FARNN_SEMIRING_SUM && semiring != FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "decomp_fst_train_set_semiring: semiring must be FARNN_SEMIRING_SUM or FARNN_SEMIRING_MAX%s%s");
+    if (semiring == FARNN_SEMIRING_MAX && c->d.S > TM_MAX_S)
+        return fail(FARNN_ERANGE, "decomp_fst_train_set_semiring: the max-semiring step holds at most 192 states%s%s");
+    c->semiring = semiring;
+    return FARNN_OK;
+}
+
 // C = A B, k ascending, every element one owner (decomp1_gemm_kernel): A element (m, k) at A[m am + k ak], B (k, n) at B[k bk + n bn]
 static void d0_gemm(hipStream_t s, const float *A, size_t am, size_t ak, const float *Bm, size_t bk, size_t bn, float *Cm, int M, int N, int K) {
     const D1Gemm g = {A, Bm, nullptr, nullptr, Cm, M, N, K, am, ak, bk, bn, (size_t)N};
@@ -580,13 +593,16 @@ static void d0_gemm(hipStream_t s, const float *A, size_t am, size_t ak, const f
 }
 
 // One step.  The chains and their back-propagation are the decomposed i-FST's (TrainPlan, with_chain_form) on the word table
-// Rtab, the matrix W and a mask of ones; the stages are the member functions, in the order they run.
+// Rtab, the matrix W and a mask of ones; the stages are the member functions, in the order they run.  In the max semiring (mx) the
+// chains are the i-FST's max chains on the same inputs, and the chain inputs' gradients come from the per-word dM_w
+// (decomp0_train_max.hip.h) in place of the five chain products.
 struct Decomp0Step : TrainPlan {
     static constexpr const char *name = "decomp_fst_train", *label_range = "K";
     farnn_decomp_fst_train_ctx *c; const farnn_decomp_fst_train_weights *w; const farnn_decomp_fst_train_outputs *o; hipStream_t s;
     TrainParams p; D0Params q; D0Fixed f; PrepJobs prep; AtbJobs jobs; Buckets bk; BucketedCrf crfst;
     D0Lds lds0; unsigned grid0; size_t Q, need0, ineed;
     float *DVS, *U, *UW, *DP, *DQ, *DPW, *DQW, *loss_part;
+    MaxWs m; D0MaxWgrad mg; size_t mneed0, mineed0, lds_mw;      // max semiring only
 
     int validate() {
         if (!w->Vgen || !w->Ce || !w->S1 || !w->S2 || !w->Cw || !w->S1w || !w->S2w || !w->WW || !w->h0 || !w->hT)
@@ -611,6 +627,21 @@ struct Decomp0Step : TrainPlan {
         if (crf) crfst.carve(a, (size_t)B, (size_t)L, K, false);
         return off0 + a.off;
     }
+    // the max semiring's workspaces: the i-FST's blocks and per-step arrays, the chunks' partial sums behind them; the argmax
+    // of every step and the word slots (the bucketing is the step's own, iws)
+    size_t carve_max_floats0(float *base) {
+        const size_t off0 = carve_max_floats(base, m, *this);
+        Carver<float> a(base ? base + off0 : nullptr);
+        const size_t nch = d0max_chunks(nwmax);
+        mg.PS1 = a.take(nch * S * R); mg.PS2 = a.take(nch * S * R); mg.PW = a.take(nch * S * S);
+        return off0 + a.off;
+    }
+    size_t carve_max_ints0(int *base) {
+        Carver<int> a(base);
+        m.mp.IDXf = a.take(N1 * S); m.mp.IDXb = a.take(N1 * S);
+        m.mp.wslot = m.wslot = a.take(V); m.mp.wlist = m.wlist = a.take(nwmax); m.mp.nwords = m.nwords = a.take(1);
+        return a.off;
+    }
     // every size the step refuses, before anything is enqueued
     int plan(int B_, int L_) {
         Q = (size_t)c->d.Q;
@@ -623,13 +654,20 @@ struct Decomp0Step : TrainPlan {
         grid0 = (unsigned)std::min<size_t>(c->n_cu, (N0 + D0_TP - 1) / D0_TP);
         need0 = carve_ws(nullptr);
         ineed = carve_bucket_ints(nullptr, bk, V, N0);
+        if (mx) {
+            lds_mw = d0max_wgrad_lds_bytes(S);
+            if (int rc = lds_fits(lds_mw)) return rc;
+            mneed0 = carve_max_floats0(nullptr); mineed0 = carve_max_ints0(nullptr);
+        }
         return FARNN_OK;
     }
     int carve(const int64_t *x, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
-    int prepare(); int forward(); int loss(); int backward(); int gradients();
+    int prepare(); int forward(); int max_forward(); int loss(); int backward(); int gradients(); int max_gradients();
+    int max_backward() { return launch(tmax_backward_kernel<true>, dim3(B, 2), TM_THREADS, lds_tok, s, p, m.mp); }
     int stages() {
         int rc;
-        if ((rc = prepare()) || (rc = forward()) || (rc = loss())) return rc;
+        if ((rc = prepare()) || (rc = mx ? max_forward() : forward()) || (rc = loss())) return rc;
+        if (mx) return (rc = max_backward()) ? rc : max_gradients();
         return (rc = backward()) ? rc : gradients();
     }
     template <int PHASE>
@@ -649,8 +687,14 @@ int Decomp0Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *
         if ((rc = c->ones.ensure(nones, "decomp_fst_train_step: out of device memory for the column of ones%s%s"))) return rc;
         c->ones_filled = 0;
     }
+    if (mx && ((rc = c->mws.ensure(mneed0, "decomp_fst_train_step: out of device memory for the max-semiring workspace%s%s")) ||
+               (rc = c->miws.ensure(mineed0, "decomp_fst_train_step: out of device memory for the max-semiring index workspace%s%s")))) return rc;
     [[maybe_unused]] const size_t carved = carve_ws(c->ws.p), icarved = carve_bucket_ints(c->iws.p, bk, V, N0);
     assert(carved == need0 && icarved == ineed);
+    if (mx) {
+        [[maybe_unused]] const size_t mcarved = carve_max_floats0(c->mws.p), micarved = carve_max_ints0(c->miws.p);
+        assert(mcarved == mneed0 && micarved == mineed0);
+    }
     carve_d0_fixed(c->fixed.p, f, c->d);
     // the chains: the i-FST's kernels on (Rtab, S1, S2, W, gates), no output mask
     p.Vgen = f.Rtab; p.S1 = w->S1; p.S2 = w->S2; p.W = f.Wm; p.C = nullptr; p.h0 = w->h0; p.hT = w->hT; p.P = w->P;
@@ -694,17 +738,22 @@ int Decomp0Step::carve(const int64_t *x, const int64_t *lengths, const int64_t *
     const int iS = (int)S, iR = (int)R, iQ = (int)Q, iK = (int)K;
     const long long n1 = (long long)N1, n0 = (long long)N0;
     jobs.chunk = 128;
-    atb_add(jobs, p.Zf, p.Tf, o->dS2, n1, iS, iR);
-    if (!farnn) {
-        atb_add(jobs, p.A, p.D1f + R, o->dS1, n1 - 1, iS, iR);
-        atb_add(jobs, p.A, p.Zf + S, o->dWW, n1 - 1, iS, iS);
-    } else {
-        atb_add(jobs, p.HBARf, p.D1f, o->dS1, n1, iS, iR);
-        atb_add(jobs, p.HBARf, p.Zf, o->dWW, n1, iS, iS);
+    if (!mx) {
+        atb_add(jobs, p.Zf, p.Tf, o->dS2, n1, iS, iR);
+        if (!farnn) {
+            atb_add(jobs, p.A, p.D1f + R, o->dS1, n1 - 1, iS, iR);
+            atb_add(jobs, p.A, p.Zf + S, o->dWW, n1 - 1, iS, iS);
+        } else {
+            atb_add(jobs, p.HBARf, p.D1f, o->dS1, n1, iS, iR);
+            atb_add(jobs, p.HBARf, p.Zf, o->dWW, n1, iS, iS);
+        }
+        atb_add(jobs, p.Zb, p.Tb, o->dS1, n1, iS, iR);
+        atb_add(jobs, p.BBAR, p.D1b, o->dS2, n1, iS, iR);
+        atb_add(jobs, p.Zb, p.BBAR, o->dWW, n1, iS, iS);
+    } else {                                                         // dS1, dS2 and dWW are d0max_reduce_kernel's
+        mg.dM = m.dM; mg.S1 = w->S1; mg.S2 = w->S2; mg.Rtab = f.Rtab; mg.wlist = m.wlist; mg.nwords = m.nwords; mg.dRt = f.dRt;
+        mg.S = iS; mg.R = iR;
     }
-    atb_add(jobs, p.Zb, p.Tb, o->dS1, n1, iS, iR);
-    atb_add(jobs, p.BBAR, p.D1b, o->dS2, n1, iS, iR);
-    atb_add(jobs, p.Zb, p.BBAR, o->dWW, n1, iS, iS);
     atb_add(jobs, p.DS, U, o->dCe, n0, iK, iR);                      // dC_embed += ds x u
     atb_add(jobs, p.DS, UW, o->dCw, n0, iK, iQ);                     // dC_wildcard += ds x uw
     atb_add(jobs, p.A, DP, f.dS1s, n1, iS, iR);                      // alpha x dp
@@ -770,12 +819,30 @@ int Decomp0Step::backward() {
         return launch(train_backward_kernel<LDSW(), GATED(), VPS(), VPR(), NS(), true>, dim3((B + NS() - 1) / NS(), 2), TR_THREADS, lds_b, s, p);
     });
 }
+// Stage 5, max semiring: the distinct words' slots (the positions are bucketed by prepare()), their blocks Tr_w, both chains
+int Decomp0Step::max_forward() {
+    tmax_slots_kernel<<<1, 1024, 0, s>>>(bk.wcount, (int)V, m.wslot, m.wlist, m.nwords);
+    const unsigned nt = (unsigned)((S + 31) / 32);
+    tmax_premix_kernel<<<dim3((unsigned)nwmax, nt * nt), 256, 0, s>>>(f.Rtab, w->S1, w->S2, f.Wm, m.wlist, m.nwords, m.M, m.MT, (int)S, (int)R);
+    return launch(tmax_forward_kernel, dim3(B, 2), TM_THREADS, lds_tok, s, p, m.mp);
+}
+// Stage 8, max semiring: dM per distinct word; dS1, dS2, dWW and the words' rows of dRtab from it, the chunks in order; then
+// the sum step's reductions
+int Decomp0Step::max_gradients() {
+    int rc;
+    if ((rc = launch(tmax_dM_kernel, (unsigned)nwmax, TM_THREADS, lds_m, s, p, m.mp, bk.list, bk.wstart, bk.wcount, m.dM))) return rc;
+    if ((rc = launch(d0max_wgrad_kernel, dim3((unsigned)d0max_chunks(nwmax), (unsigned)((R + D0M_RB - 1) / D0M_RB)), D0_THREADS, lds_mw, s, mg))) return rc;
+    const size_t ne = std::max(S * R, S * S);
+    d0max_reduce_kernel<<<(unsigned)((ne + 255) / 256), 256, 0, s>>>(mg.PS1, mg.PS2, mg.PW, m.nwords, o->dS1, o->dS2, o->dWW, S * R, S * S);
+    return gradients();
+}
 // Stage 8: the reductions, all in a fixed order
 int Decomp0Step::gradients() {
     const int iV = (int)V, iS = (int)S, iR = (int)R, iQ = (int)Q;
     const D0WordSum ws = {bk.list, bk.wstart, bk.wcount, p.len, DVS, p.DVf, p.DVb, p.DAZf, p.DAZb, p.DARf, p.DARb,
                           f.dVs, f.dRt, f.dGV1, f.dGV2, L, iS, iR, farnn};
-    decomp0_word_sum_kernel<<<(unsigned)V, 256, 0, s>>>(ws);
+    if (mx) decomp0_word_sum_kernel<true><<<(unsigned)V, 256, 0, s>>>(ws);
+    else decomp0_word_sum_kernel<false><<<(unsigned)V, 256, 0, s>>>(ws);
     if (farnn) {                                               // dRtab += dGV Wrs^T, dWrs = Rtab^T dGV
         d0_gemm(s, f.dGV1, S, 1, w->Wrs1, 1, S, f.dRg1, iV, iR, iS);
         d0_gemm(s, f.Rtab, 1, R, f.dGV1, S, 1, o->dWrs1, iR, iS, iV);

@@ -205,7 +205,10 @@ tmax_forward_kernel(const TrainParams p, const TrainMaxParams m) {
 // grid (B, 2).  Thread s: the adjoint of state s, u[s] = d n[s]; the dTr entry u[s] in[j*(s)] goes to GM; then the
 // chain input's adjoint d in[j] = sum over the states s with j*(s) = j of u[s] G[j][s] (thread j, s ascending: no
 // atomics); the gate adjoints and the carry into step t - 1 as in train_backward_kernel.
+// DET (the decomposed FST's step, decomp0_train_max.hip.h): no float atomics, as train_backward_kernel's DET form -- the gates'
+// input adjoints stay in their rows DAZ / DAR, the sequence's dh0 / dhT go to HP, and dOsum (a mask of ones there) is dropped.
 // LDS: uu, dz, dr, jj [TM_MAX_S], toks[L]
+template <bool DET = false>
 __global__ void __launch_bounds__(TM_THREADS)
 tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
     __shared__ float uu[TM_MAX_S], dz[TM_MAX_S], dr[TM_MAX_S];
@@ -247,13 +250,13 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
                 const float daz = gt * (cand - hprev) * p.sig_k * z * (1.0f - z);
                 DAZ[row] = daz;
                 dz[s] = daz;
-                atomicAdd(p.dGV1 + (size_t)tok * S + s, daz);
+                if constexpr (!DET) atomicAdd(p.dGV1 + (size_t)tok * S + s, daz);
                 if (farnn == 2) { r = RG[row]; hp = (1.0f - r) * hin + r * hprev; }     // hbar
             } else {
                 yy = gt * nl_grad_from_output(stash[row], p.nl);
             }
             float u;
-            if (dir == 0) { u = yy * os; dOacc = fmaf(yy, p.PRE[row], dOacc); }       // mask on the output
+            if (dir == 0) { u = yy * os; if constexpr (!DET) dOacc = fmaf(yy, p.PRE[row], dOacc); }       // mask on the output
             else          { u = yy; }
             const int j = IDX[row];
             jj[s] = j; uu[s] = u;
@@ -267,7 +270,7 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
                 if (jj[k] == s) din = fmaf(uu[k], g[k], din);
             float dhb;
             if (dir == 0) dhb = din;
-            else { dOacc = fmaf(din, hp, dOacc); dhb = din * os; }                   // mask on the input
+            else { if constexpr (!DET) dOacc = fmaf(din, hp, dOacc); dhb = din * os; }                   // mask on the input
             if (!farnn) gacc = dhb;
             else if (farnn == 2) {                                                    // hbar = (1-r) h_init + r h_{t-1}
                 const float dar = dhb * (hprev - hin) * p.sig_k * r * (1.0f - r);
@@ -275,7 +278,7 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
                 dhk = fmaf(dhb, r, dhk);
                 DAR[row] = dar;
                 dr[s] = dar;
-                atomicAdd(p.dGV2 + (size_t)tok * S + s, dar);
+                if constexpr (!DET) atomicAdd(p.dGV2 + (size_t)tok * S + s, dar);
             } else {
                 dhk += dhb;
             }
@@ -295,8 +298,11 @@ tmax_backward_kernel(const TrainParams p, const TrainMaxParams m) {
     }
     if (own) {
         const float g0 = gacc + Gadj[row0 * S + s] + dhin;
-        if (g0 != 0.0f) atomicAdd((dir == 0 ? p.dh0 : p.dhT) + s, g0);
-        if (dOacc != 0.0f) atomicAdd(p.dOsum + s, dOacc);
+        if constexpr (DET) p.HP[((size_t)b * 2 + dir) * S + s] = g0;
+        else {
+            if (g0 != 0.0f) atomicAdd((dir == 0 ? p.dh0 : p.dhT) + s, g0);
+            if (dOacc != 0.0f) atomicAdd(p.dOsum + s, dOacc);
+        }
     }
 }
 

@@ -32,6 +32,7 @@ def default_device():
 #   DECOMP_IND1_GATED_MAX_TRAIN  the gated model under --train_mode max, beside DECOMP_IND1_TRAIN, DECOMP_IND1_GATED_TRAIN and
 #                             BUCKETED_MAX_TRAIN (and DECOMP_IND1_CRF_TRAIN under --use_crf 1)                f9
 #   DECOMP_FST_TRAIN          the decomposed FST's training step (FARNN_S_D_W; sum semiring)                  f11
+#   DECOMP_FST_MAX_TRAIN      that step under --train_mode max, beside DECOMP_FST_TRAIN                       f11
 #   BUCKETED_MAX_TRAIN        --train_mode max for the three steps over bucketed per-word blocks (the onehot
 #                             FST, the onehot and the decomposed independent=1 model), beside each model's own f7 - f9
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3

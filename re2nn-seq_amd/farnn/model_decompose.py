@@ -85,7 +85,8 @@ class FARNN_S_D_W(FARNN_S_D_W_I_S):
             torch.nn.init.normal_(self.h0)
             torch.nn.init.normal_(self.hT)
 
-    # ---- training step (reference :373-456 with train=True; opt-in: RE2NN_DECOMP_FST_TRAIN=1) ----
+    # ---- training step (reference :373-456 with train=True; opt-in: RE2NN_DECOMP_FST_TRAIN=1, and
+    # RE2NN_DECOMP_FST_MAX_TRAIN=1 beside it for --train_mode max) ----
     # which tensors get a gradient: the reference's requires_grad flags (:52-63, :104-165); the gates and crf.transitions follow
     # in FARNN_S_D_W_I_S._train_decl, always trainable
     _TRAIN_FLAGS = {'S1': None, 'S2': None, 'embed_r_generalized': None, 'V_embed': 'train_V_embed', 'C_embed': None,
@@ -104,8 +105,8 @@ class FARNN_S_D_W(FARNN_S_D_W_I_S):
         why = None
         if a.farnn not in (0, 1, 2):
             why = '--farnn {}'.format(a.farnn)
-        elif a.train_mode != 'sum':
-            why = 'the max semiring (--train_mode {})'.format(a.train_mode)
+        elif a.train_mode != 'sum' and not (a.train_mode == 'max' and opted_in('DECOMP_FST_MAX_TRAIN')):
+            why = 'the max semiring (--train_mode {})'.format(a.train_mode)      # (opt-in: RE2NN_DECOMP_FST_MAX_TRAIN=1)
         elif a.local_loss_func != 'CE1':
             why = 'a loss other than CE1 (--local_loss_func {})'.format(a.local_loss_func)
         elif re_tags is not None or getattr(a, 'marryup_type', 'none') not in ('none', None):
@@ -128,7 +129,7 @@ class FARNN_S_D_W(FARNN_S_D_W_I_S):
         K, Q = tp['C_wildcard'].shape
         return _lib.DecompFstTrainContext(tp['V_embed'].shape[0], S, R, Q, K, nl=a.update_nonlinear, threshold=a.threshold,
                                           o_idx=self.o_idx, device=self.device_index, use_crf=self.use_crf, farnn=int(a.farnn),
-                                          sigmoid_exponent=float(a.sigmoid_exponent))
+                                          sigmoid_exponent=float(a.sigmoid_exponent), semiring=self._semiring())
 
     def _train_call(self, x, lengths, lab, ntok, re_tags):
         tp = self._tp                  # the Vgen fold stays in torch, as for the decomposed i-FST

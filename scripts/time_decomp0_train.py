@@ -10,7 +10,10 @@ rotating through four batches of the same lengths.  Prints one JSON line:
   torch_us_per_step   the float32 torch restatement of the same step (forward + backward, batched over the sequences, on the
                       same device), wall time per step between two synchronizes, median; torch_loss its loss
 
-    python scripts/time_decomp0_train.py [--steps 10] [--warmup 2] [--stages 1] [--use_crf 0|1] [--farnn 0|1|2]
+    python scripts/time_decomp0_train.py [--steps 10] [--warmup 2] [--stages 1] [--use_crf 0|1] [--farnn 0|1|2] [--semiring sum|max]
+
+--semiring max times the max-semiring step (farnn_decomp_fst_train_set_semiring) against the same restatement with the two
+recurrences through torch.max.
 
 The line carries no rate: none was measured.  Each GPU step of a job script runs it under its own time limit
 (timeout -k 10 ...)."""
@@ -27,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def torch_step(torch, w, gates, trans, x, lens, labels, farnn, k=5.0):
+def torch_step(torch, w, gates, trans, x, lens, labels, farnn, k=5.0, mx=False):
     """the step restated in torch on the device, float32: loss (backward is the caller's)"""
     Vgen, Ce, S1, S2, Cw, S1w, S2w, WW, h0, hT = w
     B, L = x.shape
@@ -44,7 +47,11 @@ def torch_step(torch, w, gates, trans, x, lens, labels, farnn, k=5.0):
         if farnn == 2:
             g = torch.sigmoid(k * (h @ gates[3] + r @ gates[4] + gates[5]))
             hbar = (1 - g) * hin + g * h
-        n = torch.tanh(((hbar @ M1) * r) @ M2.t() + hbar @ Wm)
+        if mx:          # Tr[b, j, s] = sum_r M2[s, r] r[b, r] M1[j, r] + Wm[j, s];  n[s] = max_j hbar[j] Tr[j, s]
+            Tr = torch.einsum('sr,bjr->bjs', M2, r[:, None, :] * M1[None]) + Wm
+            n = torch.tanh((hbar.unsqueeze(2) * Tr).max(1).values)
+        else:
+            n = torch.tanh(((hbar @ M1) * r) @ M2.t() + hbar @ Wm)
         return n if z is None else (1 - z) * h + z * n
 
     a0, b0 = h0.expand(B, -1), hT.expand(B, -1)
@@ -79,6 +86,7 @@ def main():
     ap.add_argument('--stages', type=int, default=1)
     ap.add_argument('--use_crf', type=int, default=0)
     ap.add_argument('--farnn', type=int, choices=(0, 1, 2), default=0)
+    ap.add_argument('--semiring', choices=('sum', 'max'), default='sum')
     a = ap.parse_args()
     import torch
     from re2nn_seq_amd import _lib, synth
@@ -113,6 +121,8 @@ def main():
     ld = torch.from_numpy(lengths).to(dev)
     labd = [torch.from_numpy(v).to(dev) for v in labels]
     tc = _lib.DecompFstTrainContext(V, S, R, Q, K, nl='tanh', device=0, use_crf=bool(a.use_crf), farnn=a.farnn, sigmoid_exponent=5.0)
+    if a.semiring == 'max':
+        tc.set_semiring('max')
     td = None if trans is None else d(trans)
     gr = np.random.RandomState(77)
     gates = []
@@ -130,7 +140,7 @@ def main():
     def one_torch(i):
         for t in leaves:
             t.grad = None
-        loss = torch_step(torch, ws, gates, td, xd[i % 4], ld, labd[i % 4], a.farnn)
+        loss = torch_step(torch, ws, gates, td, xd[i % 4], ld, labd[i % 4], a.farnn, mx=a.semiring == 'max')
         loss.backward()
         return loss
 
@@ -149,7 +159,7 @@ def main():
     for t in leaves:
         sha.update(t.grad.cpu().numpy().tobytes())
     out = {'shape': {'V': V, 'S': S, 'K': K, 'R': R, 'Q': Q, 'B': B, 'L': L, 'nl': 'tanh'}, 'valid_tokens': ntok, 'steps': a.steps,
-           'use_crf': a.use_crf, 'farnn': a.farnn, 'result_sha': sha.hexdigest()[:16], 'lib_us_per_step': float(np.median(per)),
+           'use_crf': a.use_crf, 'farnn': a.farnn, 'semiring': a.semiring, 'result_sha': sha.hexdigest()[:16], 'lib_us_per_step': float(np.median(per)),
            'lib_us_min': float(min(per)), 'lib_us_max': float(max(per)), 'loss': float(loss.detach())}
     if a.stages:
         from torch.profiler import ProfilerActivity, profile
