@@ -903,6 +903,52 @@ int  farnn_score_read(farnn_score *h, farnn_score_counts *counts, void *stream);
 /* Back to the state after create (enqueued on `stream`, not awaited). */
 int  farnn_score_reset(farnn_score *h, void *stream);
 
+/* ---- CP-ALS of a 3-way tensor given as a coordinate list, float64 ------------------------------
+ * Stands in for tensorly.parafac as the reference calls it (wfa/tensor_func.py:7-13: init='random', normalize_factors=False, no
+ * weights): the step from an automaton's [V',S,S] tensor to the factors of IIID / IID.automata.*.pkl.  One sweep is, for mode
+ * n = 0, 1, 2:  H = Hadamard product of the two other factors' Gram matrices;  M = X_(n) (Khatri-Rao product of the two other
+ * factors), on the nonzeros;  A_n = solve(H^T, M^T)^T by Cholesky.  After each sweep, with the last mode's M,
+ *     rec_error = sqrt(| ||X||^2 + sum(G0 o G1 o G2) - 2 sum(M o A_2) |) / ||X||,
+ * and from the second sweep on the run stops when |rec_errors[-2] - rec_errors[-1]| < tol, or at n_iter_max.  The initial
+ * factors are the caller's (numpy.random.RandomState(seed).random_sample((dim_n, rank)), mode order 0, 1, 2, in the mirror).
+ * Factors are [dim_n][rank] doubles, C-contiguous.  Every sum is taken in an order fixed by the data (64-nonzero chunks of a
+ * row, 1024-row panels of a factor, a fixed tree), there is no float atomic: repeated calls are bit-identical.
+ * Limits: 1 <= rank <= min(max_rank, 352) (FARNN_ERANGE above, before any launch); dims below 2^22; nnz below 2^30.
+ * One caller thread and one stream at a time per context. */
+#define FARNN_ENUMERIC (-33)   /* a Cholesky pivot of a CP-ALS normal matrix was not a positive finite number (EDOM) */
+typedef struct farnn_cp_ctx farnn_cp_ctx;
+
+/* dims[3], idx0 / idx1 / idx2 [nnz] (int32), val [nnz] (double): HOST arrays, copied.  Repeated coordinates add.  The context
+ * keeps the nonzeros in three orders, one grouped by each mode's index, and ||X||^2; its buffers are sized for
+ * min(max_rank, 352).  FARNN_EINVAL: a null pointer, nnz <= 0, max_rank < 1, a dimension outside [1, 2^22), a coordinate outside
+ * its dimension, a norm that is zero or not finite. */
+int  farnn_cp_create(const int32_t *dims, int64_t nnz, const int32_t *idx0, const int32_t *idx1, const int32_t *idx2,
+                     const double *val, int32_t max_rank, int device, farnn_cp_ctx **out);
+void farnn_cp_destroy(farnn_cp_ctx *ctx);
+/* The three stages on their own; f0 / f1 / f2, out, H, M are DEVICE pointers (the factor of `mode` itself is not read by the
+ * first two and may be NULL); enqueued on `stream` (hipStream_t as void*, NULL = the default stream).
+ * out [dims[mode]][rank] = the MTTKRP; a row without a nonzero gives zeros. */
+int  farnn_cp_mttkrp(farnn_cp_ctx *ctx, int32_t mode, int32_t rank, const double *f0, const double *f1, const double *f2,
+                     double *out, void *stream);
+/* H [rank][rank] = (A_a^T A_a) o (A_b^T A_b) of the two other modes, on v_mfma_f64_16x16x4_f64; symmetric bit for bit. */
+int  farnn_cp_normal_matrix(farnn_cp_ctx *ctx, int32_t mode, int32_t rank, const double *f0, const double *f1, const double *f2,
+                            double *H, void *stream);
+/* out [rows][rank] = M H^-1 for the symmetric positive definite H (its lower triangle is read): Cholesky, two triangular solves,
+ * no explicit inverse.  This entry waits for `stream` and reads the pivot flag: FARNN_ENUMERIC if a pivot was not a positive
+ * finite number (`out` is then meaningless; the flag is cleared and the context stays usable). */
+int  farnn_cp_solve(farnn_cp_ctx *ctx, int32_t rank, const double *H, const double *M, int32_t rows, double *out, void *stream);
+/* A whole run.  f0 / f1 / f2: HOST arrays, the initial factors in and the result out; rec_errors: HOST, [n_iter_max];
+ * *n_sweeps: the sweeps done (= the entries of rec_errors written).  The factors cross the bus once each way; in between the
+ * host reads one double and the pivot flag per sweep.  FARNN_ENUMERIC as farnn_cp_solve (the factors are then left as given). */
+int  farnn_cp_run(farnn_cp_ctx *ctx, int32_t rank, int32_t n_iter_max, double tol, double *f0, double *f1, double *f2,
+                  double *rec_errors, int32_t *n_sweeps, void *stream);
+/* enable != 0: the following runs time their stages with HIP events (and wait after every stage); also clears the totals.
+ * stage_ms[4]: normal matrix, MTTKRP, solve, error terms -- milliseconds summed over `*sweeps` timed sweeps. */
+int  farnn_cp_set_profiling(farnn_cp_ctx *ctx, int32_t enable);
+int  farnn_cp_time(farnn_cp_ctx *ctx, double *stage_ms, int64_t *sweeps);
+/* ||X||^2 and the number of distinct coordinates, as create computed them */
+int  farnn_cp_norm2(const farnn_cp_ctx *ctx, double *normx2, int64_t *nnz);
+
 /* ---- introspection / measurement ----------------------------------------------------- */
 int  farnn_abi_version(void);
 /* 1: the A/B (profiling) build of the library (csrc/build.py --probes): it also carries the forms the production build left behind --

@@ -223,6 +223,18 @@ SIGNATURES = {
     'farnn_score_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'farnn_score_read': (C.c_int, [C.c_void_p, C.POINTER(ScoreCounts), C.c_void_p]),
     'farnn_score_reset': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'farnn_cp_create': (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_double), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_cp_destroy': (None, [C.c_void_p]),
+    'farnn_cp_mttkrp': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'farnn_cp_normal_matrix': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    'farnn_cp_solve': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'farnn_cp_run': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p]),
+    'farnn_cp_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
+    'farnn_cp_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_cp_norm2': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_optim_create': (C.c_int, [C.POINTER(OptimDesc), C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_optim_destroy': (None, [C.c_void_p]),
     'farnn_optim_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -924,3 +936,93 @@ class Score:
 
     def reset(self, stream=None):
         check(load().farnn_score_reset(self._raw, stream), 'farnn_score_reset')
+
+
+ENUMERIC, ERANGE, EINVAL = -33, -34, -22       # FARNN_ENUMERIC, FARNN_ERANGE, FARNN_EINVAL
+CP_CHUNK, CP_PANEL, CP_TILE, CP_MAX_RANK = 64, 1024, 16, 352      # csrc/cp_als.hip.h
+
+
+class CpContext:
+    """Owns one farnn_cp_ctx* (float64 CP-ALS of a 3-way tensor given as a coordinate list, include/farnn.h).  A failed call
+    raises FarnnError with the return code in `.code`, except FARNN_ENUMERIC (a singular normal matrix), which raises
+    numpy.linalg.LinAlgError like the solve of the library it stands in for."""
+
+    def __init__(self, dims, idx0, idx1, idx2, val, max_rank, device=0):
+        self._raw = None
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a), dtype=np.int32)      # noqa: E731
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                     # noqa: E731
+        idx0, idx1, idx2 = i32(idx0), i32(idx1), i32(idx2)
+        val = np.ascontiguousarray(np.asarray(val), dtype=np.float64)
+        n = val.shape[0]
+        if not (idx0.shape == idx1.shape == idx2.shape == val.shape == (n,)):
+            raise ValueError('idx0, idx1, idx2 and val must be one-dimensional and equally long')
+        self.dims = tuple(int(d) for d in dims)
+        d = (C.c_int32 * 3)(*self.dims)
+        out = C.c_void_p()
+        self._check(load().farnn_cp_create(d, n, ip(idx0), ip(idx1), ip(idx2), val.ctypes.data_as(C.POINTER(C.c_double)),
+                                           int(max_rank), int(device), C.byref(out)), 'farnn_cp_create')
+        self._raw = out
+        self.max_rank = int(max_rank)
+
+    @staticmethod
+    def _check(rc, what):
+        if rc == OK:
+            return
+        msg = load().farnn_last_error()
+        text = '{} failed with code {}: {}'.format(what, rc, msg.decode() if msg else '')
+        if rc == ENUMERIC:
+            raise np.linalg.LinAlgError(text)
+        err = FarnnError(text)
+        err.code = rc
+        raise err
+
+    def close(self):
+        if self._raw:
+            load().farnn_cp_destroy(self._raw)
+            self._raw = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def norm2(self):
+        """(||X||^2, distinct coordinates)"""
+        v, n = C.c_double(0), C.c_int64(0)
+        self._check(load().farnn_cp_norm2(self._raw, C.byref(v), C.byref(n)), 'farnn_cp_norm2')
+        return v.value, n.value
+
+    def mttkrp(self, mode, rank, f_ptrs, out_ptr, stream=None):
+        """f_ptrs: the three factors' device pointers (the one of `mode` may be None)"""
+        self._check(load().farnn_cp_mttkrp(self._raw, int(mode), int(rank), f_ptrs[0], f_ptrs[1], f_ptrs[2], out_ptr, stream),
+                    'farnn_cp_mttkrp')
+
+    def normal_matrix(self, mode, rank, f_ptrs, H_ptr, stream=None):
+        self._check(load().farnn_cp_normal_matrix(self._raw, int(mode), int(rank), f_ptrs[0], f_ptrs[1], f_ptrs[2], H_ptr, stream),
+                    'farnn_cp_normal_matrix')
+
+    def solve(self, rank, H_ptr, M_ptr, rows, out_ptr, stream=None):
+        self._check(load().farnn_cp_solve(self._raw, int(rank), H_ptr, M_ptr, int(rows), out_ptr, stream), 'farnn_cp_solve')
+
+    def run(self, rank, n_iter_max, tol, factors, stream=None):
+        """factors: three float64 arrays [dim_n, rank] (the initial factors; not modified).  Returns (factors, rec_errors)."""
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))                    # noqa: E731
+        f = [np.array(a, dtype=np.float64, order='C') for a in factors]
+        for a, d in zip(f, self.dims):
+            if a.shape != (d, int(rank)):
+                raise ValueError('a factor must be [dim, rank] = {}, got {}'.format((d, int(rank)), a.shape))
+        errs = np.zeros(max(int(n_iter_max), 1), dtype=np.float64)
+        n = C.c_int32(0)
+        self._check(load().farnn_cp_run(self._raw, int(rank), int(n_iter_max), float(tol), dp(f[0]), dp(f[1]), dp(f[2]), dp(errs),
+                                        C.byref(n), stream), 'farnn_cp_run')
+        return f, [float(e) for e in errs[:n.value]]
+
+    def set_profiling(self, enable):
+        self._check(load().farnn_cp_set_profiling(self._raw, int(bool(enable))), 'farnn_cp_set_profiling')
+
+    def time(self):
+        """({'normal_matrix', 'mttkrp', 'solve', 'error'}: milliseconds summed, timed sweeps)"""
+        ms, n = (C.c_double * 4)(), C.c_int64(0)
+        self._check(load().farnn_cp_time(self._raw, ms, C.byref(n)), 'farnn_cp_time')
+        return dict(zip(('normal_matrix', 'mttkrp', 'solve', 'error'), [float(v) for v in ms])), n.value

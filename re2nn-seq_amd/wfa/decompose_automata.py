@@ -1,0 +1,219 @@
+"""Automaton -> decomposed-model pickles: the reference's ``src_seq/wfa/decompose_automata.py`` on the library's CP-ALS
+(wfa/tensor_func.py).  Same names, rank tables, seed arithmetic (``rands = rands + k * 8``), best-of-``k_best`` by the last
+error, pickle schema (init_params.py documents it) and file names; the data directory, the output directory and the rank lists
+are optional arguments with the reference's values as defaults.
+
+    python -m re2nn_seq_amd.wfa.decompose_automata --dataset D --automata_path P --independent 1|2
+           [--ranks 100,150] [--output_ranks 70] [--k_best K] [--data_dir DIR] [--out_dir DIR]
+
+``decompose_automata`` (independent = 0, the 4-way ``D.automata`` writer) is not built."""
+import argparse
+import os
+import pickle
+from copy import copy, deepcopy
+
+from numpy.linalg import LinAlgError
+
+from . import tensor_func
+from ..data import load_slot_dataset
+from ..utils import create_datetime_str, load_pkl
+from .fsa_to_tensor import dfa_to_tensor_slot_independent_wildcard, dfa_to_tensor_slot_single_wildcard
+
+DATA_DIR = '../../data/'
+OUTPUT_TENSOR_RANKS = [70, 100, 150]
+N_SEEDS = 4
+
+
+def ranks_single(dataset_name):
+    """ref :341-358"""
+    return {'MITR': [100, 150, 200], 'MITR-BIO': [250, 300], 'MITM-E-BIO': [200, 250, 300], 'ATIS-BIO': [100, 150, 200],
+            'ATIS-ZH-BIO': [300], 'SNIPS-BIO': [200, 250, 300], 'CONLL03-BIO': [100, 150, 200]}.get(dataset_name, [100, 150, 200])
+
+
+def ranks_independent(dataset_name):
+    """ref :174-187"""
+    return {'MITR': [100, 150, 200], 'MITR-BIO': [150, 200, 250], 'MITM-E-BIO': [150, 200, 250], 'ATIS-BIO': [100, 150, 200],
+            'ATIS-ZH-BIO': [150, 200, 250], 'CONLL03-BIO': [100, 150, 200]}.get(dataset_name, [100, 150, 200])
+
+
+def _best_of(k_best, rands, decompose, make_dict, copier, catch):
+    """The reference's restart loop: `rands` grows by k * 8 before every try, a try that raises `catch` is skipped, the lowest
+    last error wins.  Returns (best dict or None, lowest error, rands)."""
+    lowest_rec_error = float('inf')
+    best_save_dict = None
+    for k in range(k_best):
+        print('BEST of {}: {}'.format(k_best, k))
+        rands = rands + k * 8
+        try:
+            result = decompose(rands)
+        except catch:
+            print('Value Error or LinAlgError')
+            continue
+        rec_error = result[-1]
+        if rec_error[-1] < lowest_rec_error:
+            best_save_dict = copier(make_dict(*result[:-1]))
+            lowest_rec_error = rec_error[-1]
+    return best_save_dict, lowest_rec_error, rands
+
+
+def _dump(obj, out_dir, kind, dataset_name, time_str, init, k_best, n_states, automata_name, split_group, info_str, rule_name):
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, '{kind}.automata.{time_str}.{init}.{k}best.{n}states.{automata_name}.{split}splits.{info}.'
+                                 '{rule_name}.pkl'.format(kind=kind, time_str=time_str, init=init, k=k_best, n=n_states,
+                                                          automata_name=automata_name, split=split_group, info=info_str,
+                                                          rule_name=rule_name))
+    with open(path, 'wb') as f:
+        pickle.dump(obj, f)
+    print('FINISHED')
+    return path
+
+
+def _out_dir(out_dir, data_dir, dataset_name):
+    return out_dir if out_dir is not None else os.path.join(data_dir, dataset_name, 'automata')
+
+
+def decompose_automata(rearranged_automata, dataset_name, automata_name, split_group, init='random', k_best=5, rule_name=''):
+    """ref :17-145 (the 4-way tensor of --independent 0)"""
+    raise NotImplementedError('the D.automata writer needs the CP decomposition of a 4-way tensor, which is not built '
+                              '(DESIGN.md section 9)')
+
+
+def decompose_automata_independent(rearranged_automata, dataset_name, automata_name, split_group, init='random', k_best=5,
+                                   rule_name='', data_dir=DATA_DIR, out_dir=None, ranks=None, output_tensor_ranks=None):
+    """ref :148-312: IID.automata.*.pkl (--independent 1).  Returns the path written."""
+    print('AUTOMATA TO TENSOR')
+    print('Total States: {}'.format(len(rearranged_automata['states'])))
+    data = load_slot_dataset(dataset_name, data_dir)
+    word2idx, slot2idx = data['t2i'], data['s2i']
+    # (the reference's dfa_to_tensor_slot_independent is the _wildcard layout with the `oo` slice split off)
+    language_tensor, state2idx, wildcard_mat, new_output_tensor, _, final_vector, start_vector, language = \
+        dfa_to_tensor_slot_independent_wildcard(rearranged_automata, word2idx, slot2idx, dataset=dataset_name)
+    output_tensor, output_wildcard_mat = new_output_tensor[:-1], new_output_tensor[-1]
+
+    print('DECOMPOSE SPLIT AUTOMATA')
+    ranks = ranks_independent(dataset_name) if ranks is None else list(ranks)
+    output_tensor_ranks = OUTPUT_TENSOR_RANKS if output_tensor_ranks is None else list(output_tensor_ranks)
+    time_str = create_datetime_str()
+    n_states = len(rearranged_automata['states'])
+    all_decomposed_automata = dict()
+    all_decomposed_automata['automata'] = rearranged_automata
+    info_str = ''
+    for random_state in range(N_SEEDS):
+        rands = random_state
+        output_factor_dicts = dict()       # C related params
+        output_factor_dicts_w = dict()     # C+1 related params
+        for output_tensor_rank in output_tensor_ranks:
+            print('DECOMPOSING WILDCARD TENSOR RANK: {}, TENSOR SIZE: {}'.format(output_tensor_rank, output_tensor.shape))
+            best, _, rands = _best_of(
+                k_best, rands,
+                lambda r: tensor_func.decompose_tensor_split_slot_3d(output_tensor, output_tensor_rank, random_state=r, init=init,
+                                                                     verbose=1, n_iter_max=40),
+                lambda C, S1, S2: {'C_output': C, 'S1_output': S1, 'S2_output': S2, 'wildcard_output': output_wildcard_mat},
+                copy, ValueError)
+            output_factor_dicts[output_tensor_rank] = best
+            print('DECOMPOSING NEW WILDCARD TENSOR RANK: {}, TENSOR SIZE: {}'.format(output_tensor_rank, new_output_tensor.shape))
+            best, _, rands = _best_of(
+                k_best, rands,
+                lambda r: tensor_func.decompose_tensor_split_slot_3d(new_output_tensor, output_tensor_rank, random_state=r,
+                                                                     init=init, verbose=1, n_iter_max=40),
+                lambda C, S1, S2: {'C_output': C, 'S1_output': S1, 'S2_output': S2, 'wildcard_output': None},
+                deepcopy, ValueError)
+            output_factor_dicts_w[output_tensor_rank] = best
+
+        info_str = ''
+        factor_dicts = dict()
+        rands = 0
+        for rank in ranks:
+            print('DECOMPOSING RANK: {}, TENSOR SIZE: {}'.format(rank, language_tensor.shape))
+            best, lowest, rands = _best_of(
+                k_best, rands,
+                lambda r: tensor_func.decompose_tensor_split_slot_3d_language(language_tensor, language=language, word2idx=word2idx,
+                                                                              rank=rank, random_state=r, n_iter_max=40, init=init,
+                                                                              verbose=1),
+                lambda V, S1, S2: {'V': V, 'S1': S1, 'S2': S2, 'wildcard_mat': wildcard_mat},
+                copy, (ValueError, LinAlgError))
+            factor_dicts[rank] = best
+            info_str += '{}-{}'.format(rank, lowest.__round__(4))
+        all_decomposed_automata[random_state] = [factor_dicts, output_factor_dicts, output_factor_dicts_w]
+
+    return _dump(all_decomposed_automata, _out_dir(out_dir, data_dir, dataset_name), 'IID', dataset_name, time_str, init, k_best,
+                 n_states, automata_name, split_group, info_str, rule_name)
+
+
+def decompose_automata_single(rearranged_automata, dataset_name, automata_name, split_group, init='random', k_best=2, rule_name='',
+                              data_dir=DATA_DIR, out_dir=None, ranks=None):
+    """ref :315-433: IIID.automata.*.pkl (--independent 2).  Returns the path written."""
+    print('AUTOMATA TO TENSOR')
+    print('Total States: {}'.format(len(rearranged_automata['states'])))
+    data = load_slot_dataset(dataset_name, data_dir)
+    word2idx, slot2idx = data['t2i'], data['s2i']
+    # (the reference's dfa_to_tensor_slot_single is the _wildcard layout with the `oo` row split off)
+    language_tensor, state2idx, wildcard_mat, output_mat_new, _, final_vector, start_vector, language = \
+        dfa_to_tensor_slot_single_wildcard(rearranged_automata, word2idx, slot2idx, dataset=dataset_name)
+    output_mat, output_wildcard_vector = output_mat_new[:-1], output_mat_new[-1]
+
+    print('DECOMPOSE SPLIT AUTOMATA')
+    ranks = ranks_single(dataset_name) if ranks is None else list(ranks)
+    time_str = create_datetime_str()
+    n_states = len(rearranged_automata['states'])
+    output_factor_dicts = {'output_mat': output_mat, 'output_wildcard_vector': output_wildcard_vector}
+    output_factor_dicts_w = {'output_mat': output_mat_new, 'output_wildcard_vector': output_wildcard_vector}
+    all_decomposed_automata = dict()
+    all_decomposed_automata['automata'] = rearranged_automata
+    print(language)
+    info_str = ''
+    for random_state in range(N_SEEDS):
+        info_str = ''
+        factor_dicts = dict()
+        rands = random_state
+        for rank in ranks:
+            print('DECOMPOSING RANK: {}, TENSOR SIZE: {}'.format(rank, language_tensor.shape))
+            best, lowest, rands = _best_of(
+                k_best, rands,
+                lambda r: tensor_func.decompose_tensor_split_slot_3d_language(language_tensor, language=language, word2idx=word2idx,
+                                                                              rank=rank, random_state=r, n_iter_max=32, init=init,
+                                                                              verbose=1),
+                lambda V, S1, S2: {'V': V, 'S1': S1, 'S2': S2, 'wildcard_mat': wildcard_mat},
+                copy, (ValueError, LinAlgError))
+            factor_dicts[rank] = best
+            info_str += '{}-{}'.format(rank, lowest.__round__(4))
+        all_decomposed_automata[random_state] = [factor_dicts, output_factor_dicts, output_factor_dicts_w]
+
+    return _dump(all_decomposed_automata, _out_dir(out_dir, data_dir, dataset_name), 'IIID', dataset_name, time_str, init, k_best,
+                 n_states, automata_name, split_group, info_str, rule_name)
+
+
+def _int_list(text):
+    return [int(v) for v in text.split(',') if v]
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description='decompose an automaton into the pickles --method decompose loads')
+    p.add_argument('--dataset', required=True)
+    p.add_argument('--automata_path', required=True, help='the automaton pickle (the dict itself or {"automata": dict})')
+    p.add_argument('--independent', type=int, required=True, choices=[0, 1, 2])
+    p.add_argument('--ranks', type=_int_list, default=None)
+    p.add_argument('--output_ranks', type=_int_list, default=None)
+    p.add_argument('--k_best', type=int, default=None)
+    p.add_argument('--data_dir', default=DATA_DIR)
+    p.add_argument('--out_dir', default=None)
+    p.add_argument('--automata_name', default=None)
+    p.add_argument('--split_group', type=int, default=1)
+    p.add_argument('--rule_name', default='')
+    args = p.parse_args(argv)
+    automata = load_pkl(args.automata_path)
+    if 'automata' in automata:
+        automata = automata['automata']
+    name = args.automata_name or os.path.basename(args.automata_path)
+    if args.independent == 0:
+        return decompose_automata(automata, args.dataset, name, args.split_group, rule_name=args.rule_name)
+    if args.independent == 1:
+        return decompose_automata_independent(automata, args.dataset, name, args.split_group, k_best=args.k_best or 5,
+                                              rule_name=args.rule_name, data_dir=args.data_dir, out_dir=args.out_dir,
+                                              ranks=args.ranks, output_tensor_ranks=args.output_ranks)
+    return decompose_automata_single(automata, args.dataset, name, args.split_group, k_best=args.k_best or 2,
+                                     rule_name=args.rule_name, data_dir=args.data_dir, out_dir=args.out_dir, ranks=args.ranks)
+
+
+if __name__ == '__main__':
+    print(main())
