@@ -949,6 +949,32 @@ int  farnn_cp_time(farnn_cp_ctx *ctx, double *stage_ms, int64_t *sweeps);
 /* ||X||^2 and the number of distinct coordinates, as create computed them */
 int  farnn_cp_norm2(const farnn_cp_ctx *ctx, double *normx2, int64_t *nnz);
 
+/* ---- the same for a tensor of order 3 or 4 -------------------------------------------------------------
+ * Order 4 is tensorly.parafac as the reference's tensor4_to_factors calls it (wfa/tensor_func.py:16-27; the mirror passes
+ * tol = 1e-6): the step from an automaton's [V',C,S,S] tensor to the factors of D.automata.*.pkl.  One sweep is, for mode
+ * n = 0 .. order-1:  H = Hadamard product of the OTHER factors' Gram matrices (three at order 4);  M = the MTTKRP on the nonzeros,
+ * each term val * Fa[ia] * Fb[ib] (* Fc[ic]) with the other factors in ascending mode order;  A_n = M H^-1 as above.  After the
+ * sweep, with M of the last mode (order - 1),
+ *     rec_error = sqrt(| ||X||^2 + sum(G0 o .. o G_last) - 2 sum(M o A_last) |) / ||X||;
+ * the stop rule, the pivot flag, the limits and the fixed summation orders are the 3-way entries'.  The context keeps the
+ * nonzeros in `order` orders, one grouped by each mode.  Repeated coordinates are found by comparing coordinate TUPLES and
+ * ||X||^2 is the merged values' sum of squares: nothing rests on a flattened index, so no product of dims is refused.
+ * An order-3 context made here is the one farnn_cp_create makes, bit for bit, and serves the 3-way entries too.  The 3-way
+ * entries (farnn_cp_mttkrp, _normal_matrix, _run) on an order-4 context return FARNN_EINVAL before any launch; farnn_cp_solve,
+ * _set_profiling, _time, _norm2 and _destroy serve both orders. */
+/* dims[order]; idx[order]: HOST pointers to HOST int32 arrays [nnz].  FARNN_EINVAL as farnn_cp_create, and for an order outside
+ * {3, 4}. */
+int  farnn_cp_create_n(int32_t order, const int32_t *dims, int64_t nnz, const int32_t *const *idx, const double *val,
+                       int32_t max_rank, int device, farnn_cp_ctx **out);
+int  farnn_cp_order(const farnn_cp_ctx *ctx, int32_t *order);
+/* f[order]: a HOST array of DEVICE pointers (f[mode] is not read and may be NULL).  FARNN_EINVAL before any launch for
+ * mode >= the context's order. */
+int  farnn_cp_mttkrp_n(farnn_cp_ctx *ctx, int32_t mode, int32_t rank, const double *const *f, double *out, void *stream);
+int  farnn_cp_normal_matrix_n(farnn_cp_ctx *ctx, int32_t mode, int32_t rank, const double *const *f, double *H, void *stream);
+/* f[order]: HOST pointers to HOST arrays, the initial factors in and the result out; the rest as farnn_cp_run. */
+int  farnn_cp_run_n(farnn_cp_ctx *ctx, int32_t rank, int32_t n_iter_max, double tol, double *const *f, double *rec_errors,
+                    int32_t *n_sweeps, void *stream);
+
 /* ---- introspection / measurement ----------------------------------------------------- */
 int  farnn_abi_version(void);
 /* 1: the A/B (profiling) build of the library (csrc/build.py --probes): it also carries the forms the production build left behind --

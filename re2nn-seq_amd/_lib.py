@@ -235,6 +235,13 @@ SIGNATURES = {
     'farnn_cp_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_cp_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_cp_norm2': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    'farnn_cp_create_n': (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_double),
+                                    C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_cp_order': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    'farnn_cp_mttkrp_n': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    'farnn_cp_normal_matrix_n': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    'farnn_cp_run_n': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int32), C.c_void_p]),
     'farnn_optim_create': (C.c_int, [C.POINTER(OptimDesc), C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
     'farnn_optim_destroy': (None, [C.c_void_p]),
     'farnn_optim_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -943,12 +950,16 @@ CP_CHUNK, CP_PANEL, CP_TILE, CP_MAX_RANK = 64, 1024, 16, 352      # csrc/cp_als.
 
 
 class CpContext:
-    """Owns one farnn_cp_ctx* (float64 CP-ALS of a 3-way tensor given as a coordinate list, include/farnn.h).  A failed call
-    raises FarnnError with the return code in `.code`, except FARNN_ENUMERIC (a singular normal matrix), which raises
-    numpy.linalg.LinAlgError like the solve of the library it stands in for."""
+    """Owns one farnn_cp_ctx* (float64 CP-ALS of a 3-way or 4-way tensor given as a coordinate list, include/farnn.h).  A failed
+    call raises FarnnError with the return code in `.code`, except FARNN_ENUMERIC (a singular normal matrix), which raises
+    numpy.linalg.LinAlgError like the solve of the library it stands in for.
+
+    ``CpContext(dims, idx0, idx1, idx2, val, max_rank)`` is the 3-way form on the 3-way entries; ``CpContext.from_coo(dims,
+    idx_list, val, max_rank)`` takes 3 or 4 index arrays and goes through the farnn_cp_*_n entries."""
 
     def __init__(self, dims, idx0, idx1, idx2, val, max_rank, device=0):
         self._raw = None
+        self._n = False
         i32 = lambda a: np.ascontiguousarray(np.asarray(a), dtype=np.int32)      # noqa: E731
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                     # noqa: E731
         idx0, idx1, idx2 = i32(idx0), i32(idx1), i32(idx2)
@@ -963,6 +974,37 @@ class CpContext:
                                            int(max_rank), int(device), C.byref(out)), 'farnn_cp_create')
         self._raw = out
         self.max_rank = int(max_rank)
+
+    @classmethod
+    def from_coo(cls, dims, idx_list, val, max_rank, device=0):
+        """A tensor of order len(dims) = len(idx_list), 3 or 4, through farnn_cp_create_n (which refuses every other order)."""
+        self = cls.__new__(cls)
+        self._raw = None
+        self._n = True
+        idx = [np.ascontiguousarray(np.asarray(a), dtype=np.int32) for a in idx_list]
+        val = np.ascontiguousarray(np.asarray(val), dtype=np.float64)
+        n = val.shape[0] if val.ndim == 1 else -1
+        if len(idx) != len(dims) or any(a.shape != (n,) for a in idx):
+            raise ValueError('one index array per dimension, each one-dimensional and as long as val')
+        self.dims = tuple(int(d) for d in dims)
+        d = (C.c_int32 * max(len(self.dims), 1))(*self.dims)
+        ip = (C.c_void_p * max(len(idx), 1))(*[a.ctypes.data for a in idx])
+        out = C.c_void_p()
+        self._check(load().farnn_cp_create_n(len(self.dims), d, n, ip, val.ctypes.data_as(C.POINTER(C.c_double)), int(max_rank),
+                                             int(device), C.byref(out)), 'farnn_cp_create_n')
+        self._raw = out
+        self.max_rank = int(max_rank)
+        return self
+
+    @property
+    def order(self):
+        n = C.c_int32(0)
+        self._check(load().farnn_cp_order(self._raw, C.byref(n)), 'farnn_cp_order')
+        return n.value
+
+    @staticmethod
+    def _ptr_array(ptrs):
+        return (C.c_void_p * len(ptrs))(*[None if p is None else int(p) for p in ptrs])
 
     @staticmethod
     def _check(rc, what):
@@ -994,11 +1036,23 @@ class CpContext:
         return v.value, n.value
 
     def mttkrp(self, mode, rank, f_ptrs, out_ptr, stream=None):
-        """f_ptrs: the three factors' device pointers (the one of `mode` may be None)"""
+        """f_ptrs: the factors' device pointers, one per mode (the one of `mode` may be None)"""
+        if len(f_ptrs) != len(self.dims):
+            raise ValueError('one factor pointer per mode')
+        if self._n:
+            self._check(load().farnn_cp_mttkrp_n(self._raw, int(mode), int(rank), self._ptr_array(f_ptrs), out_ptr, stream),
+                        'farnn_cp_mttkrp_n')
+            return
         self._check(load().farnn_cp_mttkrp(self._raw, int(mode), int(rank), f_ptrs[0], f_ptrs[1], f_ptrs[2], out_ptr, stream),
                     'farnn_cp_mttkrp')
 
     def normal_matrix(self, mode, rank, f_ptrs, H_ptr, stream=None):
+        if len(f_ptrs) != len(self.dims):
+            raise ValueError('one factor pointer per mode')
+        if self._n:
+            self._check(load().farnn_cp_normal_matrix_n(self._raw, int(mode), int(rank), self._ptr_array(f_ptrs), H_ptr, stream),
+                        'farnn_cp_normal_matrix_n')
+            return
         self._check(load().farnn_cp_normal_matrix(self._raw, int(mode), int(rank), f_ptrs[0], f_ptrs[1], f_ptrs[2], H_ptr, stream),
                     'farnn_cp_normal_matrix')
 
@@ -1006,14 +1060,21 @@ class CpContext:
         self._check(load().farnn_cp_solve(self._raw, int(rank), H_ptr, M_ptr, int(rows), out_ptr, stream), 'farnn_cp_solve')
 
     def run(self, rank, n_iter_max, tol, factors, stream=None):
-        """factors: three float64 arrays [dim_n, rank] (the initial factors; not modified).  Returns (factors, rec_errors)."""
+        """factors: one float64 array [dim_n, rank] per mode (the initial factors; not modified).  Returns (factors, rec_errors)."""
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))                    # noqa: E731
         f = [np.array(a, dtype=np.float64, order='C') for a in factors]
+        if len(f) != len(self.dims):
+            raise ValueError('one factor per mode')
         for a, d in zip(f, self.dims):
             if a.shape != (d, int(rank)):
                 raise ValueError('a factor must be [dim, rank] = {}, got {}'.format((d, int(rank)), a.shape))
         errs = np.zeros(max(int(n_iter_max), 1), dtype=np.float64)
         n = C.c_int32(0)
+        if self._n:
+            self._check(load().farnn_cp_run_n(self._raw, int(rank), int(n_iter_max), float(tol),
+                                              self._ptr_array([a.ctypes.data for a in f]), dp(errs), C.byref(n), stream),
+                        'farnn_cp_run_n')
+            return f, [float(e) for e in errs[:n.value]]
         self._check(load().farnn_cp_run(self._raw, int(rank), int(n_iter_max), float(tol), dp(f[0]), dp(f[1]), dp(f[2]), dp(errs),
                                         C.byref(n), stream), 'farnn_cp_run')
         return f, [float(e) for e in errs[:n.value]]

@@ -1,15 +1,16 @@
-// Kernels of the float64 CP-ALS on coordinate lists (farnn_cp_*; include/farnn.h, DESIGN.md row f12).  Host code: farnn_cp.hip.
+// Kernels of the float64 CP-ALS on coordinate lists (farnn_cp_*; include/farnn.h, DESIGN.md rows f12, f13).  Host code: farnn_cp.hip.
 //
-// One ALS stage for mode n is: H = Gram(A_a) o Gram(A_b) of the two other factors, M = the MTTKRP on the nonzeros, A_n = M H^-1 by
-// Cholesky.  Every sum below is taken in an order fixed by the DATA (chunks of a row, panels of a factor, a fixed tree), never by the
+// One ALS stage for mode n is: H = the Hadamard product of the other factors' Gram matrices (two at order 3, three at order 4),
+// M = the MTTKRP on the nonzeros, A_n = M H^-1 by Cholesky.  Every sum below is taken in an order fixed by the DATA (chunks of a row, panels of a factor, a fixed tree), never by the
 // launch geometry, and there is no float atomic anywhere: a repeated call gives the same bits.
-//   cp_mttkrp_chunk_kernel   one thread per (chunk of <= CP_CHUNK nonzeros of one row, rank column): the chunk's sum, in list order
+//   cp_mttkrp_chunk_kernel   <ORDER> one thread per (chunk of <= CP_CHUNK nonzeros of one row, rank column): the chunk's sum, in list
+//                            order; a term is val * Fa[ia] * Fb[ib] (* Fc[ic] at order 4), the other modes ascending
 //   cp_mttkrp_row_kernel     one thread per (row, rank column): the row's chunk sums in chunk order (an empty row: zero) -- the one
 //                            owner of the output element.  A long row (state 0 owns most edges) is spread over its chunks' threads
 //   cp_gram_kernel           one wavefront per (16 x 16 tile of the upper triangle, panel of CP_PANEL factor rows): v_mfma_f64_16x16x4_f64
 //                            down the panel, one accumulator, rows in order
-//   cp_hadamard_kernel       H[i][j] = (sum of the a-panels) * (sum of the b-panels), panels in order, read from the upper triangle
-//                            only: H is symmetric bit for bit
+//   cp_hadamard_kernel       <NG> H[i][j] = (sum of the a-panels) * (sum of the b-panels) (* (sum of the c-panels) at order 4), panels in
+//                            order, read from the upper triangle only: H is symmetric bit for bit
 //   cp_cholesky_kernel       one workgroup, left-looking in 16-column panels: the panel and the 16 finished rows it needs live in LDS,
 //                            the factor L (and its transpose, for the solves' contiguous reads) in global memory
 //   cp_trisolve_kernel       one workgroup per CP_TILE right-hand-side rows (in LDS): L y = m, then L^T x = y, column by column
@@ -36,17 +37,26 @@ struct CpSlot {                     // what the host reads once per sweep
 };
 
 // ---- MTTKRP -----------------------------------------------------------------------------------------------------------------
-// chunk_beg / chunk_end: the nonzero range of a chunk (one row's, at most CP_CHUNK long); ia / ib: the two other modes' indices
+// chunk_beg / chunk_end: the nonzero range of a chunk (one row's, at most CP_CHUNK long); ia / ib / ic: the other modes' indices in
+// ascending mode order (ic and Fc are not read at ORDER 3, whose sum is the one it always was)
+template <int ORDER>
 __global__ void __launch_bounds__(CP_THREADS) cp_mttkrp_chunk_kernel(const int *__restrict__ chunk_beg, const int *__restrict__ chunk_end,
                                                                      int nchunks, const int *__restrict__ ia, const int *__restrict__ ib,
-                                                                     const double *__restrict__ val, const double *__restrict__ Fa,
-                                                                     const double *__restrict__ Fb, int R, double *__restrict__ part) {
+                                                                     const int *__restrict__ ic, const double *__restrict__ val,
+                                                                     const double *__restrict__ Fa, const double *__restrict__ Fb,
+                                                                     const double *__restrict__ Fc, int R, double *__restrict__ part) {
+    static_assert(ORDER == 3 || ORDER == 4, "CP-ALS of order 3 or 4");
     const int ch = blockIdx.x * 4 + threadIdx.y, r = blockIdx.y * 64 + threadIdx.x;
     if (ch >= nchunks || r >= R) return;
     const int beg = chunk_beg[ch], end = chunk_end[ch];
     double acc = 0.0;
-    for (int e = beg; e < end; e++)
-        acc += val[e] * Fa[(size_t)ia[e] * R + r] * Fb[(size_t)ib[e] * R + r];
+    if constexpr (ORDER == 3) {
+        for (int e = beg; e < end; e++)
+            acc += val[e] * Fa[(size_t)ia[e] * R + r] * Fb[(size_t)ib[e] * R + r];
+    } else {
+        for (int e = beg; e < end; e++)
+            acc += val[e] * Fa[(size_t)ia[e] * R + r] * Fb[(size_t)ib[e] * R + r] * Fc[(size_t)ic[e] * R + r];
+    }
     part[(size_t)ch * R + r] = acc;
 }
 
@@ -92,12 +102,18 @@ __device__ __forceinline__ double cp_gram_at(const double *__restrict__ P, int p
     return s;
 }
 
+template <int NG>
 __global__ void __launch_bounds__(CP_THREADS) cp_hadamard_kernel(const double *__restrict__ Pa, int panels_a, const double *__restrict__ Pb,
-                                                                 int panels_b, int R, double *__restrict__ H) {
+                                                                 int panels_b, const double *__restrict__ Pc, int panels_c, int R,
+                                                                 double *__restrict__ H) {
+    static_assert(NG == 2 || NG == 3, "two Grams at order 3, three at order 4");
     const int idx = blockIdx.x * CP_THREADS + threadIdx.x;
     if (idx >= R * R) return;
     const int i = idx / R, j = idx - i * R;
-    H[idx] = cp_gram_at(Pa, panels_a, R, i, j) * cp_gram_at(Pb, panels_b, R, i, j);
+    if constexpr (NG == 2)
+        H[idx] = cp_gram_at(Pa, panels_a, R, i, j) * cp_gram_at(Pb, panels_b, R, i, j);
+    else
+        H[idx] = cp_gram_at(Pa, panels_a, R, i, j) * cp_gram_at(Pb, panels_b, R, i, j) * cp_gram_at(Pc, panels_c, R, i, j);
 }
 
 // ---- Cholesky: H = L L^T, lower; H's lower triangle is read -------------------------------------------------------------------

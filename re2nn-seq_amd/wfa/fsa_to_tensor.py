@@ -1,7 +1,8 @@
 """Automaton dict -> dense numpy tensors: the ".pkl loader" side of the tagging path.
 
 Boundary restatement of the reference's ``src_seq/wfa/fsa_to_tensor.py:398-615``
-(``dfa_to_tensor_slot_{new,independent,single}_wildcard``).  The three public functions
+(``dfa_to_tensor_slot_{new,independent,single}_wildcard``) and of ``:176-257``
+(``dfa_to_tensor_slot_new``, the layout the D.automata writer decomposes).  The public functions
 keep the reference's names, argument order and return tuples so that the drivers read the
 same; internally they share one edge walker that reports every edge as
 ``(word ids, label column, from index, to index, is_wildcard)``.
@@ -125,6 +126,57 @@ def dfa_to_tensor_slot_new_wildcard(automata, word2idx, slot2idx, dataset='MITR-
     print("LANGUAGE SET SIZE: {}".format(len(language)))
     return (language_tensor, state2idx, wildcard_tensor, wildcard_wildcard_tensor,
             final_vector, start_vector, sorted(language))
+
+
+def dfa_to_tensor_slot_new(automata, word2idx, slot2idx, dataset='MITR-BIO'):
+    """The layout the D.automata writer decomposes (ref :176-257): C = len(slot2idx) with no `oo` column.  A '$<:>oo' edge goes to
+    wildcard_wildcard_tensor[S,S], a '$' edge with a slot to wildcard_tensor[C,S,S], word and class edges to
+    language_tensor[V,C,S,S]; `oo` must sit on a '$' edge; an out-of-vocabulary rule word writes nothing."""
+    state2idx, edges = _walk_edges(automata, word2idx, slot2idx, dataset, strict_oo=True)
+    S, C, V = len(automata['states']), len(slot2idx), len(word2idx)
+    language_tensor = np.zeros((V, C, S, S))
+    wildcard_tensor = np.zeros((C, S, S))
+    wildcard_wildcard_tensor = np.zeros((S, S))
+    language = set()
+    for wids, col, fi, ti, words in edges:
+        if wids is None:
+            if col == C:
+                wildcard_wildcard_tensor[fi, ti] = 1
+            else:
+                wildcard_tensor[col, fi, ti] = 1
+        else:
+            language_tensor[wids, col, fi, ti] = 1
+            language.update(words)
+    final_vector, start_vector = _start_final(automata, S)
+    print("LANGUAGE SET SIZE: {}".format(len(language)))
+    return (language_tensor, state2idx, wildcard_tensor, wildcard_wildcard_tensor,
+            final_vector, start_vector, sorted(language))
+
+
+def dfa_to_edges_slot_new(automata, word2idx, slot2idx, dataset='MITR-BIO'):
+    """dfa_to_tensor_slot_new without the dense [V,C,S,S] tensor: its nonzeros (all of value 1) as int32 coordinate arrays, each
+    coordinate once, in lexicographic order.  Returns (word, label, frm, to, dims, state2idx, wildcard_tensor,
+    wildcard_wildcard_tensor, final_vector, start_vector, language), dims = (V, C, S, S) the tensor's shape."""
+    state2idx, edges = _walk_edges(automata, word2idx, slot2idx, dataset, strict_oo=True)
+    S, C, V = len(automata['states']), len(slot2idx), len(word2idx)
+    wildcard_tensor = np.zeros((C, S, S))
+    wildcard_wildcard_tensor = np.zeros((S, S))
+    language = set()
+    coords = []
+    for wids, col, fi, ti, words in edges:
+        if wids is None:
+            if col == C:
+                wildcard_wildcard_tensor[fi, ti] = 1
+            else:
+                wildcard_tensor[col, fi, ti] = 1
+        else:
+            coords += [(w, col, fi, ti) for w in wids]
+            language.update(words)
+    coords = np.unique(np.asarray(coords, dtype=np.int32).reshape(-1, 4), axis=0)      # an entry set twice is still 1
+    final_vector, start_vector = _start_final(automata, S)
+    print("LANGUAGE SET SIZE: {}".format(len(language)))
+    return (coords[:, 0].copy(), coords[:, 1].copy(), coords[:, 2].copy(), coords[:, 3].copy(), (V, C, S, S), state2idx,
+            wildcard_tensor, wildcard_wildcard_tensor, final_vector, start_vector, sorted(language))
 
 
 def dfa_to_tensor_slot_independent_wildcard(automata, word2idx, slot2idx, dataset='MITR-BIO'):
