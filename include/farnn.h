@@ -319,8 +319,36 @@ int farnn_tag(farnn_model *m, const int64_t *x, const int64_t *lengths, int32_t 
               int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream);
 
 /* Pre-size the handle's device workspace so that farnn_tag() for up to (B,L) allocates nothing
- * (required before capturing farnn_tag() into a hipGraph). */
+ * (required before capturing farnn_tag() into a hipGraph).  On a vector-input handle (below) this also sizes the token
+ * table [B L][Rp + SP per gate] and the identity id array: a later farnn_tag_vectors() within (B,L) allocates nothing. */
 int farnn_reserve(farnn_model *m, int32_t B, int32_t L);
+
+/* ---- vector input: FARNN_S_SF (reference model_decompose_single.py:307-579) -------------------------------------------
+ * The decomposed i-FST recurrence on a dense input, one rule-space vector per token, in place of word ids and a per-word
+ * table: whatever produces contextual token vectors (the reference: EmbedAggregator behind an encoder) reaches the
+ * automaton through it.
+ *
+ * farnn_decomp_sf_create takes farnn_decomp_ifst_desc with V = 0 and Vgen = NULL (anything else: FARNN_EINVAL); nothing
+ * per word is ever built.  Sum semiring only: the max semiring needs an S x S block per token and is refused with
+ * FARNN_EINVAL.  The CRF, the priority layer P and the gates (farnn 0 / 1 / 2) are the id handle's.
+ *
+ * farnn_tag_vectors:
+ *   v        float32 [B,L,R] dense (device); rows at positions >= lengths[b] are never read (they may hold anything).
+ *   lengths, tags, flat_tags, scores, stream: as in farnn_tag.
+ *   mode     FARNN_MODE_LOCAL only (forward_score / forward_RE exist on the onehot models): anything else FARNN_EINVAL.
+ * Every call first builds a token table -- per valid position [v padded to Rp | v . Wrs1 + bs1 | v . Wrs2 + bs2], the gate
+ * halves summed in exactly the order the id handle's create-time table uses -- and then runs the id path's recurrence,
+ * score and decode kernels unchanged on the ids b L + t.  A vector that is bit for bit a row of Vgen is therefore tagged
+ * bit for bit like that word on an id handle of the same weights.
+ * Shapes the packed-rows kernels do not hold fall back to decomp_chain_kernel on an id handle; that kernel is NOT served
+ * from the token table: such a shape is refused with FARNN_ERANGE before anything is launched -- at create when
+ * Rp + SP per gate > 2048, at the call when no packed-rows form fits the call's L.
+ * farnn_tag on a vector-input handle, and farnn_tag_vectors on any other handle, are refused with FARNN_EINVAL (so is
+ * farnn_tag_host_submit, which calls farnn_tag).
+ * These two entry points were ADDED to ABI version 2: no existing signature or struct changed, so the number stands. */
+int farnn_decomp_sf_create(const farnn_decomp_ifst_desc *desc, int device, farnn_model **out);
+int farnn_tag_vectors(farnn_model *m, const float *v, const int64_t *lengths, int32_t B, int32_t L,
+                      int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream);
 
 void farnn_destroy(farnn_model *m);
 
@@ -993,7 +1021,8 @@ double farnn_kernel_algorithmic_bytes(const farnn_model *m, int32_t which, int64
  * on every N-th farnn_tag() call (N=1: every call; event records cost a few microseconds of
  * launch latency each, so a stride keeps the timed region honest); enable=0 stops.
  * farnn_kernel_time() synchronises, then reports the accumulated milliseconds and the number of
- * timed launches of kernel `which` (0 = recurrence chain, 1 = score+decode, 2 = prep). */
+ * timed launches of kernel `which` (0 = recurrence chain, 1 = score+decode, 2 = prep, 3 = the token table of
+ * farnn_tag_vectors). */
 int  farnn_set_profiling(farnn_model *m, int32_t enable);
 int  farnn_kernel_time(farnn_model *m, int32_t which, double *total_ms, int64_t *launches);
 /* the kernel behind slot `which`, read from the plan of the handle's last farnn_tag() call (before the first call, and after

@@ -17,7 +17,7 @@ NL = {'none': 0, 'relu': 1, 'tanh': 2, 'relutanh': 3, 'sigmoid': 4}
 SEMIRING = {'sum': 0, 'max': 1}
 MODE_LOCAL, MODE_FULL, MODE_RE = 0, 1, 2
 HOST_SLOTS = 4                  # FARNN_HOST_SLOTS: batches the host-buffer path keeps in flight
-KERN_CHAIN, KERN_SCORE, KERN_PREP = 0, 1, 2
+KERN_CHAIN, KERN_SCORE, KERN_PREP, KERN_TABLE = 0, 1, 2, 3
 
 _f32p = C.POINTER(C.c_float)
 
@@ -333,6 +333,8 @@ SIGNATURES = {
     'farnn_decomp_fst_create': (C.c_int, [C.POINTER(DecompFstDesc), C.c_int, C.POINTER(_vp)]),
     'farnn_tag': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     'farnn_reserve': (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    'farnn_decomp_sf_create': (C.c_int, [C.POINTER(DecompIfstDesc), C.c_int, C.POINTER(_vp)]),
+    'farnn_tag_vectors': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     'farnn_tag_host_submit': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'farnn_flatten_host': (C.c_int64, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     'farnn_tag_host_wait': (C.c_int, [_vp, C.c_int32, _vp, C.POINTER(C.c_int64)]),
@@ -437,6 +439,11 @@ class Handle:
     def tag(self, x_ptr, len_ptr, B, L, mode, tags_ptr=None, flat_ptr=None, scores_ptr=None, stream=None):
         check(load().farnn_tag(self.raw, x_ptr, len_ptr, B, L, mode, tags_ptr, flat_ptr, scores_ptr,
                                stream), 'farnn_tag')
+
+    def tag_vectors(self, v_ptr, len_ptr, B, L, mode=MODE_LOCAL, tags_ptr=None, flat_ptr=None, scores_ptr=None, stream=None):
+        """farnn_tag on a vector-input handle (create_decomp_sf): v float32 [B, L, R] dense on the device, MODE_LOCAL only."""
+        check(load().farnn_tag_vectors(self.raw, v_ptr, len_ptr, B, L, mode, tags_ptr, flat_ptr, scores_ptr,
+                                       stream), 'farnn_tag_vectors')
 
     def tag_host_submit(self, x_ptr, len_ptr, B, L):
         """Host buffers in (int64 [B,L], [B]); returns a ticket for tag_host_wait.  Work is enqueued, not awaited."""
@@ -614,6 +621,23 @@ def create_decomp_ifst(Vgen, S1, S2, W, Cout, h0, hT, P=None, farnn=0, gates=Non
                        float(sigmoid_exponent), NL[nl], SEMIRING[semiring], float(threshold), int(o_idx),
                        int(bool(use_crf)), ptr(crf_trans), 0)
     return _create('farnn_decomp_ifst_create', d, device, (Vgen, S1, S2, W, Cout, h0, hT, P, crf_trans, g))
+
+
+def create_decomp_sf(S1, S2, W, Cout, h0, hT, P=None, farnn=0, gates=None, sigmoid_exponent=5, nl='none', semiring='sum',
+                     threshold=0.5, o_idx=0, use_crf=False, crf_trans=None, device=0):
+    """The decomposed i-FST on vectors (FARNN_S_SF): create_decomp_ifst without a word table; tag with Handle.tag_vectors."""
+    S1, S2, W, Cout, h0, hT = (f32(a) for a in (S1, S2, W, Cout, h0, hT))
+    P = None if P is None else f32(P)
+    crf_trans = None if crf_trans is None else f32(crf_trans)
+    g = {k: f32(v) for k, v in (gates or {}).items()}
+    S, R = S1.shape
+    d = DecompIfstDesc(0, S, R, Cout.shape[0], None, ptr(S1), ptr(S2), ptr(W), ptr(Cout),
+                       ptr(h0), ptr(hT), ptr(P), int(farnn),
+                       ptr(g.get('Wss1')), ptr(g.get('Wrs1')), ptr(g.get('bs1')),
+                       ptr(g.get('Wss2')), ptr(g.get('Wrs2')), ptr(g.get('bs2')),
+                       float(sigmoid_exponent), NL[nl], SEMIRING[semiring], float(threshold), int(o_idx),
+                       int(bool(use_crf)), ptr(crf_trans), 0)
+    return _create('farnn_decomp_sf_create', d, device, (S1, S2, W, Cout, h0, hT, P, crf_trans, g))
 
 
 def create_decomp_ifst_folded(V_embed, E, G, beta, S1, S2, W, Cout, h0, hT, add_nl='none', normalize='none', P=None,

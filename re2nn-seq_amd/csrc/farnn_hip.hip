@@ -42,6 +42,9 @@ extern "C" int farnn_set_compact(farnn_model *m, int32_t enable) {
 }
 
 // ---- workspace -------------------------------------------------------------------------------
+// floats of a row of the token table: what decomp_rows_kernel calls tvl
+static int sf_row_floats(const farnn_model *m) { return m->Rp + (m->dw.farnn >= 1 ? m->SP : 0) + (m->dw.farnn == 2 ? m->SP : 0); }
+
 extern "C" int farnn_reserve(farnn_model *m, int32_t B, int32_t L) {
     if (!m || B <= 0 || L <= 0) return fail(FARNN_EINVAL, "reserve: bad arguments%s%s");
     Workspace &w = m->ws;
@@ -63,6 +66,14 @@ extern "C" int farnn_reserve(farnn_model *m, int32_t B, int32_t L) {
         FARNN_HIP_TRY(hipMalloc((void **)&w.crf_scores, (size_t)nB * nL * m->Kp * sizeof(float) + 1024));   // +1 KiB: LDS-DMA pieces
     if (m->d1_BSSp)
         FARNN_HIP_TRY(hipMalloc((void **)&w.d1_br, (size_t)nB * nL * ((m->S + 15) / 16) * ((m->RO + 15) / 16 * 16) * sizeof(float)));
+    if (m->sf) {      // the token table (rows of the handle's own tvl floats; +1 KiB like dev_alloc) and the identity ids of the largest call
+        const size_t nt = (size_t)nB * nL, tt_bytes = nt * sf_row_floats(m) * sizeof(float) + 1024;
+        FARNN_HIP_TRY(hipMalloc((void **)&w.tt, tt_bytes));
+        FARNN_HIP_TRY(hipMemset(w.tt, 0, tt_bytes));       // (rows of pad positions are never written; nothing reads them either)
+        FARNN_HIP_TRY(hipMalloc((void **)&w.ids, nt * sizeof(int64_t)));
+        iota_kernel<<<(unsigned)((nt + 255) / 256), 256>>>(w.ids, (long long)nt);
+        FARNN_HIP_TRY(hipGetLastError());
+    }
     FARNN_HIP_TRY(hipMemset(w.A, 0, stash));
     FARNN_HIP_TRY(hipMemset(w.Bk, 0, stash));
     FARNN_HIP_TRY(hipDeviceSynchronize());
@@ -327,6 +338,11 @@ static int plan_tag(const farnn_model *m, int B, int L, int full, bool flat, boo
         case KIND_DECOMP:
             if (m->dense_decomp) return plan_chain_and_decode(m, p, flat, scores, offs, lm_tags, offs_ok);
             plan_decomp_recurrence(m, p, !m->use_crf, offs_ok);
+            if (m->sf) {
+                if (p.rec == REC_DECOMP_CHAIN)     // (decomp_chain_kernel is not served from the token table: include/farnn.h)
+                    return fail(FARNN_ERANGE, "tag_vectors: no packed-rows form holds this model at this sequence length%s%s");
+                p.table = true; p.table_cols = sf_row_floats(m) - m->Rp;
+            }
             return p.fused ? FARNN_OK : plan_score_decode(m, p, flat, scores, offs);
         case KIND_DECOMP0:
             // the score kernel's tile and its static tokid[] share the workgroup's 160 KiB: refused here, before anything is launched
@@ -380,7 +396,12 @@ extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
                 case REC_CHAIN_REGS: return p.fused ? "chain_regs_kernel<fused: scores + decode beside the recurrence>"
                                                     : (p.half ? "chain_regs_kernel<f16 blocks>" : "chain_regs_kernel");
                 case REC_DECOMP_REGS: return p.fused ? "decomp_regs_kernel<fused: scores + decode beside the recurrence>" : "decomp_regs_kernel";
-                case REC_DECOMP_ROWS: return "decomp_rows_kernel";
+                case REC_DECOMP_ROWS: {      // (a vector-input handle reports the form too; the id handles' name is what it always was)
+                    static const char *const forms[] = {"decomp_rows_kernel<form 0>", "decomp_rows_kernel<form 1>", "decomp_rows_kernel<form 2>",
+                        "decomp_rows_kernel<form 3>", "decomp_rows_kernel<form 4>", "decomp_rows_kernel<form 5>", "decomp_rows_kernel<form 6>",
+                        "decomp_rows_kernel<form 7>", "decomp_rows_kernel<form 8>", "decomp_rows_kernel<form 9>", "decomp_rows_kernel<form 10>"};
+                    return (m->sf && p.rows.form >= 0 && p.rows.form <= 10) ? forms[p.rows.form] : "decomp_rows_kernel";
+                }
                 case REC_DECOMP_CHAIN: return "decomp_chain_kernel";
                 default: return "chain_kernel";
             }
@@ -392,6 +413,7 @@ extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
                               : (m->kind == KIND_DECOMP0 ? "decomp0_score_kernel"
                               : (m->use_crf ? "score_tile_kernel+viterbi_kernel" : (m->last_lm_score ? "label_map_score_kernel" : "score_tile_kernel")))));
         case KERN_PREP:  return "batch_prep_kernel";
+        case KERN_TABLE: return m->sf ? "token_table_kernel" : "";
         default: return "";
     }
 }
@@ -529,10 +551,14 @@ static int launch_compact(farnn_model *m, const TagPlan &pl, const int64_t *x, c
 static int launch_decomp_recurrence(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
     const int *order = pl.order_valid ? m->ws.order : nullptr;
     const int sort = pl.sort_in_kernel ? 1 : 0;
+    // a vector-input call: the same kernels on the call's token table -- its rows in place of the per-word rows, one "word" per position
+    DecompWeights dw = m->dw;
+    DecompRowsPack rows = m->rows;
+    if (pl.table) { dw.V = pl.B * pl.L; dw.Vgen = m->ws.tt; rows.TVt = m->ws.tt; }
     KernelTimer kt(m, KERN_CHAIN, s);
     if (pl.rec == REC_DECOMP_ROWS)
-        return launch_decomp_rows(m->rows, m->dw, pl.rows, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, pl.rows_cu, s);
-    if (pl.rec == REC_DECOMP_CHAIN) return launch_decomp_chain(m->dw, x, len, order, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s);
+        return launch_decomp_rows(rows, dw, pl.rows, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, pl.rows_cu, s);
+    if (pl.rec == REC_DECOMP_CHAIN) return launch_decomp_chain(dw, x, len, order, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s);
     BesideParams bs;
     if (pl.fused) {
         memset(&bs, 0, sizeof(bs));
@@ -540,7 +566,7 @@ static int launch_decomp_recurrence(farnn_model *m, const TagPlan &pl, const int
         handoff_words(m, &bs.prog, &bs.arr, &bs.done);
         bs.spin = tun(TUN_FUSE_SPIN); bs.dbg = tun(TUN_DBG); bs.sp = sp;
     }
-    return launch_decomp_regs(m->rows, m->dw, pl.regs, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s, pl.fused ? &bs : nullptr);
+    return launch_decomp_regs(rows, dw, pl.regs, x, len, order, sort, m->ws.A, m->ws.Bk, pl.B, pl.L, pl.full, s, pl.fused ? &bs : nullptr);
 }
 
 static int launch_recurrence(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, const ScoreParams &sp, hipStream_t s) {
@@ -700,9 +726,19 @@ __global__ void clamp_oo_column_kernel(float *scores, long long rows, int K, int
     }
 }
 
-// order the streams, reserve, plan, then launch from the plan: prep, recurrence, scores + decode
+// the token table of a vector-input call (decomp_vec.hip.h)
+static int launch_table(farnn_model *m, const TagPlan &pl, const float *v, const int64_t *len, hipStream_t s) {
+    TokenTableParams p;
+    p.v = v; p.len = len; p.Wrs1 = m->dw.Wrs1; p.bs1 = m->dw.bs1; p.Wrs2 = m->dw.Wrs2; p.bs2 = m->dw.bs2; p.TT = m->ws.tt;
+    p.B = pl.B; p.L = pl.L; p.R = m->R; p.Rp = m->Rp; p.S = m->S; p.SP = m->SP; p.tvl = sf_row_floats(m); p.ncols = pl.table_cols;
+    KernelTimer kt(m, KERN_TABLE, s);
+    return launch_token_table(p, s);
+}
+
+// order the streams, reserve, plan, then launch from the plan: prep, (token table,) recurrence, scores + decode
+// v != nullptr: farnn_tag_vectors -- x is ignored, the recurrence runs on the workspace's identity ids
 static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, int32_t B, int32_t L,
-                    int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream) {
+                    int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream, const float *v = nullptr) {
     TunScope tun_scope(&m->tun);
     FARNN_HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -746,6 +782,10 @@ static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, in
         FARNN_HIP_TRY(hipGetLastError());
     }
     const ScoreParams sp = make_score_params(m, pl, lengths, tags, flat_tags, scores);
+    if (pl.table) {
+        if ((rc = launch_table(m, pl, v, lengths, s))) return rc;
+        x = m->ws.ids;
+    }
     if ((rc = launch_recurrence(m, pl, x, lengths, sp, s))) return rc;
     return launch_score(m, pl, x, lengths, sp, tags, flat_tags, scores, s);
 }
@@ -756,6 +796,7 @@ extern "C" int farnn_tag(farnn_model *m, const int64_t *x, const int64_t *length
     if (B <= 0 || L <= 0) return fail(FARNN_EINVAL, "tag: B and L must be positive%s%s");
     if (mode != FARNN_MODE_LOCAL && mode != FARNN_MODE_FULL && mode != FARNN_MODE_RE)
         return fail(FARNN_EINVAL, "tag: bad mode%s%s");
+    if (m->sf) return fail(FARNN_EINVAL, "tag: this handle takes vectors, not word ids (farnn_decomp_sf_create): call farnn_tag_vectors%s%s");
     if (mode != FARNN_MODE_RE) return tag_impl(m, x, lengths, B, L, mode, tags, flat_tags, scores, stream);
     if (m->kind != KIND_IFST && m->kind != KIND_FST4 && m->kind != KIND_IND1)
         return fail(FARNN_EINVAL, "tag: FARNN_MODE_RE exists on the onehot models only (model_onehot.py:148)%s%s");
@@ -766,6 +807,17 @@ extern "C" int farnn_tag(farnn_model *m, const int64_t *x, const int64_t *length
         scores, rows, m->K, m->C - 1, m->threshold);
     FARNN_HIP_TRY(hipGetLastError());
     return FARNN_OK;
+}
+
+extern "C" int farnn_tag_vectors(farnn_model *m, const float *v, const int64_t *lengths, int32_t B, int32_t L,
+                                 int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream) {
+    if (!m || !v || !lengths) return fail(FARNN_EINVAL, "tag_vectors: null model / v / lengths%s%s");
+    if (B <= 0 || L <= 0) return fail(FARNN_EINVAL, "tag_vectors: B and L must be positive%s%s");
+    if (!m->sf) return fail(FARNN_EINVAL, "tag_vectors: this handle takes word ids (only farnn_decomp_sf_create makes a vector-input handle): call farnn_tag%s%s");
+    if (mode != FARNN_MODE_LOCAL)
+        return fail(FARNN_EINVAL, "tag_vectors: FARNN_MODE_LOCAL only (forward_score / forward_RE exist on the onehot models only)%s%s");
+    if ((long long)B * L > 0x7fffffffLL) return fail(FARNN_ERANGE, "tag_vectors: more than 2^31 - 1 positions%s%s");
+    return tag_impl(m, nullptr, lengths, B, L, mode, tags, flat_tags, scores, stream, v);
 }
 
 static void host_slot_free(farnn_model::HostSlot &h) {

@@ -581,7 +581,9 @@ static int build_rows_pack(farnn_model *m) {
         pack_p1_kernel<<<blocks((long long)k.n1 * k.ld2), 256>>>(q, k.P1, k.ld2);
     }
     // the per-word rows a step reads, side by side: [Vgen row | update-gate row | reset-gate row] (one base, one load per prefetch slot)
-    if (w.farnn == 0) {
+    if (m->V == 0) {
+        k.TVt = nullptr;                    // a vector-input handle: the table is built per call (decomp_vec.hip.h)
+    } else if (w.farnn == 0) {
         k.TVt = w.Vgen;
     } else {
         float *T = nullptr;
@@ -618,7 +620,7 @@ static int upload_chain_factors(farnn_model *m, const float *Vgen, int odV, cons
     w.S = m->S; w.SP = m->SP; w.R = m->R; w.Rp = m->Rp; w.V = m->V;
     w.farnn = g.farnn; w.nl = m->nl; w.semiring = m->semiring; w.sig_k = m->sig_k;
     float *tmp = nullptr;
-    if ((rc = upload_padded(m, &tmp, Vgen, m->V, m->R, m->V, m->Rp, odV))) return rc; w.Vgen = tmp;
+    if (m->V > 0) { if ((rc = upload_padded(m, &tmp, Vgen, m->V, m->R, m->V, m->Rp, odV))) return rc; w.Vgen = tmp; }   // (V = 0: a vector-input handle)
     if ((rc = upload_padded(m, &tmp, S1, m->S, m->R, m->S, m->Rp, odS))) return rc; w.S1 = tmp;
     if ((rc = upload_padded(m, &tmp, S2, m->S, m->R, m->S, m->Rp, odS))) return rc; w.S2 = tmp;
     if ((rc = upload_transposed(m, &tmp, S1, m->S, m->R, m->SP, odS))) return rc; w.S1T = tmp;
@@ -662,12 +664,16 @@ static int decomp_geometry(farnn_model *m, const Desc *d) {
 
 // ---- create: decomposed i-FST ------------------------------------------------------------------
 // od_vgen / od_s12: Vgen resp. S1, S2 are device pointers whatever d->weights_on_device says (the folded creator)
-static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, farnn_model **out, int od_vgen, int od_s12) {
+// sf: the vector-input handle (farnn_decomp_sf_create): V = 0 and no Vgen, nothing per word is ever built
+static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, farnn_model **out, int od_vgen, int od_s12, bool sf = false) {
     int rc = begin_create(d != nullptr, out);
     if (rc) return rc;
-    if (d->V <= 0 || d->S <= 0 || d->R <= 0 || d->K <= 0 || !d->Vgen || !d->S1 || !d->S2 || !d->W ||
+    if (sf && (d->V != 0 || d->Vgen)) return fail(FARNN_EINVAL, "decomp_sf: V must be 0 and Vgen NULL (the vectors come with every call)%s%s");
+    if ((!sf && (d->V <= 0 || !d->Vgen)) || d->S <= 0 || d->R <= 0 || d->K <= 0 || !d->S1 || !d->S2 || !d->W ||
         !d->Cout || !d->h0 || !d->hT)
         return fail(FARNN_EINVAL, "decomp_ifst: sizes must be positive and factor pointers non-null%s%s");
+    if (sf && d->semiring != FARNN_SEMIRING_SUM)
+        return fail(FARNN_EINVAL, "decomp_sf: the max semiring needs an S x S block per token; vector input exists in the sum semiring only%s%s");
     const GateSrc gates{d->farnn, d->Wss1, d->Wrs1, d->bs1, d->Wss2, d->Wrs2, d->bs2};
     if ((rc = check_gates(gates, "decomp_ifst"))) return rc;
     if (d->nl < 0 || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "decomp_ifst: bad nl%s%s");
@@ -683,13 +689,22 @@ static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, 
     if ((rc = upload_start_final(m, d->h0, d->hT, od))) return rc;
     if ((rc = upload_decode_tables(m, d->P, d->crf_trans, od))) return rc;
     if ((rc = build_rows_pack(m))) return rc;
-    if ((rc = build_dense_blocks(m))) return rc;
+    if (sf) {
+        // decomp_chain_kernel (the fallback behind the packed rows) reads rows at stride Rp and computes its gates itself: it is not
+        // served from the token table, its shapes are refused (include/farnn.h)
+        if (!m->rows.ok) return fail(FARNN_ERANGE, "decomp_sf: a per-token row of more than %s floats (Rp + SP per gate) is not supported%s", "2048", "");
+        m->sf = true;
+    } else if ((rc = build_dense_blocks(m))) return rc;
     *out = own.release();
     return FARNN_OK;
 }
 
 extern "C" int farnn_decomp_ifst_create(const farnn_decomp_ifst_desc *d, int device, farnn_model **out) {
     return decomp_ifst_create_impl(d, device, out, 0, 0);
+}
+
+extern "C" int farnn_decomp_sf_create(const farnn_decomp_ifst_desc *d, int device, farnn_model **out) {
+    return decomp_ifst_create_impl(d, device, out, 0, 0, true);
 }
 
 // largest eigenvalue of a symmetric positive semi-definite n x n matrix (a Gram matrix; doubles; n <= a few hundred: create time).

@@ -12,19 +12,20 @@
 #include "layout.hip.h"
 #include "decomp_chain.hip.h"
 #include "decomp_rows.hip.h"
+#include "decomp_vec.hip.h"
 #include "chain_regs_params.hip.h"
 #include "tag_plan.hip.h"
 
 using namespace farnn;
 
 enum { KIND_IFST = 2, KIND_IND1 = 1, KIND_FST4 = 0, KIND_DECOMP = 12, KIND_DECOMP1 = 11, KIND_DECOMP0 = 10 };
-enum { KERN_CHAIN = 0, KERN_SCORE = 1, KERN_PREP = 2, KERN_COUNT = 3 };
+enum { KERN_CHAIN = 0, KERN_SCORE = 1, KERN_PREP = 2, KERN_TABLE = 3 /* token_table_kernel (farnn_tag_vectors) */, KERN_COUNT = 4 };
 
 struct Prof {
     std::vector<hipEvent_t> ev[KERN_COUNT];   // (start, stop) pairs
     std::vector<hipEvent_t> pool;             // events created ahead of the timed region (farnn_set_profiling)
-    double ms[KERN_COUNT] = {0, 0, 0};
-    long long n[KERN_COUNT] = {0, 0, 0};
+    double ms[KERN_COUNT] = {};
+    long long n[KERN_COUNT] = {};
     hipEvent_t get() {
         hipEvent_t e = nullptr;
         if (!pool.empty()) { e = pool.back(); pool.pop_back(); return e; }
@@ -41,9 +42,11 @@ struct Workspace {
     size_t hs_bytes = 0;
     float *crf_scores = nullptr;
     float *d1_br = nullptr;                 // [B*L][MT][NT*16] per-row-tile partial output-rank vectors (decomposed independent=1)
+    float *tt = nullptr;                    // [B*L][tvl] the call's token table (a vector-input handle: decomp_vec.hip.h)
+    int64_t *ids = nullptr;                 // [B*L] ids[i] = i: the identity ids its recurrence runs on
     int B = 0, L = 0;                       // CAPACITY: sequences, positions
     void release() {
-        for (void *p : {(void *)A, (void *)Bk, (void *)offs, (void *)order, (void *)hs, (void *)crf_scores, (void *)d1_br})
+        for (void *p : {(void *)A, (void *)Bk, (void *)offs, (void *)order, (void *)hs, (void *)crf_scores, (void *)d1_br, (void *)tt, (void *)ids})
             if (p) (void)hipFree(p);
         *this = Workspace();
     }
@@ -91,6 +94,7 @@ struct farnn_model {
     bool last_lm_score = false;
     int chain_ks = 3;
     bool dense_decomp = false;              // decomposed model served by dense per-word blocks + chain_kernel
+    bool sf = false;                        // vector input (farnn_decomp_sf_create): no word table, V = 0; farnn_tag_vectors builds a token table per call
     int profiling = 0;          // 0 off, N>0: time every N-th farnn_tag call
     long long calls = 0;
     int prof_this_call = 0;

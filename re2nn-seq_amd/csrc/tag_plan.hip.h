@@ -1,4 +1,4 @@
-// The plan of ONE farnn_tag call: everything that is decided about it -- which launches serve it and in which form -- as plain
+// The plan of ONE farnn_tag / farnn_tag_vectors call: everything that is decided about it -- which launches serve it and in which form -- as plain
 // host state.  plan_tag (farnn_hip.hip) fills it from the model, (B, L), the mode and the outputs asked for, before anything is
 // enqueued; the launch_* helpers there read it and decide nothing; the handle keeps the last call's plan, and farnn_kernel_name /
 // farnn_kernel_algorithmic_bytes report from it.
@@ -42,6 +42,10 @@ struct TagPlan {
     bool sort_in_kernel = false;            // ... and select their sequence by length rank
     bool order_valid = false;               // the recurrence reads the launch order the prep launch wrote
     int prep = PREP_NONE, prep_G = 1;       // PREP_SMALL: lanes per sequence
+    // ---- the token table of a vector-input call (farnn_tag_vectors): token_table_kernel in front of the recurrence, which then
+    // runs on the identity ids with V = B L
+    bool table = false;
+    int table_cols = 0;                     // its gate columns: 0 (farnn = 0: the padded copy alone), SP or 2 SP
     // ---- recurrence
     int rec = REC_CHAIN_KERNEL;
     bool fused = false;                     // scores + decode beside the recurrence: the call's ONE launch

@@ -259,3 +259,160 @@ class FARNN_S_D_W_I_S(Trainable, NativeTagger):
                                                  crf_trans=tp.get('crf.transitions'),
                                                  gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]), valid_tokens=ntok,
                                                  teacher=None if re_tags is None else self._teacher(re_tags, x.shape[1]))
+
+
+_SF_PARAM_KEYS = ('S1', 'S2', 'C_output_mat', 'wildcard_mat', 'wildcard_output_vector', 'h0', 'hT') + _GATE_KEYS
+
+
+class FARNN_S_SF(NativeTagger):
+    """Host mirror of the reference's vector-input i-FST tagger ``FARNN_S_SF`` (model_decompose_single.py:307-579): the
+    recurrence of FARNN_S_D_W_I_S on a dense input [B, L, R], one rule-space vector per token, in place of word ids and a word
+    table.  Inference runs in the HIP library (farnn_decomp_sf_create / farnn_tag_vectors); training needs d loss / d input for
+    whatever produced the vectors and is not built."""
+    _param_keys = _SF_PARAM_KEYS
+    pad_additional_states = FARNN_S_D_W_I_S.pad_additional_states
+    get_random = FARNN_S_D_W_I_S.get_random
+
+    def state_dict(self):
+        sd = {k: getattr(self, k) for k in self._param_keys if hasattr(self, k)}
+        sd['priority_layer.priority_mat'] = torch.from_numpy(self.priority_full)
+        if self.use_crf:
+            sd['crf.transitions'] = self.crf_transitions
+        return sd
+
+    def load_state_dict(self, sd, strict=False):
+        for k, v in sd.items():
+            v = torch.as_tensor(np.asarray(v)).float() if not torch.is_tensor(v) else v.detach().float().cpu()
+            if k in self._param_keys:
+                setattr(self, k, v)
+            elif k == 'priority_layer.priority_mat':
+                self.priority_full = v.numpy()
+            elif k == 'crf.transitions':
+                self.crf_transitions = v
+        self.invalidate()
+        return self
+
+    def __init__(self, S1=None, S2=None, C_output_mat=None, wildcard_mat=None, wildcard_output_vector=None,
+                 final_vector=None, start_vector=None, priority_mat=None, args=None, o_idx=0, is_cuda=True):
+        super().__init__(args, o_idx)
+        a = args
+        if a.train_mode == 'max':
+            raise NotImplementedError('FARNN_S_SF: --train_mode max needs an S x S block per token; the vector-input tagger exists '
+                                      'in the sum semiring only (DESIGN.md, row f14)')
+        t = lambda x: torch.from_numpy(np.asarray(x)).float()      # noqa: E731
+        self.additional_states = int(a.additional_states)
+        self.C = C_output_mat.shape[0]
+        self.S, self.R = S1.shape
+        self.use_crf = bool(a.use_crf)
+        self.crf_transitions = None
+        if self.use_crf:
+            self.crf_transitions = crf_default_transitions(self.C)
+            self.C += 2
+        self.priority_full = expand_priority(self.C, priority_mat)
+        self.random = bool(a.random)
+        self.h0 = self.pad_additional_states(t(start_vector))
+        self.hT = self.pad_additional_states(t(final_vector))
+        # init_forward_parameters (ref :355-415)
+        self.S1 = self.pad_additional_states(t(S1))
+        self.S2 = self.pad_additional_states(t(S2))
+        C_o = np.asarray(C_output_mat)
+        if a.use_crf == 1:
+            C_o = np.concatenate((C_o, self.get_random((2, self.S)).numpy() * a.rand_constant), axis=0)
+        self.C_output_mat = self.pad_additional_states(t(C_o))
+        self.wildcard_mat = self.pad_additional_states(t(wildcard_mat))
+        self.wildcard_output_vector = self.pad_additional_states(t(wildcard_output_vector))
+        Sp = self.S + self.additional_states
+        if a.farnn in (1, 2):
+            self.Wss1 = torch.randn((Sp, Sp)).float()
+            self.Wrs1 = torch.randn((self.R, Sp)).float()
+            self.bs1 = torch.ones((1, Sp)).float() * a.bias_init
+            if a.farnn == 2:
+                self.Wss2 = torch.randn((Sp, Sp)).float()
+                self.Wrs2 = torch.randn((self.R, Sp)).float()
+                self.bs2 = torch.ones((1, Sp)).float() * a.bias_init
+            if a.xavier:
+                for name in _GATE_KEYS:
+                    if hasattr(self, name) and not name.startswith('bs'):
+                        torch.nn.init.xavier_normal_(getattr(self, name))
+                if a.farnn == 1:
+                    torch.nn.init.xavier_normal_(self.bs1)
+        if self.random:
+            for name in ('S1', 'S2', 'C_output_mat', 'wildcard_mat'):
+                torch.nn.init.xavier_normal_(getattr(self, name))
+            torch.nn.init.normal_(self.h0)
+            torch.nn.init.normal_(self.hT)
+
+    def _build_handle(self):
+        a = self.args
+        if a.local_loss_func != 'CE1':
+            raise NotImplementedError('only CE1 is reachable from main.py (:127)')
+        gates = {k: (getattr(self, k).reshape(-1) if k.startswith('bs') else getattr(self, k)).numpy()
+                 for k in _GATE_KEYS if hasattr(self, k)}
+        return _lib.create_decomp_sf(
+            self.S1.numpy(), self.S2.numpy(), self.wildcard_mat.numpy(), self.C_output_mat.numpy(), self.h0.numpy(),
+            self.hT.numpy(), P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
+            sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear, semiring='sum', threshold=a.threshold,
+            o_idx=self.o_idx, use_crf=self.use_crf,
+            crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(), device=self.device_index)
+
+    def run_vectors(self, input, lengths, want_tags=False, want_flat=False, want_scores=False):
+        """One farnn_tag_vectors() call on input[:, :lengths.max()] (ref :497: L = lengths.max()).  A view that is not
+        contiguous, not float32 or not on the device is copied on the host side, like the id mirrors' inputs."""
+        dev = self._dev()
+        h = self.handle
+        L = int(lengths.max().item())
+        v = input[:, :L].to(device=dev, dtype=torch.float32).contiguous()
+        ln = lengths.to(device=dev, dtype=torch.int64).contiguous()
+        B, _, R = v.shape
+        if R != self.R:
+            raise ValueError('FARNN_S_SF: input vectors have {} entries, the automaton\'s rank is {}'.format(R, self.R))
+        tags = torch.empty((B, L), dtype=torch.int32, device=dev) if want_tags else None
+        flat = torch.empty((int(ln.clamp(0, L).sum().item()),), dtype=torch.int64, device=dev) if want_flat else None
+        scores = torch.empty((B, L, h.num_columns()), dtype=torch.float32, device=dev) if want_scores else None
+        with torch.cuda.device(dev):
+            h.tag_vectors(v.data_ptr(), ln.data_ptr(), B, L, _lib.MODE_LOCAL,
+                          None if tags is None else tags.data_ptr(), None if flat is None else flat.data_ptr(),
+                          None if scores is None else scores.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return {'tags': tags, 'flat': flat, 'scores': scores, '_keep': (v, ln)}
+
+    def forward(self, input, label, lengths, train=False, re_tags=None):
+        """(None, flat_pred, flat_true) of ref :483-579 with train=False."""
+        if train:
+            raise NotImplementedError('FARNN_S_SF: training needs d loss / d input for the encoder in front of it and is not '
+                                      'built (DESIGN.md, row f14); call forward(..., train=False)')
+        r = self.run_vectors(input, lengths, want_flat=True)
+        return None, r['flat'].to(label.device), self._flatten(label, lengths)
+
+    __call__ = forward
+    forward_local = forward
+
+    def forward_score(self, *a, **k):
+        raise NotImplementedError('forward_score exists only on the onehot models (ref model_onehot.py:351)')
+
+    def forward_RE(self, *a, **k):
+        raise NotImplementedError('forward_RE exists only on the onehot models (ref model_onehot.py:148)')
+
+    def submit_local(self, *a, **k):
+        raise NotImplementedError('FARNN_S_SF takes vectors: the host-buffer path (word ids) does not apply')
+
+
+class FARNN_S_bert:
+    """``FARNN_S_bert`` of the reference (model_decompose_single_with_bert.py): EmbedAggregator in front of FARNN_S_SF.  The
+    reference builds a BertModel inside; here ``encoder`` is ANY callable (bert_input, bert_attend_mask, bert_valid_mask,
+    lengths) -> [B, L, D] contextual token vectors, D = static_embed.shape[1]."""
+
+    def __init__(self, V=None, S1=None, S2=None, C_output_mat=None, wildcard_mat=None, wildcard_output_vector=None,
+                 final_vector=None, start_vector=None, static_embed=None, priority_mat=None, args=None, o_idx=0,
+                 is_cuda=True, encoder=None):
+        from .embed_aggregator import EmbedAggregator
+        self.embed = EmbedAggregator(args, V, static_embed, encoder=encoder)
+        self.slot_filler = FARNN_S_SF(S1=S1, S2=S2, C_output_mat=C_output_mat, wildcard_mat=wildcard_mat,
+                                      wildcard_output_vector=wildcard_output_vector, final_vector=final_vector,
+                                      start_vector=start_vector, priority_mat=priority_mat, args=args, o_idx=o_idx,
+                                      is_cuda=is_cuda)
+
+    def forward(self, input, bert_input, bert_attend_mask, bert_valid_mask, lengths, label, train=False, re_tags=None):
+        vecs = self.embed.forward_bert(input, bert_input, bert_attend_mask, bert_valid_mask, lengths)
+        return self.slot_filler(vecs, label, lengths, train=train, re_tags=re_tags)
+
+    __call__ = forward

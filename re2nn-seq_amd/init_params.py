@@ -78,7 +78,9 @@ def get_init_params_seq_independent_single(args, s2i, t2i, data_dir='../data/'):
         assert args.use_priority == 0
 
     if bool(getattr(args, 'use_bert', 0)):
-        raise NotImplementedError('the BERT front-end is outside the forward tagging path (SURVEY.md 2, row 23)')
+        raise NotImplementedError('--use_bert 1 needs the transformers package and BERT weights, which this project does not ship; the tagger behind the '
+                                  'encoder is built: compose your own encoder with farnn.model_decompose_single.FARNN_S_bert(encoder=...) '
+                                  '(DESIGN.md, row f14)')
     return (V_embed_extend, S1, S2, pretrain_embed_extend, wildcard_mat, wildcard_output_vector,
             final_vector, start_vector, priority_mat, C_output_mat, None)
 

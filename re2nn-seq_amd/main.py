@@ -195,7 +195,9 @@ def dispatch(args):
         return train_slot_onehot(args, data_dir=args.data_dir, model_dir=args.model_dir)
     if args.method == 'decompose':
         if args.use_bert:
-            raise NotImplementedError('the BERT front-end is out of scope (SURVEY.md 2, row 23)')
+            raise NotImplementedError('--use_bert 1 needs the transformers package and BERT weights, which this project does not ship; the tagger behind the '
+                                      'encoder is built: compose your own encoder with farnn.model_decompose_single.FARNN_S_bert(encoder=...) '
+                                      '(DESIGN.md, row f14)')
         from .train_decompose import train_slot_decompose
         return train_slot_decompose(args, data_dir=args.data_dir, model_dir=args.model_dir)
     raise NotImplementedError('--method baseline (BiRNN / MarryUp baselines) is out of scope '
