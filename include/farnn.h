@@ -470,6 +470,32 @@ int  farnn_decomp_ifst_teacher_max_train_step(farnn_train_ctx *ctx, const farnn_
                                               const int64_t *lengths, const int64_t *labels, const float *re_scores,
                                               const farnn_teacher *teacher, int32_t B, int32_t L, int64_t valid_tokens,
                                               const farnn_train_outputs *out, void *stream);
+/* ---- the same step on a dense input: FARNN_S_SF (reference model_decompose_single.py:483-580 with train=True)
+ * One rule-space vector per token, v [B][L][R], in place of word ids and the table Vgen, and d loss / d v beside the weight
+ * gradients: what an encoder in front of the automaton is trained through.  Scope: the sum semiring, farnn = 0/1/2, every
+ * update_nonlinear, the CE1 loss or (use_crf) the CRF negative log-likelihood, the priority layer P; no KD / PR teacher.  The size
+ * limits are the id step's (S, R <= 512, B (L+1) max(S, R) < 2^30, the CRF's LDS limit, 160 KiB of LDS per launch).
+ *
+ * farnn_decomp_sf_train_create: farnn_train_create for such a context; dims->V must be 0 (anything else: FARNN_EINVAL, as
+ * farnn_train_create refuses V = 0).  Nothing per word is allocated; the workspaces follow the per-call B L.  The context is
+ * destroyed, profiled and timed by farnn_train_destroy / farnn_train_set_profiling / farnn_train_time.
+ *
+ * farnn_decomp_sf_train_step:
+ *   w        the id step's weights with Vgen = NULL;  out: the id step's outputs with dVgen = NULL
+ *   v        float32 [B][L][R] dense (device).  A row at a position t >= lengths[b] reaches no arithmetic that reaches an output:
+ *            it may hold anything, NaN and Inf included.
+ *   dv       float32 [B][L][R] (device), written whole by the step: d loss / d v at the valid positions, exact zeros at the pads.
+ *            No float atomic and a fixed summation order: two calls on the same inputs give the same bits.
+ *   The loss, the tags and the weight gradients are the id step's on a table whose rows are these vectors and the ids b L + t.
+ * FARNN_EINVAL, before anything is enqueued and with the output buffers untouched: a NULL v or dv, a non-NULL w->Vgen or
+ * out->dVgen, a context made by farnn_train_create.  On a vector-input context farnn_decomp_ifst_train_step, both teacher entries
+ * (their KL term reads the scores at the pad positions, that is the pad vectors) and
+ * farnn_train_set_semiring(FARNN_SEMIRING_MAX) (an S x S block per token) return FARNN_EINVAL.
+ * These two entry points were ADDED to ABI version 2: no existing signature or struct changed, so the number stands. */
+int  farnn_decomp_sf_train_create(const farnn_train_dims *dims, int device, farnn_train_ctx **out);
+int  farnn_decomp_sf_train_step(farnn_train_ctx *ctx, const farnn_train_weights *w, const float *v, const int64_t *lengths,
+                                const int64_t *labels, int32_t B, int32_t L, int64_t valid_tokens,
+                                const farnn_train_outputs *out, float *dv, void *stream);
 /* accumulated HIP-event time of the step's launches since the last call (ms) and the number of steps timed;
  * profiling is enabled with farnn_train_set_profiling(ctx, 1) */
 int  farnn_train_set_profiling(farnn_train_ctx *ctx, int32_t enable);

@@ -311,6 +311,9 @@ SIGNATURES = {
     'farnn_decomp_ifst_teacher_max_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p, C.POINTER(Teacher), C.c_int32, C.c_int32,
                                                            C.c_int64, C.POINTER(TrainOutputs), C.c_void_p]),
+    'farnn_decomp_sf_train_create': (C.c_int, [C.POINTER(TrainDims), C.c_int, C.POINTER(C.c_void_p)]),
+    'farnn_decomp_sf_train_step': (C.c_int, [C.c_void_p, C.POINTER(TrainWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int64, C.POINTER(TrainOutputs), C.c_void_p, C.c_void_p]),
     'farnn_train_set_profiling': (C.c_int, [C.c_void_p, C.c_int32]),
     'farnn_train_time': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'farnn_train_set_semiring': (C.c_int, [C.c_void_p, C.c_int32]),
@@ -786,6 +789,25 @@ class TrainContext(_TrainContextBase):
         entry = 'farnn_decomp_ifst_teacher_max_train_step' if max_entry else 'farnn_decomp_ifst_teacher_train_step'
         check(getattr(load(), entry)(self._raw, C.byref(w), x_ptr, len_ptr, labels_ptr, re_ptr, C.byref(t),
                                      int(B), int(L), int(valid_tokens), C.byref(o), stream), entry)
+
+
+class SfTrainContext(TrainContext):
+    """Owns one farnn_train_ctx* made by farnn_decomp_sf_train_create: the training step of the vector-input i-FST (FARNN_S_SF;
+    include/farnn.h).  Sum semiring only, no teacher: set_semiring('max'), step() and teacher_step() are refused
+    by the library on such a context."""
+    _create = 'farnn_decomp_sf_train_create'
+
+    def __init__(self, S, R, K, nl='none', threshold=0.5, o_idx=0, device=0, use_crf=False, farnn=0, sigmoid_exponent=5.0):
+        super().__init__(0, S, R, K, nl=nl, threshold=threshold, o_idx=o_idx, device=device, use_crf=use_crf, farnn=farnn,
+                         sigmoid_exponent=sigmoid_exponent)
+
+    def step_vectors(self, weights, v_ptr, len_ptr, labels_ptr, B, L, valid_tokens, outputs, dv_ptr, stream=None):
+        """farnn_decomp_sf_train_step: v_ptr / dv_ptr are the device pointers of the float [B][L][R] input and its gradient;
+        weights / outputs as step()'s, without Vgen / dVgen."""
+        w = self._weights(**{k: (weights.get(k) or None) for k, _ in self._weights._fields_})
+        o = self._outputs(**{k: outputs.get(k) for k, _ in self._outputs._fields_})
+        check(load().farnn_decomp_sf_train_step(self._raw, C.byref(w), v_ptr, len_ptr, labels_ptr, int(B), int(L),
+                                                int(valid_tokens), C.byref(o), dv_ptr, stream), 'farnn_decomp_sf_train_step')
 
 
 class DecompFstTrainContext(_TrainContextBase):

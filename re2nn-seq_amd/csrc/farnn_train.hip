@@ -1,5 +1,5 @@
-// libfarnn_hip.so -- the six training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the decomposed
-// FST on the same chains (farnn_decomp_fst_train_*), the onehot
+// libfarnn_hip.so -- the training steps: the decomposed i-FST (farnn_train_*; include/farnn.h), the same on a dense
+// input (farnn_decomp_sf_train_*), the decomposed FST on the same chains (farnn_decomp_fst_train_*), the onehot
 // i-FST (farnn_onehot_train_*), the onehot FST (farnn_fst4_train_*), the onehot independent=1 model (farnn_ind1_train_*) and the
 // decomposed independent=1 model (farnn_decomp_ind1_train_*), and the optimizer step that follows any of them (farnn_optim_*, at
 // the end).  Their own translation unit: the training kernels (train.hip.h: the scores and the loss, shared by the first two
@@ -24,6 +24,7 @@
 #include "decomp1_train.hip.h"
 #include "decomp0_train.hip.h"
 #include "decomp0_train_max.hip.h"
+#include "sf_train.hip.h"
 #include "decomp1_gated_train.hip.h"
 #include "decomp1_gated_max_train.hip.h"
 #include "train_bucketed_crf.hip.h"
@@ -46,12 +47,17 @@ struct farnn_train_ctx : TrainCtxBase {     // (err: the kernels set bit 0 on a 
     DevBuf<float> ones;           // 1.0f each: bias gradients as a product with a column of ones
     DevBuf<float> mws;            // max semiring only (train_max.hip.h): M, MT, dM, IN, GM; allocated on first use
     DevBuf<int> miws;             // max semiring only: IDX, the bucketing of the positions, the word slots
+    // a vector-input context (farnn_decomp_sf_train_create, d.V = 0; sf_train.hip.h): nothing per word, and the position ids
+    bool vector_input = false;
+    DevBuf<int64_t> ids;          // [B L] 0, 1, 2, ...: the chains' token ids, written on the device when the buffer grows
 };
 
-extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out) {
+// farnn_train_create (vec = false) and farnn_decomp_sf_train_create (vec = true: no vocabulary)
+static int train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out, bool vec) {
     if (!d || !out) return fail(FARNN_EINVAL, "train_create: null argument%s%s");
     *out = nullptr;
-    if (d->V <= 0 || d->S <= 0 || d->R <= 0 || d->K <= 0) return fail(FARNN_EINVAL, "train_create: bad dimensions%s%s");
+    if ((vec ? d->V != 0 : d->V <= 0) || d->S <= 0 || d->R <= 0 || d->K <= 0)
+        return fail(FARNN_EINVAL, vec ? "decomp_sf_train_create: bad dimensions (a vector-input context has V = 0)%s%s" : "train_create: bad dimensions%s%s");
     if (d->nl < FARNN_NL_NONE || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "train_create: bad nonlinearity%s%s");
     // the CRF loss kernel keeps exp(transitions) in LDS: K = 190 is the hard limit (L = 4); at L = 64 it is K = 140
     // (checked per call, farnn_decomp_ifst_train_step returns FARNN_ERANGE before enqueuing anything)
@@ -62,6 +68,7 @@ extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_t
     if ((rc = train_ctx_create("train", d, device, out))) return rc;
     farnn_train_ctx *c = *out;
     c->n_cu = device_cus(device);
+    c->vector_input = vec;
     const size_t S = d->S, R = d->R, V = d->V;
     const char *oom = "train_create: out of device memory%s%s";
     if ((rc = c->fixed.ensure(2 * S * R + S * S + 2 * S + (d->farnn ? 2 * S * S + 2 * S * R : 0), oom)) ||
@@ -74,6 +81,8 @@ extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_t
     if (d->farnn) { c->Wss1T = c->dOsum + S; c->Wss2T = c->Wss1T + S * S; c->Wrs1T = c->Wss2T + S * S; c->Wrs2T = c->Wrs1T + S * R; }
     return FARNN_OK;
 }
+extern "C" int farnn_train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out) { return train_create(d, device, out, false); }
+extern "C" int farnn_decomp_sf_train_create(const farnn_train_dims *d, int device, farnn_train_ctx **out) { return train_create(d, device, out, true); }
 extern "C" void farnn_train_destroy(farnn_train_ctx *c) { train_ctx_destroy(c); }
 extern "C" int farnn_train_set_profiling(farnn_train_ctx *c, int32_t enable) { return train_ctx_set_profiling("train", c, enable); }
 extern "C" int farnn_train_time(farnn_train_ctx *c, double *total_ms, int64_t *steps) { return train_ctx_time("train", c, total_ms, steps); }
@@ -82,6 +91,8 @@ extern "C" int farnn_train_set_semiring(farnn_train_ctx *c, int32_t semiring) {
     if (!c) return fail(FARNN_EINVAL, "train_set_semiring: null context%s%s");
     if (semiring != FARNN_SEMIRING_SUM && semiring != FARNN_SEMIRING_MAX)
         return fail(FARNN_EINVAL, "train_set_semiring: semiring must be FARNN_SEMIRING_SUM or FARNN_SEMIRING_MAX%s%s");
+    if (semiring == FARNN_SEMIRING_MAX && c->vector_input)
+        return fail(FARNN_EINVAL, "train_set_semiring: a vector-input context exists in the sum semiring only (the max semiring needs an S x S block per token)%s%s");
     if (semiring == FARNN_SEMIRING_MAX && c->d.S > TM_MAX_S)
         return fail(FARNN_ERANGE, "train_set_semiring: the max-semiring step holds at most 192 states%s%s");
     c->semiring = semiring;
@@ -492,6 +503,7 @@ extern "C" int farnn_decomp_ifst_train_step(farnn_train_ctx *c, const farnn_trai
                                             const int64_t *lengths, const int64_t *labels, int32_t B, int32_t L,
                                             int64_t valid_tokens, const farnn_train_outputs *o, void *stream) {
     TunScope tun_scope(c ? &c->tun : nullptr);     // (a null context: run_train_step refuses it)
+    if (c && c->vector_input) return fail(FARNN_EINVAL, "train_step: a vector-input context takes farnn_decomp_sf_train_step%s%s");
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream);
 }
 
@@ -501,6 +513,7 @@ extern "C" int farnn_decomp_ifst_teacher_train_step(farnn_train_ctx *c, const fa
                                                     const farnn_train_outputs *o, void *stream) {
     TunScope tun_scope(c ? &c->tun : nullptr);
     if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_train_step: null teacher argument%s%s");
+    if (c && c->vector_input) return fail(FARNN_EINVAL, "teacher_train_step: a vector-input context has no teacher (the KL term reads the scores at the pad positions)%s%s");
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
                                      [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; });
 }
@@ -513,8 +526,183 @@ extern "C" int farnn_decomp_ifst_teacher_max_train_step(farnn_train_ctx *c, cons
                                                         const farnn_train_outputs *o, void *stream) {
     TunScope tun_scope(c ? &c->tun : nullptr);
     if (!re_scores || !teacher) return fail(FARNN_EINVAL, "teacher_max_train_step: null teacher argument%s%s");
+    if (c && c->vector_input) return fail(FARNN_EINVAL, "teacher_max_train_step: a vector-input context has no teacher (the KL term reads the scores at the pad positions)%s%s");
     return run_train_step<TrainStep>(c, w, x, lengths, labels, B, L, valid_tokens, o, stream,
                                      [&](TrainStep &t) { t.re = re_scores; t.tch = teacher; t.tch_max = true; });
+}
+
+// ---- training step of the vector-input i-FST (FARNN_S_SF; sf_train.hip.h) ---------------------------------
+// The decomposed i-FST's step with v [B][L][R] as the chains' table and the ids b L + t as their tokens (p.V = B L): the plan,
+// the chains, the loss and the job lists' shared part are TrainStep's; what was per word (the gate halves, their adjoints,
+// dWrs, dVgen) is per token here.  Sum semiring, no teacher.
+struct SfStep : TrainStep {
+    static constexpr const char *name = "decomp_sf_train";
+    const float *v; float *dv;
+    SfGateParams gp; SfDvParams dp;
+    size_t need_sf; unsigned tgrid;
+    float *GV1, *GV2, *dG1, *dG2, *VM;       // VM [B L][R]: v at the valid positions, zero at the pads (dWrs is reduced from it)
+
+    int validate() {
+        if (!c->vector_input) return fail(FARNN_EINVAL, "decomp_sf_train_step: the context was made by farnn_train_create (word ids): farnn_decomp_ifst_train_step is its step%s%s");
+        if (w->Vgen || o->dVgen) return fail(FARNN_EINVAL, "decomp_sf_train_step: Vgen and dVgen must be NULL (the input is v, its gradient dv)%s%s");
+        if (!w->S1 || !w->S2 || !w->W || !w->C || !w->h0 || !w->hT) return fail(FARNN_EINVAL, "decomp_sf_train_step: null weight%s%s");
+        if (!o->loss || !o->dS1 || !o->dS2 || !o->dW || !o->dC || !o->dh0 || !o->dhT || !o->tags)
+            return fail(FARNN_EINVAL, "decomp_sf_train_step: null output%s%s");
+        if (c->d.use_crf && (!w->crf_trans || !o->dtrans)) return fail(FARNN_EINVAL, "decomp_sf_train_step: CRF transitions / their gradient missing%s%s");
+        if (c->d.farnn >= 1 && (!w->Wss1 || !w->Wrs1 || !w->bs1 || !o->dWss1 || !o->dWrs1 || !o->dbs1))
+            return fail(FARNN_EINVAL, "decomp_sf_train_step: update-gate weights / gradients missing%s%s");
+        if (c->d.farnn == 2 && (!w->Wss2 || !w->Wrs2 || !w->bs2 || !o->dWss2 || !o->dWrs2 || !o->dbs2))
+            return fail(FARNN_EINVAL, "decomp_sf_train_step: reset-gate weights / gradients missing%s%s");
+        return FARNN_OK;
+    }
+    // the step's own arrays, behind everything the chains lay out (none of them needs the step's memset: every element read is written first)
+    size_t carve_sf(float *base) {
+        Carver<float> a(base);
+        p.DVf = a.take(N1 * R); p.DVb = a.take(N1 * R); p.HP = a.take((size_t)B * 2 * S); p.OP = a.take((size_t)B * 2 * S);
+        if (crf) p.crf_loss_part = a.take((size_t)B); else p.loss_part = a.take((size_t)lgrid * 8);
+        if (farnn) { GV1 = a.take(N0 * S); GV2 = a.take(N0 * S); dG1 = a.take(N0 * S); dG2 = a.take(N0 * S); VM = a.take(N0 * R); }
+        return a.off;
+    }
+    int plan(int B_, int L_) {
+        if (int rc = train_plan(c, B_, L_, false, *this)) return rc;       // (the sum semiring: farnn_train_set_semiring refuses the other)
+        V = N0;                                                            // the "vocabulary" of the chains: one row per position
+        need_sf = carve_sf(nullptr);
+        tgrid = (unsigned)std::min<size_t>(4 * (size_t)c->n_cu, (N0 + SF_TP - 1) / SF_TP);
+        int rc;
+        return (farnn && (rc = lds_fits(sf_gate_lds_bytes(R)))) ? rc : lds_fits(sf_dv_lds_bytes(S, farnn));
+    }
+    int carve(const int64_t *, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens);
+    int prepare(); int sf_loss(); int backward(); int gradients();
+    int stages() {
+        int rc;
+        if ((rc = prepare()) || (rc = forward()) || (rc = sf_loss())) return rc;
+        return (rc = backward()) ? rc : gradients();
+    }
+};
+
+int SfStep::carve(const int64_t *, const int64_t *lengths, const int64_t *labels, int64_t valid_tokens) {
+    int rc;
+    if ((rc = c->ws.ensure(need + need_sf, "decomp_sf_train_step: out of device memory for the workspace%s%s"))) return rc;
+    if (farnn && c->ones.n < N1) {
+        if ((rc = c->ones.ensure(N1, "decomp_sf_train_step: out of device memory for the column of ones%s%s"))) return rc;
+        std::vector<float> hones(N1, 1.0f);
+        FARNN_HIP_TRY(hipMemcpy(c->ones.p, hones.data(), N1 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (c->ids.n < N0) {
+        // growth only (like the column of ones): filled on the device and awaited here, so that a later step on any stream finds them
+        if ((rc = c->ids.ensure(N0, "decomp_sf_train_step: out of device memory for the position ids%s%s"))) return rc;
+        sf_iota_kernel<<<(unsigned)((c->ids.n + 255) / 256), 256, 0, s>>>(c->ids.p, c->ids.n);
+        FARNN_HIP_TRY(hipStreamSynchronize(s));
+    }
+    [[maybe_unused]] const size_t carved = carve_train_ws(c->ws.p, p, *this), carved_sf = carve_sf(c->ws.p + need);
+    assert(carved == need && carved_sf == need_sf);
+    p.Vgen = v; p.S1 = w->S1; p.S2 = w->S2; p.W = w->W; p.C = w->C; p.h0 = w->h0; p.hT = w->hT; p.P = w->P;
+    p.S1T = c->S1T; p.S2T = c->S2T; p.WT = c->WT; p.Osum = c->Osum;
+    p.x = c->ids.p; p.len = lengths; p.labels = labels; p.err = c->err.dev;
+    if (crf) p.trans = w->crf_trans;
+    p.farnn = farnn; p.sig_k = c->d.sigmoid_exponent;
+    if (farnn) {
+        p.Wss1 = w->Wss1; p.Wrs1 = w->Wrs1; p.bs1 = w->bs1; p.Wss2 = w->Wss2; p.Wrs2 = w->Wrs2; p.bs2 = w->bs2;
+        p.Wss1T = c->Wss1T; p.Wss2T = c->Wss2T; p.Wrs1T = c->Wrs1T; p.Wrs2T = c->Wrs2T;
+        p.GV1 = GV1; p.GV2 = GV2;
+    }
+    p.nss_f = nss_f; p.nss_b = nss_b;
+    p.dOsum = c->dOsum; p.dh0 = o->dh0; p.dhT = o->dhT; p.loss = o->loss; p.tags = o->tags;
+    p.B = B; p.L = L; p.V = (int)N0; p.S = (int)S; p.R = (int)R; p.K = (int)K; p.nl = c->d.nl; p.o_idx = c->d.o_idx;
+    p.threshold = c->d.threshold; p.inv_tokens = 1.0f / (float)valid_tokens;
+    gp = {v, lengths, w->Wrs1, w->Wrs2, GV1, GV2, VM, B, L, (int)S, (int)R, farnn};
+    dp = {lengths, p.DVf, p.DVb, p.DAZf, p.DAZb, p.DARf, p.DARb, c->Wrs1T, c->Wrs2T, dv, dG1, dG2, B, L, (int)S, (int)R, farnn};
+    // the preparation jobs: the outputs and accumulators to zero, the transposes, the column sum of C
+    PrepJobs &pj = prep;
+    prep_add(pj, 0, nullptr, o->loss, 1, 1); prep_add(pj, 0, nullptr, o->dS1, S, R);
+    prep_add(pj, 0, nullptr, o->dS2, S, R); prep_add(pj, 0, nullptr, o->dW, S, S); prep_add(pj, 0, nullptr, o->dC, K, S);
+    prep_add(pj, 0, nullptr, o->dh0, 1, S); prep_add(pj, 0, nullptr, o->dhT, 1, S); prep_add(pj, 0, nullptr, c->dOsum, 1, S);
+    prep_add(pj, 1, w->S1, c->S1T, S, R); prep_add(pj, 1, w->S2, c->S2T, S, R); prep_add(pj, 1, w->W, c->WT, S, S);
+    prep_add(pj, 2, w->C, c->Osum, K, S);
+    if (farnn) {
+        prep_add(pj, 0, nullptr, o->dWss1, S, S); prep_add(pj, 0, nullptr, o->dWrs1, R, S); prep_add(pj, 0, nullptr, o->dbs1, 1, S);
+        prep_add(pj, 1, w->Wss1, c->Wss1T, S, S); prep_add(pj, 1, w->Wrs1, c->Wrs1T, R, S);
+        if (farnn == 2) {
+            prep_add(pj, 0, nullptr, o->dWss2, S, S); prep_add(pj, 0, nullptr, o->dWrs2, R, S); prep_add(pj, 0, nullptr, o->dbs2, 1, S);
+            prep_add(pj, 1, w->Wss2, c->Wss2T, S, S); prep_add(pj, 1, w->Wrs2, c->Wrs2T, R, S);
+        }
+    }
+    if (pj.total < 0) return fail(FARNN_ERANGE, "decomp_sf_train_step: too many preparation jobs%s%s");
+    // the parameter gradients: the id step's products over the per-token rows; dWrs = sum over the valid positions of
+    // v_t^T (the position's gate adjoints), from the masked copy of v and sf_dv_kernel's per-position sums (zero rows at the pads)
+    const int iS = (int)S, iR = (int)R, iK = (int)K;
+    const long long n1 = (long long)N1, n0 = (long long)N0;
+    AtbJobs &jobs = grad_jobs;
+    jobs.chunk = 128;
+    atb_add(jobs, p.Zf, p.Tf, o->dS2, n1, iS, iR);
+    if (!farnn) {
+        atb_add(jobs, p.A, p.D1f + R, o->dS1, n1 - 1, iS, iR);
+        atb_add(jobs, p.A, p.Zf + S, o->dW, n1 - 1, iS, iS);
+    } else {
+        atb_add(jobs, p.HBARf, p.D1f, o->dS1, n1, iS, iR);
+        atb_add(jobs, p.HBARf, p.Zf, o->dW, n1, iS, iS);
+    }
+    atb_add(jobs, p.Zb, p.Tb, o->dS1, n1, iS, iR);
+    atb_add(jobs, p.BBAR, p.D1b, o->dS2, n1, iS, iR);
+    atb_add(jobs, p.Zb, p.BBAR, o->dW, n1, iS, iS);
+    atb_add(jobs, p.DS, p.AB, o->dC, n0, iK, iS);
+    if (farnn) {
+        atb_add(jobs, p.A, p.DAZf + S, o->dWss1, n1 - 1, iS, iS);
+        atb_add(jobs, p.Bk, p.DAZb + S, o->dWss1, n1 - 1, iS, iS);
+        atb_add(jobs, VM, dG1, o->dWrs1, n0, iR, iS);
+        atb_add(jobs, c->ones.p, p.DAZf, o->dbs1, n1, 1, iS);
+        atb_add(jobs, c->ones.p, p.DAZb, o->dbs1, n1, 1, iS);
+        if (farnn == 2) {
+            atb_add(jobs, p.A, p.DARf + S, o->dWss2, n1 - 1, iS, iS);
+            atb_add(jobs, p.Bk, p.DARb + S, o->dWss2, n1 - 1, iS, iS);
+            atb_add(jobs, VM, dG2, o->dWrs2, n0, iR, iS);
+            atb_add(jobs, c->ones.p, p.DARf, o->dbs2, n1, 1, iS);
+            atb_add(jobs, c->ones.p, p.DARb, o->dbs2, n1, 1, iS);
+        }
+    }
+    if (jobs.total_wgs < 0) return fail(FARNN_ERANGE, "decomp_sf_train_step: too many gradient products for one launch%s%s");
+    if ((rc = c->part.ensure(atb_partial_floats(jobs), "decomp_sf_train_step: out of device memory for the partial products%s%s"))) return rc;
+    jobs.partial = c->part.p;
+    return FARNN_OK;
+}
+// Stage 4: zero the chains' workspace, the outputs and the accumulators, transpose the weights; the gates' input halves of the
+// valid positions
+int SfStep::prepare() {
+    FARNN_HIP_TRY(hipMemsetAsync(c->ws.p, 0, need * sizeof(float), s));
+    train_prep_kernel<<<(prep.total + 255) / 256, 256, 0, s>>>(prep);
+    return farnn ? launch(sf_gate_kernel, tgrid, SF_THREADS, sf_gate_lds_bytes(R), s, gp) : FARNN_OK;
+}
+// Stage 6: TrainStep's, with the loss summed from partials in index order (per wavefront of the loss kernel, or per sequence
+// of the CRF kernel) in place of the float atomics
+int SfStep::sf_loss() {
+    if (int rc = loss()) return rc;
+    if (crf) onehot_loss_sum_kernel<<<1, 64, 0, s>>>(p.crf_loss_part, B, o->loss);
+    else launch_loss_sum(p.loss_part, lgrid, o->loss, s);
+    return FARNN_OK;
+}
+// Stage 7: back-propagation through time: d v_t and the gates' input adjoints stay in their per-step rows (the DET form)
+int SfStep::backward() {
+    return with_chain_form(*this, ldsw_b, ns_b, [&](auto LDSW, auto GATED, auto VPS, auto VPR, auto NS) {
+        return launch(train_backward_kernel<LDSW(), GATED(), VPS(), VPR(), NS(), true, true>, dim3((B + NS() - 1) / NS(), 2), TR_THREADS, lds_b, s, p);
+    });
+}
+// Stage 8: dv assembled per position, then the parameter gradients as products over the per-token rows
+int SfStep::gradients() {
+    if (int rc = launch(sf_dv_kernel, tgrid, SF_THREADS, sf_dv_lds_bytes(S, farnn), s, dp)) return rc;
+    sf_seq_sum_kernel<<<(unsigned)((3 * S + 255) / 256), 256, 0, s>>>(p.HP, p.OP, o->dh0, o->dhT, c->dOsum, B, (int)S);
+    atb_launch(grad_jobs, s);
+    add_row_to_all_kernel<<<(unsigned)((K * S + 255) / 256), 256, 0, s>>>(o->dC, c->dOsum, (int)K, (int)S);
+    return FARNN_OK;
+}
+
+extern "C" int farnn_decomp_sf_train_step(farnn_train_ctx *c, const farnn_train_weights *w, const float *v, const int64_t *lengths,
+                                          const int64_t *labels, int32_t B, int32_t L, int64_t valid_tokens,
+                                          const farnn_train_outputs *o, float *dv, void *stream) {
+    TunScope tun_scope(c ? &c->tun : nullptr);
+    if (!v || !dv) return fail(FARNN_EINVAL, "decomp_sf_train_step: null v or dv%s%s");
+    // (the chains' token ids are the context's own: the driver's x argument only has to be non-null)
+    return run_train_step<SfStep>(c, w, lengths, lengths, labels, B, L, valid_tokens, o, stream,
+                                  [&](SfStep &t) { t.v = v; t.dv = dv; });
 }
 
 // ---- training step of the decomposed FST (FARNN_S_D_W; decomp0_train.hip.h) ------------------------------

@@ -64,6 +64,9 @@ struct TrainParams {
     // train_backward_kernel's DET form (decomp0_train.hip.h; NULL in every other step): what the plain form adds with atomics is stored
     float *DVf, *DVb;         // [B][L+1][R] d v_t of every step, beside D1f / D1b
     float *HP;                // [B][2][S] the sequence's share of dh0, dhT
+    // the vector-input step (sf_train.hip.h; NULL in every other step): no float atomic adds more than two values
+    float *OP;                // [B][2][S] the sequence's and direction's share of dOsum (train_backward_kernel's SEQ_ROWS form)
+    float *crf_loss_part;     // [B] the sequence's CRF loss, in place of the atomic on `loss`
 };
 
 __device__ __forceinline__ float nl_grad_from_output(float y, int nl) {
@@ -590,6 +593,7 @@ train_crf_kernel(const TrainParams p) {
     if (n == 0) {
         if constexpr (!BIG)
             for (int e = tid; e < K * K; e += nt) dpart[e] = 0.0f;
+        if (p.crf_loss_part && tid == 0) p.crf_loss_part[b] = 0.0f;
         return;
     }
     const float *F;
@@ -696,7 +700,8 @@ train_crf_kernel(const TrainParams p) {
         gold += tr[prev * TS + STOP];
         ex[prev * TS + STOP] -= 1.0f;
         red[0] = logZ;
-        atomicAdd(p.loss, logZ - gold);
+        if (p.crf_loss_part) p.crf_loss_part[b] = logZ - gold;
+        else atomicAdd(p.loss, logZ - gold);
         float bv = -INFINITY; int ptr = 0;
         for (int i = 0; i < K; i++) { const float c = vp[i] + tr[i * TS + STOP]; if (c > bv) { bv = c; ptr = i; } }
         for (int t = n - 1; t >= 0; t--) {
@@ -831,8 +836,9 @@ __global__ void crf_reduce_kernel(const float *__restrict__ part, float *dtrans,
 // LDS: [Ma | Mb | Mc | Md] z fp [2][mv_pad(S)], d1 [2][mv_pad(R)], pa pb [8][2][max(S,R)], pc [8][2][S], toks [2][L]
 // DET (the decomposed FST's step): no float atomics -- d v_t goes to its row of DVf / DVb, the gates' input adjoints stay in
 // their rows DAZ / DAR, the sequence's dh0 / dhT go to HP, and dOsum (a mask of ones there) is dropped; the caller sums them in a
-// fixed order.  The plain form is what it was.
-template <bool LDSW, bool GATED, int VPS, int VPR, int NS, bool DET = false>
+// fixed order.  The plain form is what it was.  SEQ_ROWS (the vector-input step, sf_train.hip.h, whose Osum is C's column sum): the
+// DET form, and the sequence's share of dOsum stored in OP beside HP.
+template <bool LDSW, bool GATED, int VPS, int VPR, int NS, bool DET = false, bool SEQ_ROWS = false>
 __global__ void __launch_bounds__(TR_THREADS)
 train_backward_kernel(const TrainParams p) {
     constexpr int VPT = VPS > VPR ? VPS : VPR;       // slots per thread: VPS cover 2 S states, VPR cover 2 R ranks
@@ -1057,7 +1063,10 @@ train_backward_kernel(const TrainParams p) {
     for (int k = 0; k < VPT; k++) {
         if (sv[k]) {
             const float g0 = gacc[k] + G_base[srow[k]] + dhin[k];
-            if constexpr (DET) p.HP[((size_t)(b0 + sq[k]) * 2 + dir) * S + ss[k]] = g0;
+            if constexpr (DET) {
+                p.HP[((size_t)(b0 + sq[k]) * 2 + dir) * S + ss[k]] = g0;
+                if constexpr (SEQ_ROWS) p.OP[((size_t)(b0 + sq[k]) * 2 + dir) * S + ss[k]] = dOacc[k];
+            }
             else {
                 if (g0 != 0.0f) atomicAdd((dir == 0 ? p.dh0 : p.dhT) + ss[k], g0);
                 if (dOacc[k] != 0.0f) atomicAdd(p.dOsum + ss[k], dOacc[k]);

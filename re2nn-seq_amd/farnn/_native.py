@@ -37,6 +37,7 @@ def default_device():
 #                             FST, the onehot and the decomposed independent=1 model), beside each model's own f7 - f9
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3
 #   DECOMP_TEACHER_MAX_TRAIN  those terms under --train_mode max, beside DECOMP_TEACHER_TRAIN                 f3
+#   SF_TRAIN                  the vector-input tagger's training step (FARNN_S_SF, FARNN_S_bert; sum semiring)  f14
 #   NATIVE_OPTIM              the library's one-launch Adam / SGD in train_onehot.train_epochs                f6
 #   DEVICE_METRICS            an epoch's loss and TRAIN metrics counted on the device and read once, in
 #                             train_onehot.train_epochs (metrics/device.py; evaluation stays on the host path) f10

@@ -30,6 +30,27 @@ class EmbedAggregator:
             setattr(self, k, getattr(self, k).to(device))
         return self
 
+    # ---- training: the leaves behind FARNN_S_SF's d loss / d input ----------------------------------------
+    _TRAIN_FLAGS = {'V_embed': 'train_V_embed', 'embed_r_generalized': None, 'beta_vec': 'train_beta'}     # ref :50, :66, :69-71
+
+    def requires_grad_(self, mode=True):
+        """Make V_embed, embed_r_generalized and beta_vec autograd leaves with the reference's requires_grad flags (mode=False:
+        none of them).  Call it after to(device): the leaves are the tensors where they then live."""
+        for k, flag in self._TRAIN_FLAGS.items():
+            want = bool(mode) and (flag is None or bool(getattr(self.args, flag, 0)))
+            setattr(self, k, getattr(self, k).detach().requires_grad_(want))
+        return self
+
+    def named_parameters(self):
+        named = [(k, getattr(self, k)) for k in self._TRAIN_FLAGS if getattr(self, k).requires_grad]
+        if isinstance(self.encoder, torch.nn.Module):
+            named += [('encoder.' + k, t) for k, t in self.encoder.named_parameters() if t.requires_grad]
+        return iter(named)
+
+    def parameters(self):
+        """The trainable leaves (after requires_grad_()) and, where the encoder is a torch.nn.Module, its parameters."""
+        return iter([t for _, t in self.named_parameters()])
+
     def get_generalized_v_embed_vec(self, v_batch_vec, emb_batch_vec):
         """ref :77-93"""
         gen = torch.einsum('bld,dr->blr', emb_batch_vec.float(), self.embed_r_generalized)

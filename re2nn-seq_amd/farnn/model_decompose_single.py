@@ -264,12 +264,53 @@ class FARNN_S_D_W_I_S(Trainable, NativeTagger):
 _SF_PARAM_KEYS = ('S1', 'S2', 'C_output_mat', 'wildcard_mat', 'wildcard_output_vector', 'h0', 'hT') + _GATE_KEYS
 
 
-class FARNN_S_SF(NativeTagger):
+class FARNN_S_SF(Trainable, NativeTagger):
     """Host mirror of the reference's vector-input i-FST tagger ``FARNN_S_SF`` (model_decompose_single.py:307-579): the
     recurrence of FARNN_S_D_W_I_S on a dense input [B, L, R], one rule-space vector per token, in place of word ids and a word
-    table.  Inference runs in the HIP library (farnn_decomp_sf_create / farnn_tag_vectors); training needs d loss / d input for
-    whatever produced the vectors and is not built."""
+    table.  Inference runs in the HIP library (farnn_decomp_sf_create / farnn_tag_vectors).  Training is
+    one library call as well (farnn_decomp_sf_train_step): forward(..., train=True) returns a loss that autograd connects to
+    the trainable weights AND to ``input``, so that whatever produced the vectors (an encoder, EmbedAggregator's bridge matrix)
+    is fine-tuned through the automaton.  Scope: the sum semiring, farnn 0 / 1 / 2, CE1 or the CRF, the priority layer; no KD /
+    PR teacher.  Opt-in for its first release: RE2NN_SF_TRAIN=1."""
     _param_keys = _SF_PARAM_KEYS
+    # which tensors get a gradient: the reference's requires_grad flags (ref :343-346, :357-401)
+    _TRAIN_FLAGS = {'S1': None, 'S2': None, 'C_output_mat': 'train_c_output', 'wildcard_mat': 'train_wildcard',
+                    'h0': 'train_h0', 'hT': 'train_hT'}
+
+    def _train_decl(self):
+        """_TRAIN_FLAGS, then the gates of --farnn 1 / 2 and the CRF's transitions, always trainable (as FARNN_S_D_W_I_S's)."""
+        extra = _GATE_KEYS[:3 * int(self.args.farnn)] + (('crf.transitions',) if self.use_crf else ())
+        return Trainable._train_decl(self) + [(k, True) for k in extra]
+
+    def _check_trainable(self):
+        a = self.args
+        if a.farnn not in (0, 1, 2) or a.train_mode != 'sum' or a.local_loss_func != 'CE1':
+            raise NotImplementedError('FARNN_S_SF: the HIP training step covers the sum semiring and the CE1 loss (with or without '
+                                      'the CRF) (DESIGN.md, row f14)')
+
+    def _check_step(self, re_tags):
+        if re_tags is not None or getattr(self.args, 'marryup_type', 'none') in ('kd', 'pr'):
+            raise NotImplementedError('FARNN_S_SF: the KD / PR teacher terms (re_tags, --marryup_type kd | pr) are not built: their KL '
+                                      'term reads the scores at the pad positions, that is the pad vectors (DESIGN.md, row f14)')
+
+    def _train_context(self):
+        tp, a = self._tp, self.args
+        S, R = tp['S1'].shape
+        return _lib.SfTrainContext(S, R, tp['C_output_mat'].shape[0], nl=a.update_nonlinear, threshold=a.threshold,
+                                   o_idx=self.o_idx, device=self.device_index, use_crf=self.use_crf, farnn=int(a.farnn),
+                                   sigmoid_exponent=float(a.sigmoid_exponent))
+
+    def _copy_back(self, tp):
+        for k, t in tp.items():
+            setattr(self, {'crf.transitions': 'crf_transitions'}.get(k, k), t.detach().cpu())
+
+    def _train_call(self, v, lengths, lab, ntok, re_tags):
+        tp = self._tp
+        if v.shape[2] != self.R:
+            raise ValueError('FARNN_S_SF: input vectors have {} entries, the automaton\'s rank is {}'.format(v.shape[2], self.R))
+        return train_step.decomp_sf_train_step(self._tc, v, tp['S1'], tp['S2'], tp['wildcard_mat'], tp['C_output_mat'], tp['h0'],
+                                               tp['hT'], self._tpP, lengths, lab, crf_trans=tp.get('crf.transitions'),
+                                               gates=tuple(tp[k] for k in _GATE_KEYS[:3 * int(self.args.farnn)]), valid_tokens=ntok)
     pad_additional_states = FARNN_S_D_W_I_S.pad_additional_states
     get_random = FARNN_S_D_W_I_S.get_random
 
@@ -376,10 +417,15 @@ class FARNN_S_SF(NativeTagger):
         return {'tags': tags, 'flat': flat, 'scores': scores, '_keep': (v, ln)}
 
     def forward(self, input, label, lengths, train=False, re_tags=None):
-        """(None, flat_pred, flat_true) of ref :483-579 with train=False."""
+        """(loss, flat_pred, flat_true) of ref :483-579; the loss is None with train=False.  train=True (under RE2NN_SF_TRAIN=1):
+        the loss carries a gradient towards ``input`` and the trainable weights (parameters())."""
         if train:
-            raise NotImplementedError('FARNN_S_SF: training needs d loss / d input for the encoder in front of it and is not '
-                                      'built (DESIGN.md, row f14); call forward(..., train=False)')
+            if not opted_in('SF_TRAIN'):
+                raise NotImplementedError('FARNN_S_SF: training needs d loss / d input for the encoder in front of it and is not '
+                                          'built (DESIGN.md, row f14); call forward(..., train=False)')
+            self._check_step(re_tags)
+            return Trainable.forward_local(self, input, label, lengths, train=True, re_tags=re_tags)
+        self.sync_from_training()
         r = self.run_vectors(input, lengths, want_flat=True)
         return None, r['flat'].to(label.device), self._flatten(label, lengths)
 
@@ -411,7 +457,14 @@ class FARNN_S_bert:
                                       start_vector=start_vector, priority_mat=priority_mat, args=args, o_idx=o_idx,
                                       is_cuda=is_cuda)
 
+    def parameters(self):
+        """The aggregator's leaves (EmbedAggregator.requires_grad_()), a torch.nn.Module encoder's parameters, and the
+        automaton's (after its first training step, or slot_filler.enable_training())."""
+        return iter(list(self.embed.parameters()) + list(self.slot_filler.parameters()))
+
     def forward(self, input, bert_input, bert_attend_mask, bert_valid_mask, lengths, label, train=False, re_tags=None):
+        """train=True (RE2NN_SF_TRAIN=1): the loss's backward() reaches the aggregator's leaves and the
+        encoder through d loss / d vecs."""
         vecs = self.embed.forward_bert(input, bert_input, bert_attend_mask, bert_valid_mask, lengths)
         return self.slot_filler(vecs, label, lengths, train=train, re_tags=re_tags)
 

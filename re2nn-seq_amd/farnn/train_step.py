@@ -1,5 +1,6 @@
 """The training steps on the HIP path: one torch.autograd.Function (_TrainStep) around farnn_decomp_ifst_train_step,
-farnn_onehot_ifst_train_step, farnn_fst4_train_step, farnn_ind1_train_step and farnn_decomp_ind1_train_step (include/farnn.h).
+farnn_onehot_ifst_train_step, farnn_fst4_train_step, farnn_ind1_train_step, farnn_decomp_ind1_train_step and
+farnn_decomp_sf_train_step (include/farnn.h).
 Each public function below describes its weights to it (the C struct's field, the tensor, when its gradient is asked of the
 library) and, where the call is not the context's plain step(), makes the library call itself (teacher_step, step_crf).
 
@@ -121,6 +122,26 @@ def decomp_ifst_train_step(tc, Vgen, S1, S2, W, Cmat, h0, hT, P, x, lengths, lab
     spec = [(n, t, ALWAYS) for n, t in zip(('Vgen', 'S1', 'S2', 'W', 'C', 'h0', 'hT'), (Vgen, S1, S2, W, Cmat, h0, hT))]
     spec += [('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)] + [(n, g, ALWAYS) for n, g in zip(GATE_NAMES, gates)]
     return _step(tc, valid_tokens, x, lengths, labels, spec, call)
+
+
+def decomp_sf_train_step(tc, v, S1, S2, W, Cmat, h0, hT, P, lengths, labels, crf_trans=None, gates=(), valid_tokens=None):
+    """The vector-input i-FST (FARNN_S_SF, model_decompose_single.py:483-580), sum semiring, no teacher: returns
+    (loss scalar tensor with grad, tags int32 [B,L] with -1 at pads).  v [B, >= L, R] is a differentiable input, L =
+    labels.shape[1]: v[:, :L] is made contiguous float32 on the weights' device, and its gradient (exact zeros at the pad
+    positions, bit-identical from call to call) comes back scaled by the incoming gradient, like the weights'.  One library call
+    (farnn_decomp_sf_train_step on an _lib.SfTrainContext).  gates, crf_trans, valid_tokens: as decomp_ifst_train_step's."""
+    if len(gates) not in (0, 3, 6):
+        raise ValueError('gates: none, Wss1 Wrs1 bs1 (farnn 1) or those and Wss2 Wrs2 bs2 (farnn 2), not {} tensors'.format(len(gates)))
+    B, L = labels.shape
+    if v.dim() != 3 or v.shape[0] != B or v.shape[1] < L or v.shape[2] != S1.shape[1]:
+        raise ValueError('v must be [B, >= L, R] = [{}, >= {}, {}], not {}'.format(B, L, S1.shape[1], tuple(v.shape)))
+    v = v[:, :L].to(device=S1.device)
+
+    def call(weights, ptrs, dims, outputs, stream):
+        tc.step_vectors(weights, weights['v'], ptrs[1], ptrs[2], *dims, outputs, outputs['dv'], stream)
+    spec = [(n, t, ALWAYS) for n, t in zip(('S1', 'S2', 'W', 'C', 'h0', 'hT'), (S1, S2, W, Cmat, h0, hT))]
+    spec += [('v', v, ALWAYS), ('P', P, NEVER), ('crf_trans', crf_trans, ALWAYS)] + [(n, g, ALWAYS) for n, g in zip(GATE_NAMES, gates)]
+    return _step(tc, valid_tokens, labels, lengths, labels, spec, call)      # (x only gives the step its [B, L])
 
 
 _D0_NAMES = ('Vgen', 'Ce', 'S1', 'S2', 'Cw', 'S1w', 'S2w', 'WW', 'h0', 'hT')
