@@ -347,6 +347,23 @@ int farnn_reserve(farnn_model *m, int32_t B, int32_t L);
  * farnn_tag_host_submit, which calls farnn_tag).
  * These two entry points were ADDED to ABI version 2: no existing signature or struct changed, so the number stands. */
 int farnn_decomp_sf_create(const farnn_decomp_ifst_desc *desc, int device, farnn_model **out);
+/* ---- ... in the max semiring (reference model_decompose_single.py:435-442: Tr[b] = S1 diag(v_b) S2^T + W,
+ * h' = max_j hbar[j] Tr[j, s]) ------------------------------------------------------------------------------------------
+ * farnn_decomp_sf_max_create takes the same descriptor with semiring == FARNN_SEMIRING_MAX, V = 0 and Vgen = NULL (anything
+ * else: FARNN_EINVAL; farnn_decomp_sf_create goes on refusing the max semiring).  Tagging only: a training context with vector
+ * input and the max semiring is still refused.  farnn_tag_vectors serves the handle, FARNN_MODE_LOCAL only, by one of two routes
+ * chosen per call before anything is launched:
+ *   dense    farnn == 0 and a model the dense chain kernels hold (what an id handle of the max semiring requires for its per-word
+ *            blocks), up to 16 GiB of blocks a call: token_blocks_kernel writes one [SR][SP] block per valid token and its
+ *            transpose into the handle's grow-only workspace (farnn_reserve sizes it), each entry summed exactly like the id
+ *            handle's create-time block of a word; the chain, score and decode kernels of that id handle follow on the ids b L + t.
+ *   generic  farnn 1 / 2, or anything the dense route does not take: token_table_kernel writes the padded copy [B L][Rp] and
+ *            decomp_chain_kernel materialises Tr per step from it, as on an id handle.
+ * On either route a vector that is bit for bit a row of Vgen is tagged bit for bit like that word on a max-semiring
+ * farnn_decomp_ifst_create handle of the same weights.  A shape neither route holds: FARNN_ERANGE, nothing launched.
+ * farnn_kernel_name(m, 3) names the kernel in front of the last call's recurrence: token_blocks_kernel or token_table_kernel.
+ * ADDED to ABI version 2: no existing signature or struct changed, so the number stands. */
+int farnn_decomp_sf_max_create(const farnn_decomp_ifst_desc *desc, int device, farnn_model **out);
 int farnn_tag_vectors(farnn_model *m, const float *v, const int64_t *lengths, int32_t B, int32_t L,
                       int32_t mode, int32_t *tags, int64_t *flat_tags, float *scores, void *stream);
 

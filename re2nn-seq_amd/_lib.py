@@ -337,6 +337,7 @@ SIGNATURES = {
     'farnn_tag': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     'farnn_reserve': (C.c_int, [_vp, C.c_int32, C.c_int32]),
     'farnn_decomp_sf_create': (C.c_int, [C.POINTER(DecompIfstDesc), C.c_int, C.POINTER(_vp)]),
+    'farnn_decomp_sf_max_create': (C.c_int, [C.POINTER(DecompIfstDesc), C.c_int, C.POINTER(_vp)]),
     'farnn_tag_vectors': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     'farnn_tag_host_submit': (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'farnn_flatten_host': (C.c_int64, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
@@ -641,6 +642,23 @@ def create_decomp_sf(S1, S2, W, Cout, h0, hT, P=None, farnn=0, gates=None, sigmo
                        float(sigmoid_exponent), NL[nl], SEMIRING[semiring], float(threshold), int(o_idx),
                        int(bool(use_crf)), ptr(crf_trans), 0)
     return _create('farnn_decomp_sf_create', d, device, (S1, S2, W, Cout, h0, hT, P, crf_trans, g))
+
+
+def create_decomp_sf_max(S1, S2, W, Cout, h0, hT, P=None, farnn=0, gates=None, sigmoid_exponent=5, nl='none', threshold=0.5,
+                         o_idx=0, use_crf=False, crf_trans=None, device=0):
+    """create_decomp_sf in the max semiring (farnn_decomp_sf_max_create): tagging only, with Handle.tag_vectors."""
+    S1, S2, W, Cout, h0, hT = (f32(a) for a in (S1, S2, W, Cout, h0, hT))
+    P = None if P is None else f32(P)
+    crf_trans = None if crf_trans is None else f32(crf_trans)
+    g = {k: f32(v) for k, v in (gates or {}).items()}
+    S, R = S1.shape
+    d = DecompIfstDesc(0, S, R, Cout.shape[0], None, ptr(S1), ptr(S2), ptr(W), ptr(Cout),
+                       ptr(h0), ptr(hT), ptr(P), int(farnn),
+                       ptr(g.get('Wss1')), ptr(g.get('Wrs1')), ptr(g.get('bs1')),
+                       ptr(g.get('Wss2')), ptr(g.get('Wrs2')), ptr(g.get('bs2')),
+                       float(sigmoid_exponent), NL[nl], SEMIRING['max'], float(threshold), int(o_idx),
+                       int(bool(use_crf)), ptr(crf_trans), 0)
+    return _create('farnn_decomp_sf_max_create', d, device, (S1, S2, W, Cout, h0, hT, P, crf_trans, g))
 
 
 def create_decomp_ifst_folded(V_embed, E, G, beta, S1, S2, W, Cout, h0, hT, add_nl='none', normalize='none', P=None,

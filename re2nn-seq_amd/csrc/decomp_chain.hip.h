@@ -160,12 +160,16 @@ decomp_chain_kernel(const DecompParams p) {
     }
 }
 
+// dynamic LDS of decomp_chain_kernel (a plan asks before anything is launched)
+inline size_t decomp_chain_lds_bytes(const DecompWeights &w, int L) {
+    return ((size_t)((L + 3) & ~3) + 3 * (size_t)w.SP + 2 * (size_t)w.Rp) * sizeof(float);
+}
+
 inline int launch_decomp_chain(const DecompWeights &w, const int64_t *x, const int64_t *len,
                                const int *order, float *A, float *Bk, int B, int L, int full, hipStream_t s) {
     DecompParams p;
     p.w = w; p.x = x; p.len = len; p.A = A; p.Bk = Bk; p.B = B; p.L = L; p.full = full;
-    const int Lr = (L + 3) & ~3;
-    size_t lds = ((size_t)Lr + 3 * (size_t)w.SP + 2 * (size_t)w.Rp) * sizeof(float);
+    const size_t lds = decomp_chain_lds_bytes(w, L);
     if (lds > 160 * 1024) return fail(FARNN_ERANGE, "decomposed chain: LDS budget exceeded%s%s");
     if (lds > 48 * 1024)
         FARNN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(decomp_chain_kernel),

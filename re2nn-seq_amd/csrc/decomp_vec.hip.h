@@ -137,6 +137,173 @@ token_table_kernel(const TokenTableParams p) {
     }
 }
 
+// ---- the per-call TOKEN BLOCKS of the vector-input tagger in the max semiring (model_decompose_single.py:435-442) -------------
+// h' = max_j hbar[j] Tr[j][s] needs the step's whole transition matrix, Tr[n] = S1 diag(v[n]) S2^T + W, and with vectors that are
+// rows of no table that is one S x S block per TOKEN and per call: a [B L S] x [R] x [S] product (51 GFLOP over the 9 516 valid tokens
+// of a ragged 256 x 64 batch at S = 104, R = 250) in front of the dense chain kernels, which then read the blocks exactly as they read an id handle's per-word
+// blocks -- layout [SR][SP] per block, pads zero, Mf[n][i][j] = Tr[i][j] and Mb[n][j][i] = Tr[i][j] -- on the identity ids.
+//
+// Every ENTRY is accumulated exactly like materialise_blocks_kernel (layout.hip.h) accumulates it for a word: the product
+// v[r] S1[i][r] rounded on its own, fmaf with S2[j][r] over r = 0 .. R-1 in order from 0, then + W[i][j].  A vector that is a row of
+// Vgen gets the bits of that word's create-time block.  So, as in token_table_kernel: no matrix-core instruction, no split of the
+// r loop between lanes; the tile only decides who computes an entry.
+//
+// One workgroup per valid token and 128 x 128 tile of its block (one tile up to S = 128); n8 = ceil(min(S, 128) / 8) and
+// n8 x n8 threads (169 at S = 104, launched as 192), a thread 8 x 8 accumulators: rows {4 ti .., 4 n8 + 4 ti ..}, columns
+// {4 tj .., 4 n8 + 4 tj ..}, so that the lanes of a wavefront read contiguous 16-byte pieces of a staged row.  Per 32 ranks the
+// A operand, S1^T's tile scaled by v[n] ([rank][i]: the product is rounded once, by the thread that stages it), lies in LDS beside
+// S2^T's tile ([rank][j]); per rank a thread issues four ds_read_b128 for 64 FMAs.  S1^T and S2^T (208 KB at S = 104, R = 250) stay
+// in L2: a token re-stages them, 26 flops per byte staged, well under what a compute unit's L2 port delivers -- so one token per
+// workgroup, no token loop inside it, and the ragged batch balances itself.  LDS: 2 x 32 x 132 floats = 33 KiB static (four
+// workgroups per compute unit); the epilogue's transpose tile aliases it.  The epilogue adds W, stores Mf's rows as 16-byte pieces
+// and passes each 4 n8 x 4 n8 quadrant through LDS transposed, so that Mb's rows leave as contiguous runs as well; the tile of
+// (0, 0) also zeroes the pad rows S .. SR-1 of both images.
+// By design bound by f32 FMA issue: 64 FMAs against 4 LDS reads (16 LDS cycles per wavefront and rank, three wavefronts per
+// workgroup) and, per token, 2 SR SP 4 bytes of stores (92 KB at S = 104) against 5.4 MFLOP at R = 250.  Measured (256 x 64 ragged,
+// S = 104, profiles/sf_max_tag_timing.json): R = 250 1 026 us, 50 TFLOP/s, 38 % of the packed-FMA rate -- the single staging buffer
+// and its two barriers per round, not the FMA pipe, set the pace; R = 50 315 us, bound by the 871 MB of stores.
+constexpr int TB_TILE = 128;          // rows and columns of a block per workgroup
+constexpr int TB_KC = 32;             // ranks staged per round
+constexpr int TB_LD = TB_TILE + 4;    // row stride (floats) of the staged tiles: 16-byte aligned rows
+constexpr int TB_LDT = 68;            // row stride of the epilogue's transpose tile (a quadrant is at most 64 x 64)
+constexpr int TB_MAX_THREADS = 256;
+
+struct TokenBlocksParams {
+    const float *v;               // [B][L][R] dense
+    const int64_t *len;           // [B]
+    const float *S1T, *S2T;       // [R][SP]
+    const float *W;               // [S][SP]
+    float *Mf, *Mb;               // [B L][SR][SP]
+    int B, L, R, S, SP, SR;
+    int n8, ntile;                // threads per side; 128-wide tiles per side
+};
+
+__global__ void __launch_bounds__(TB_MAX_THREADS)
+token_blocks_kernel(const TokenBlocksParams p) {
+    __shared__ __align__(16) float smem[2 * TB_KC * TB_LD];
+    float *As = smem, *Bs = smem + TB_KC * TB_LD;
+    const long long n = blockIdx.x;
+    if ((int)(n % p.L) >= clamp_len(p.len[n / p.L], p.L)) return;             // a pad position: neither read nor written
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int i0 = ((int)blockIdx.y / p.ntile) * TB_TILE, j0 = ((int)blockIdx.y % p.ntile) * TB_TILE;
+    const int n8 = p.n8, H = 4 * n8;
+    const bool active = tid < n8 * n8;
+    const int ti = active ? tid / n8 : 0, tj = active ? tid - ti * n8 : 0;
+    const int S = p.S, SP = p.SP, R = p.R;
+    const float *vn = p.v + n * R;
+
+    float acc[8][8];
+#pragma unroll
+    for (int a = 0; a < 8; a++)
+#pragma unroll
+        for (int q = 0; q < 8; q++) acc[a][q] = 0.0f;
+
+    for (int k0 = 0; k0 < R; k0 += TB_KC) {
+        // ---- stage A = v[n][k] S1T[k][i0 ..) and B = S2T[k][j0 ..): 32 ranks x 32 pieces of four, zero past SP and past R ----
+        for (int e = tid; e < TB_KC * (TB_TILE / 4); e += nthr) {
+            const int k = e >> 5, c = (e & 31) * 4, r = k0 + k;
+            v4f a = {0.0f, 0.0f, 0.0f, 0.0f}, b = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (r < R) {
+                if (i0 + c < SP) {
+                    const v4f s1 = *reinterpret_cast<const v4f *>(&p.S1T[(long long)r * SP + i0 + c]);
+                    const float x = vn[r];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) a[q] = x * s1[q];
+                }
+                if (j0 + c < SP) b = *reinterpret_cast<const v4f *>(&p.S2T[(long long)r * SP + j0 + c]);
+            }
+            *reinterpret_cast<v4f *>(&As[k * TB_LD + c]) = a;
+            *reinterpret_cast<v4f *>(&Bs[k * TB_LD + c]) = b;
+        }
+        __syncthreads();
+        if (active) {
+            // (the ranks past R are not run: fmaf(0, 0, acc) is acc for every acc but -0)
+            const int kn = R - k0 < TB_KC ? R - k0 : TB_KC;
+#pragma unroll 2
+            for (int k = 0; k < kn; k++) {
+                const v4f a0 = *reinterpret_cast<const v4f *>(&As[k * TB_LD + ti * 4]);
+                const v4f a1 = *reinterpret_cast<const v4f *>(&As[k * TB_LD + H + ti * 4]);
+                const v4f b0 = *reinterpret_cast<const v4f *>(&Bs[k * TB_LD + tj * 4]);
+                const v4f b1 = *reinterpret_cast<const v4f *>(&Bs[k * TB_LD + H + tj * 4]);
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        acc[a][q] = fmaf(a0[a], b0[q], acc[a][q]);
+                        acc[a][4 + q] = fmaf(a0[a], b1[q], acc[a][4 + q]);
+                        acc[4 + a][q] = fmaf(a1[a], b0[q], acc[4 + a][q]);
+                        acc[4 + a][4 + q] = fmaf(a1[a], b1[q], acc[4 + a][4 + q]);
+                    }
+            }
+        }
+        __syncthreads();
+    }
+
+    const long long base = n * (long long)p.SR * SP;
+    // ---- + W; zero outside S x S; Mf's rows ----
+    if (active) {
+#pragma unroll
+        for (int a = 0; a < 8; a++) {
+            const int i = i0 + (a < 4 ? 0 : H) + ti * 4 + (a & 3);
+#pragma unroll
+            for (int hq = 0; hq < 2; hq++) {
+                const int j = j0 + hq * H + tj * 4;
+                v4f out = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (i < S && j < SP) {
+                    const v4f w = *reinterpret_cast<const v4f *>(&p.W[(long long)i * SP + j]);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) out[q] = j + q < S ? acc[a][hq * 4 + q] + w[q] : 0.0f;
+                    *reinterpret_cast<v4f *>(&p.Mf[base + (long long)i * SP + j]) = out;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) acc[a][hq * 4 + q] = out[q];
+            }
+        }
+    }
+    // ---- Mb = the transpose, a quadrant at a time through LDS (the loop above ended on a barrier: the staging tiles are free) ----
+    float *T = smem;
+#pragma unroll
+    for (int ha = 0; ha < 2; ha++)
+#pragma unroll
+        for (int hq = 0; hq < 2; hq++) {
+            if (active) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const v4f t = {acc[ha * 4][hq * 4 + q], acc[ha * 4 + 1][hq * 4 + q], acc[ha * 4 + 2][hq * 4 + q], acc[ha * 4 + 3][hq * 4 + q]};
+                    *reinterpret_cast<v4f *>(&T[(tj * 4 + q) * TB_LDT + ti * 4]) = t;
+                }
+            }
+            __syncthreads();
+            for (int e = tid; e < H * n8; e += nthr) {
+                const int jl = e / n8, c = (e - jl * n8) * 4;
+                const int j = j0 + hq * H + jl, i = i0 + ha * H + c;
+                if (j < S && i < SP)
+                    *reinterpret_cast<v4f *>(&p.Mb[base + (long long)j * SP + i]) = *reinterpret_cast<const v4f *>(&T[jl * TB_LDT + c]);
+            }
+            __syncthreads();
+        }
+    // ---- the pad rows S .. SR-1 of both images ----
+    if (blockIdx.y == 0) {
+        const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
+        const long long r0 = base + (long long)S * SP;           // (S SP is a multiple of four)
+        for (int e = tid; e < (p.SR - S) * SP / 4; e += nthr) {
+            *reinterpret_cast<v4f *>(&p.Mf[r0 + 4LL * e]) = z;
+            *reinterpret_cast<v4f *>(&p.Mb[r0 + 4LL * e]) = z;
+        }
+    }
+}
+
+inline int launch_token_blocks(TokenBlocksParams p, hipStream_t s) {
+    const long long NT = (long long)p.B * p.L;
+    const int side = p.S < TB_TILE ? p.S : TB_TILE;
+    p.n8 = (side + 7) / 8;
+    p.ntile = (p.S + TB_TILE - 1) / TB_TILE;
+    const int threads = (p.n8 * p.n8 + 63) / 64 * 64;
+    token_blocks_kernel<<<dim3((unsigned)NT, p.ntile * p.ntile), dim3(threads), 0, s>>>(p);
+    FARNN_HIP_TRY(hipGetLastError());
+    return FARNN_OK;
+}
+
 // ids[i] = i: with them x[b L + t] = b L + t names the token's own row, whatever the call's L
 __global__ void iota_kernel(int64_t *ids, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -43,7 +43,10 @@ extern "C" int farnn_set_compact(farnn_model *m, int32_t enable) {
 
 // ---- workspace -------------------------------------------------------------------------------
 // floats of a row of the token table: what decomp_rows_kernel calls tvl
-static int sf_row_floats(const farnn_model *m) { return m->Rp + (m->dw.farnn >= 1 ? m->SP : 0) + (m->dw.farnn == 2 ? m->SP : 0); }
+// (a max-semiring handle's rows are the padded copy alone: decomp_chain_kernel computes its gates itself)
+static int sf_row_floats(const farnn_model *m) {
+    return m->sf_max ? m->Rp : m->Rp + (m->dw.farnn >= 1 ? m->SP : 0) + (m->dw.farnn == 2 ? m->SP : 0);
+}
 
 extern "C" int farnn_reserve(farnn_model *m, int32_t B, int32_t L) {
     if (!m || B <= 0 || L <= 0) return fail(FARNN_EINVAL, "reserve: bad arguments%s%s");
@@ -68,8 +71,20 @@ extern "C" int farnn_reserve(farnn_model *m, int32_t B, int32_t L) {
         FARNN_HIP_TRY(hipMalloc((void **)&w.d1_br, (size_t)nB * nL * ((m->S + 15) / 16) * ((m->RO + 15) / 16 * 16) * sizeof(float)));
     if (m->sf) {      // the token table (rows of the handle's own tvl floats; +1 KiB like dev_alloc) and the identity ids of the largest call
         const size_t nt = (size_t)nB * nL, tt_bytes = nt * sf_row_floats(m) * sizeof(float) + 1024;
-        FARNN_HIP_TRY(hipMalloc((void **)&w.tt, tt_bytes));
-        FARNN_HIP_TRY(hipMemset(w.tt, 0, tt_bytes));       // (rows of pad positions are never written; nothing reads them either)
+        // a max-semiring handle on the dense route: the two block images of the largest call that route takes (plan_tag), and the
+        // token table only when a call within the capacity can fall through to the generic route
+        const size_t nblk = (m->sf_max && m->sf_dense) ? std::min(nt, (size_t)m->sf_block_tokens) : 0;
+        if (nblk) {
+            const size_t tb_bytes = nblk * m->geom.SR * m->SP * sizeof(float) + 1024;      // +1 KiB like dev_alloc
+            FARNN_HIP_TRY(hipMalloc((void **)&w.tbf, tb_bytes));
+            FARNN_HIP_TRY(hipMalloc((void **)&w.tbb, tb_bytes));
+            FARNN_HIP_TRY(hipMemset(w.tbf, 0, tb_bytes));  // (blocks of pad positions are never written; no chain kernel's step reads them)
+            FARNN_HIP_TRY(hipMemset(w.tbb, 0, tb_bytes));
+        }
+        if (!nblk || nt > nblk) {
+            FARNN_HIP_TRY(hipMalloc((void **)&w.tt, tt_bytes));
+            FARNN_HIP_TRY(hipMemset(w.tt, 0, tt_bytes));   // (rows of pad positions are never written; nothing reads them either)
+        }
         FARNN_HIP_TRY(hipMalloc((void **)&w.ids, nt * sizeof(int64_t)));
         iota_kernel<<<(unsigned)((nt + 255) / 256), 256>>>(w.ids, (long long)nt);
         FARNN_HIP_TRY(hipGetLastError());
@@ -337,6 +352,19 @@ static int plan_tag(const farnn_model *m, int B, int L, int full, bool flat, boo
             return plan_chain(m, p, false, lm_tags, offs_ok);
         case KIND_DECOMP:
             if (m->dense_decomp) return plan_chain_and_decode(m, p, flat, scores, offs, lm_tags, offs_ok);
+            if (m->sf_max) {
+                // dense route: one block per token in front of the chain kernels, planned exactly like a dense_decomp id handle
+                // with V = B L; beyond the workspace's cap (tag_create.hip.h), or with gates, the generic kernel on the padded copy
+                if (m->sf_dense && (long long)B * L <= m->sf_block_tokens) {
+                    p.blocks = true;
+                    return plan_chain_and_decode(m, p, flat, scores, offs, lm_tags, offs_ok);
+                }
+                if (decomp_chain_lds_bytes(m->dw, L) > 160 * 1024)
+                    return fail(FARNN_ERANGE, "tag_vectors: decomp_chain_kernel's LDS does not hold this model at this sequence length%s%s");
+                p.rec = REC_DECOMP_CHAIN;
+                p.table = true; p.table_cols = 0;
+                return plan_score_decode(m, p, flat, scores, offs);
+            }
             plan_decomp_recurrence(m, p, !m->use_crf, offs_ok);
             if (m->sf) {
                 if (p.rec == REC_DECOMP_CHAIN)     // (decomp_chain_kernel is not served from the token table: include/farnn.h)
@@ -413,7 +441,7 @@ extern "C" const char *farnn_kernel_name(const farnn_model *m, int32_t which) {
                               : (m->kind == KIND_DECOMP0 ? "decomp0_score_kernel"
                               : (m->use_crf ? "score_tile_kernel+viterbi_kernel" : (m->last_lm_score ? "label_map_score_kernel" : "score_tile_kernel")))));
         case KERN_PREP:  return "batch_prep_kernel";
-        case KERN_TABLE: return m->sf ? "token_table_kernel" : "";
+        case KERN_TABLE: return !m->sf ? "" : p.blocks ? "token_blocks_kernel" : "token_table_kernel";
         default: return "";
     }
 }
@@ -474,10 +502,10 @@ static int launch_chain_regs_form(farnn_model *m, const TagPlan &pl, const int64
     const bool mx = m->semiring == FARNN_SEMIRING_MAX;
     RegsParams rp;
     memset(&rp, 0, sizeof(rp));
-    rp.Mf = m->Mf; rp.Mb = m->Mb; rp.blk = (long long)m->geom.SR * m->SP;
+    rp.Mf = pl.blocks ? m->ws.tbf : m->Mf; rp.Mb = pl.blocks ? m->ws.tbb : m->Mb; rp.blk = (long long)m->geom.SR * m->SP;
     rp.o = m->o; rp.h0 = m->h0; rp.hT = m->hT; rp.x = x; rp.len = len;
     rp.order = pl.order_valid ? m->ws.order : nullptr; rp.sort = pl.sort_in_kernel ? 1 : 0;
-    rp.A = m->ws.A; rp.Bk = m->ws.Bk; rp.B = pl.B; rp.L = pl.L; rp.S = m->S; rp.SP = m->SP; rp.CPR = rg.CPR; rp.V = m->V;
+    rp.A = m->ws.A; rp.Bk = m->ws.Bk; rp.B = pl.B; rp.L = pl.L; rp.S = m->S; rp.SP = m->SP; rp.CPR = rg.CPR; rp.V = pl.blocks ? pl.B * pl.L : m->V;
     rp.G = rg.G; rp.RPG = rg.RPG; rp.RQ = rg.RQ; rp.D = rg.D; rp.PS = rg.PS; rp.pair = rg.wide ? 0 : 1;
     rp.nl = m->nl; rp.full = pl.full; rp.dbg = tun(TUN_DBG);
     rp.dest = pl.dest ? 1 : 0; rp.half = pl.half ? 1 : 0; rp.row80 = pl.row80 ? 1 : 0;          // chain_dest.hip.h
@@ -507,11 +535,11 @@ static int launch_chain_regs_form(farnn_model *m, const TagPlan &pl, const int64
 static int launch_chain_kernel(farnn_model *m, const TagPlan &pl, const int64_t *x, const int64_t *len, hipStream_t s) {
     const ChainGeom &g = m->geom;
     ChainParams p;
-    p.Mf = m->Mf; p.Mb = m->Mb; p.blk = (long long)m->geom.SR * m->SP;
+    p.Mf = pl.blocks ? m->ws.tbf : m->Mf; p.Mb = pl.blocks ? m->ws.tbb : m->Mb; p.blk = (long long)m->geom.SR * m->SP;
     p.o = m->o; p.h0 = m->h0; p.hT = m->hT; p.x = x; p.len = len; p.A = m->ws.A; p.Bk = m->ws.Bk;
     p.order = pl.order_valid ? m->ws.order : nullptr;
     p.sort = pl.sort_in_kernel ? 1 : 0;
-    p.B = pl.B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.CPR = g.CPR; p.V = m->V;
+    p.B = pl.B; p.L = pl.L; p.S = m->S; p.SP = m->SP; p.CPR = g.CPR; p.V = pl.blocks ? pl.B * pl.L : m->V;
     p.NW = g.NW; p.NLD = g.NLD; p.G = g.G; p.LPR = g.LPR; p.RPG = g.RPG; p.RPGp = g.RPGp; p.NQ = g.NQ;
     p.nl = m->nl; p.full = pl.full; p.dbg = tun(TUN_DBG);
     p.KS = pl.KS; p.NQP = pl.NQP; p.PPS = pl.PPS;
@@ -735,6 +763,16 @@ static int launch_table(farnn_model *m, const TagPlan &pl, const float *v, const
     return launch_token_table(p, s);
 }
 
+// the token blocks of a max-semiring vector-input call on the dense route (decomp_vec.hip.h)
+static int launch_blocks(farnn_model *m, const TagPlan &pl, const float *v, const int64_t *len, hipStream_t s) {
+    TokenBlocksParams p;
+    memset(&p, 0, sizeof(p));
+    p.v = v; p.len = len; p.S1T = m->dw.S1T; p.S2T = m->dw.S2T; p.W = m->dw.W; p.Mf = m->ws.tbf; p.Mb = m->ws.tbb;
+    p.B = pl.B; p.L = pl.L; p.R = m->R; p.S = m->S; p.SP = m->SP; p.SR = m->geom.SR;
+    KernelTimer kt(m, KERN_TABLE, s);
+    return launch_token_blocks(p, s);
+}
+
 // order the streams, reserve, plan, then launch from the plan: prep, (token table,) recurrence, scores + decode
 // v != nullptr: farnn_tag_vectors -- x is ignored, the recurrence runs on the workspace's identity ids
 static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, int32_t B, int32_t L,
@@ -782,8 +820,8 @@ static int tag_impl(farnn_model *m, const int64_t *x, const int64_t *lengths, in
         FARNN_HIP_TRY(hipGetLastError());
     }
     const ScoreParams sp = make_score_params(m, pl, lengths, tags, flat_tags, scores);
-    if (pl.table) {
-        if ((rc = launch_table(m, pl, v, lengths, s))) return rc;
+    if (pl.table || pl.blocks) {
+        if ((rc = pl.blocks ? launch_blocks(m, pl, v, lengths, s) : launch_table(m, pl, v, lengths, s))) return rc;
         x = m->ws.ids;
     }
     if ((rc = launch_recurrence(m, pl, x, lengths, sp, s))) return rc;
@@ -796,7 +834,7 @@ extern "C" int farnn_tag(farnn_model *m, const int64_t *x, const int64_t *length
     if (B <= 0 || L <= 0) return fail(FARNN_EINVAL, "tag: B and L must be positive%s%s");
     if (mode != FARNN_MODE_LOCAL && mode != FARNN_MODE_FULL && mode != FARNN_MODE_RE)
         return fail(FARNN_EINVAL, "tag: bad mode%s%s");
-    if (m->sf) return fail(FARNN_EINVAL, "tag: this handle takes vectors, not word ids (farnn_decomp_sf_create): call farnn_tag_vectors%s%s");
+    if (m->sf) return fail(FARNN_EINVAL, "tag: this handle takes vectors, not word ids (farnn_decomp_sf_create / farnn_decomp_sf_max_create): call farnn_tag_vectors%s%s");
     if (mode != FARNN_MODE_RE) return tag_impl(m, x, lengths, B, L, mode, tags, flat_tags, scores, stream);
     if (m->kind != KIND_IFST && m->kind != KIND_FST4 && m->kind != KIND_IND1)
         return fail(FARNN_EINVAL, "tag: FARNN_MODE_RE exists on the onehot models only (model_onehot.py:148)%s%s");

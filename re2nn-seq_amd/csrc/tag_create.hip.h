@@ -663,17 +663,26 @@ static int decomp_geometry(farnn_model *m, const Desc *d) {
 }
 
 // ---- create: decomposed i-FST ------------------------------------------------------------------
+// The two block images of a max-semiring vector-input call, 2 B L SR SP 4 bytes, live in the handle's grow-only workspace.  The
+// cap keeps one handle from taking the device: 1 024 x 128 positions at S = 104 are 131 072 blocks of SR x SP = 110 x 104
+// floats, 12.0 GB for both images -- the largest batch the tagging benchmarks run -- and stay on the dense route under
+// 16 GiB, a sixteenth of the card's 288 GB; a larger call tags through decomp_chain_kernel, slower but in B L Rp 4 bytes.
+constexpr size_t SF_MAX_BLOCK_BYTES = (size_t)16 << 30;
+
 // od_vgen / od_s12: Vgen resp. S1, S2 are device pointers whatever d->weights_on_device says (the folded creator)
 // sf: the vector-input handle (farnn_decomp_sf_create): V = 0 and no Vgen, nothing per word is ever built
-static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, farnn_model **out, int od_vgen, int od_s12, bool sf = false) {
+// sf_max (with sf): its max-semiring form (farnn_decomp_sf_max_create)
+static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, farnn_model **out, int od_vgen, int od_s12, bool sf = false, bool sf_max = false) {
     int rc = begin_create(d != nullptr, out);
     if (rc) return rc;
     if (sf && (d->V != 0 || d->Vgen)) return fail(FARNN_EINVAL, "decomp_sf: V must be 0 and Vgen NULL (the vectors come with every call)%s%s");
     if ((!sf && (d->V <= 0 || !d->Vgen)) || d->S <= 0 || d->R <= 0 || d->K <= 0 || !d->S1 || !d->S2 || !d->W ||
         !d->Cout || !d->h0 || !d->hT)
         return fail(FARNN_EINVAL, "decomp_ifst: sizes must be positive and factor pointers non-null%s%s");
-    if (sf && d->semiring != FARNN_SEMIRING_SUM)
+    if (sf && !sf_max && d->semiring != FARNN_SEMIRING_SUM)
         return fail(FARNN_EINVAL, "decomp_sf: the max semiring needs an S x S block per token; vector input exists in the sum semiring only%s%s");
+    if (sf_max && d->semiring != FARNN_SEMIRING_MAX)
+        return fail(FARNN_EINVAL, "decomp_sf_max: the descriptor's semiring must be FARNN_SEMIRING_MAX (the sum semiring: farnn_decomp_sf_create)%s%s");
     const GateSrc gates{d->farnn, d->Wss1, d->Wrs1, d->bs1, d->Wss2, d->Wrs2, d->bs2};
     if ((rc = check_gates(gates, "decomp_ifst"))) return rc;
     if (d->nl < 0 || d->nl > FARNN_NL_RELUTANH) return fail(FARNN_EINVAL, "decomp_ifst: bad nl%s%s");
@@ -689,7 +698,13 @@ static int decomp_ifst_create_impl(const farnn_decomp_ifst_desc *d, int device, 
     if ((rc = upload_start_final(m, d->h0, d->hT, od))) return rc;
     if ((rc = upload_decode_tables(m, d->P, d->crf_trans, od))) return rc;
     if ((rc = build_rows_pack(m))) return rc;
-    if (sf) {
+    if (sf_max) {
+        // the dense route's test is build_dense_blocks' own; nothing is built here: the blocks are the call's (farnn_reserve, plan_tag)
+        m->sf = m->sf_max = true;
+        pick_chain_geometry(m);
+        m->sf_dense = m->dw.farnn == 0 && m->geom.NCH <= 4 && m->geom.SP == m->SP;
+        m->sf_block_tokens = (long long)(SF_MAX_BLOCK_BYTES / (2 * (size_t)m->geom.SR * m->SP * sizeof(float)));
+    } else if (sf) {
         // decomp_chain_kernel (the fallback behind the packed rows) reads rows at stride Rp and computes its gates itself: it is not
         // served from the token table, its shapes are refused (include/farnn.h)
         if (!m->rows.ok) return fail(FARNN_ERANGE, "decomp_sf: a per-token row of more than %s floats (Rp + SP per gate) is not supported%s", "2048", "");
@@ -705,6 +720,10 @@ extern "C" int farnn_decomp_ifst_create(const farnn_decomp_ifst_desc *d, int dev
 
 extern "C" int farnn_decomp_sf_create(const farnn_decomp_ifst_desc *d, int device, farnn_model **out) {
     return decomp_ifst_create_impl(d, device, out, 0, 0, true);
+}
+
+extern "C" int farnn_decomp_sf_max_create(const farnn_decomp_ifst_desc *d, int device, farnn_model **out) {
+    return decomp_ifst_create_impl(d, device, out, 0, 0, true, true);
 }
 
 // largest eigenvalue of a symmetric positive semi-definite n x n matrix (a Gram matrix; doubles; n <= a few hundred: create time).

@@ -19,7 +19,7 @@
 using namespace farnn;
 
 enum { KIND_IFST = 2, KIND_IND1 = 1, KIND_FST4 = 0, KIND_DECOMP = 12, KIND_DECOMP1 = 11, KIND_DECOMP0 = 10 };
-enum { KERN_CHAIN = 0, KERN_SCORE = 1, KERN_PREP = 2, KERN_TABLE = 3 /* token_table_kernel (farnn_tag_vectors) */, KERN_COUNT = 4 };
+enum { KERN_CHAIN = 0, KERN_SCORE = 1, KERN_PREP = 2, KERN_TABLE = 3 /* token_table_kernel / token_blocks_kernel (farnn_tag_vectors) */, KERN_COUNT = 4 };
 
 struct Prof {
     std::vector<hipEvent_t> ev[KERN_COUNT];   // (start, stop) pairs
@@ -44,9 +44,10 @@ struct Workspace {
     float *d1_br = nullptr;                 // [B*L][MT][NT*16] per-row-tile partial output-rank vectors (decomposed independent=1)
     float *tt = nullptr;                    // [B*L][tvl] the call's token table (a vector-input handle: decomp_vec.hip.h)
     int64_t *ids = nullptr;                 // [B*L] ids[i] = i: the identity ids its recurrence runs on
+    float *tbf = nullptr, *tbb = nullptr;   // [tokens][SR][SP] the call's token blocks and their transposes (a max-semiring vector-input handle)
     int B = 0, L = 0;                       // CAPACITY: sequences, positions
     void release() {
-        for (void *p : {(void *)A, (void *)Bk, (void *)offs, (void *)order, (void *)hs, (void *)crf_scores, (void *)d1_br, (void *)tt, (void *)ids})
+        for (void *p : {(void *)A, (void *)Bk, (void *)offs, (void *)order, (void *)hs, (void *)crf_scores, (void *)d1_br, (void *)tt, (void *)ids, (void *)tbf, (void *)tbb})
             if (p) (void)hipFree(p);
         *this = Workspace();
     }
@@ -95,6 +96,11 @@ struct farnn_model {
     int chain_ks = 3;
     bool dense_decomp = false;              // decomposed model served by dense per-word blocks + chain_kernel
     bool sf = false;                        // vector input (farnn_decomp_sf_create): no word table, V = 0; farnn_tag_vectors builds a token table per call
+    // ... in the max semiring (farnn_decomp_sf_max_create): per call one S x S block per token (token_blocks_kernel) in front of the
+    // dense chain kernels where sf_dense (farnn = 0 and the chain geometry holds the model), up to sf_block_tokens positions a call;
+    // else the padded copy of v (token_table_kernel<false>) under decomp_chain_kernel
+    bool sf_max = false, sf_dense = false;
+    long long sf_block_tokens = 0;
     int profiling = 0;          // 0 off, N>0: time every N-th farnn_tag call
     long long calls = 0;
     int prof_this_call = 0;

@@ -46,6 +46,9 @@ struct TagPlan {
     // runs on the identity ids with V = B L
     bool table = false;
     int table_cols = 0;                     // its gate columns: 0 (farnn = 0: the padded copy alone), SP or 2 SP
+    // ---- the token blocks of a max-semiring vector-input call: token_blocks_kernel in front of the dense chain kernels, which then
+    // read the workspace's blocks on the identity ids with V = B L
+    bool blocks = false;
     // ---- recurrence
     int rec = REC_CHAIN_KERNEL;
     bool fused = false;                     // scores + decode beside the recurrence: the call's ONE launch

@@ -21,7 +21,7 @@ def default_device():
     return torch.cuda.current_device() if torch.cuda.is_available() else 0
 
 
-# The opt-in switches of the training steps (each opt-in for its first release), all read through opted_in():
+# The opt-in switches of the training steps and of new tagging forms (each opt-in for its first release), all read through opted_in():
 #   RE2NN_<name>=1            what it opens                                                                   DESIGN.md row
 #   ONEHOT_MAX_TRAIN          --train_mode max for the onehot i-FST (FARNN_S_O_I_S)                           f5
 #   ONEHOT_FST_TRAIN          the onehot FST's training step (FARNN_S_O)                                      f7
@@ -38,6 +38,7 @@ def default_device():
 #   DECOMP_TEACHER_TRAIN      the KD / PR teacher terms of the decomposed i-FST (--marryup_type kd | pr)      f3
 #   DECOMP_TEACHER_MAX_TRAIN  those terms under --train_mode max, beside DECOMP_TEACHER_TRAIN                 f3
 #   SF_TRAIN                  the vector-input tagger's training step (FARNN_S_SF, FARNN_S_bert; sum semiring)  f14
+#   SF_MAX                    the vector-input tagger under --train_mode max: tagging only (FARNN_S_SF, FARNN_S_bert) f14
 #   NATIVE_OPTIM              the library's one-launch Adam / SGD in train_onehot.train_epochs                f6
 #   DEVICE_METRICS            an epoch's loss and TRAIN metrics counted on the device and read once, in
 #                             train_onehot.train_epochs (metrics/device.py; evaluation stays on the host path) f10

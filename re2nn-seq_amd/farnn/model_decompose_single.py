@@ -271,7 +271,8 @@ class FARNN_S_SF(Trainable, NativeTagger):
     one library call as well (farnn_decomp_sf_train_step): forward(..., train=True) returns a loss that autograd connects to
     the trainable weights AND to ``input``, so that whatever produced the vectors (an encoder, EmbedAggregator's bridge matrix)
     is fine-tuned through the automaton.  Scope: the sum semiring, farnn 0 / 1 / 2, CE1 or the CRF, the priority layer; no KD /
-    PR teacher.  Opt-in for its first release: RE2NN_SF_TRAIN=1."""
+    PR teacher.  Opt-in for its first release: RE2NN_SF_TRAIN=1.  --train_mode max (ref :435-442) tags only
+    (farnn_decomp_sf_max_create), under RE2NN_SF_MAX=1; its training is not built."""
     _param_keys = _SF_PARAM_KEYS
     # which tensors get a gradient: the reference's requires_grad flags (ref :343-346, :357-401)
     _TRAIN_FLAGS = {'S1': None, 'S2': None, 'C_output_mat': 'train_c_output', 'wildcard_mat': 'train_wildcard',
@@ -337,7 +338,7 @@ class FARNN_S_SF(Trainable, NativeTagger):
                  final_vector=None, start_vector=None, priority_mat=None, args=None, o_idx=0, is_cuda=True):
         super().__init__(args, o_idx)
         a = args
-        if a.train_mode == 'max':
+        if a.train_mode == 'max' and not opted_in('SF_MAX'):
             raise NotImplementedError('FARNN_S_SF: --train_mode max needs an S x S block per token; the vector-input tagger exists '
                                       'in the sum semiring only (DESIGN.md, row f14)')
         t = lambda x: torch.from_numpy(np.asarray(x)).float()      # noqa: E731
@@ -389,12 +390,14 @@ class FARNN_S_SF(Trainable, NativeTagger):
             raise NotImplementedError('only CE1 is reachable from main.py (:127)')
         gates = {k: (getattr(self, k).reshape(-1) if k.startswith('bs') else getattr(self, k)).numpy()
                  for k in _GATE_KEYS if hasattr(self, k)}
-        return _lib.create_decomp_sf(
-            self.S1.numpy(), self.S2.numpy(), self.wildcard_mat.numpy(), self.C_output_mat.numpy(), self.h0.numpy(),
-            self.hT.numpy(), P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
-            sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear, semiring='sum', threshold=a.threshold,
-            o_idx=self.o_idx, use_crf=self.use_crf,
-            crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(), device=self.device_index)
+        kw = dict(P=self.priority_full if a.use_priority else None, farnn=a.farnn, gates=gates,
+                  sigmoid_exponent=a.sigmoid_exponent, nl=a.update_nonlinear, threshold=a.threshold,
+                  o_idx=self.o_idx, use_crf=self.use_crf,
+                  crf_trans=None if self.crf_transitions is None else self.crf_transitions.numpy(), device=self.device_index)
+        w = (self.S1.numpy(), self.S2.numpy(), self.wildcard_mat.numpy(), self.C_output_mat.numpy(), self.h0.numpy(), self.hT.numpy())
+        if a.train_mode == 'max':      # (constructed under RE2NN_SF_MAX=1 only)
+            return _lib.create_decomp_sf_max(*w, **kw)
+        return _lib.create_decomp_sf(*w, semiring='sum', **kw)
 
     def run_vectors(self, input, lengths, want_tags=False, want_flat=False, want_scores=False):
         """One farnn_tag_vectors() call on input[:, :lengths.max()] (ref :497: L = lengths.max()).  A view that is not
@@ -420,6 +423,9 @@ class FARNN_S_SF(Trainable, NativeTagger):
         """(loss, flat_pred, flat_true) of ref :483-579; the loss is None with train=False.  train=True (under RE2NN_SF_TRAIN=1):
         the loss carries a gradient towards ``input`` and the trainable weights (parameters())."""
         if train:
+            if self.args.train_mode == 'max':
+                raise NotImplementedError('FARNN_S_SF: --train_mode max is built for tagging only; its training step needs dM per '
+                                          'token and is not built (DESIGN.md, row f14); call forward(..., train=False)')
             if not opted_in('SF_TRAIN'):
                 raise NotImplementedError('FARNN_S_SF: training needs d loss / d input for the encoder in front of it and is not '
                                           'built (DESIGN.md, row f14); call forward(..., train=False)')
